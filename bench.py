@@ -17,7 +17,8 @@ are independent).  One RCCL gather per step collects the result shards on rank 0
 after EVERY step inside the timed region (`--gather step`, default: K steps = K gathered result sets,
 each gather overlapped with the next step's compute); `--gather job` gathers only the last step's shards,
 `--gather none` leaves the results sharded.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes what the last timed step returned on rank 0 as
+DIR/<name>.npy (dump_outputs below); the inputs are fixed, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -43,6 +44,39 @@ def level_bytes(D, deg0, lev):
     """One level of SURVEY 8(d)'s model: 4 n input polynomials of degree d read, 4 n/2 of degree 2d written."""
     n, d = D >> lev, deg0 << lev
     return 64 * (n * (d + 1) + (n // 2) * (2 * d + 1))
+
+
+DUMP_BYTES = 64 * 10**6 - 4096   # --dump-outputs: bytes of array data in all (64 MB less room for the .npy headers)
+DUMP_SEED = 0x5EED      # --dump-outputs: seed of the signal sample taken when the outputs exceed DUMP_BYTES
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: write what the timed path returned in its last step as DIR/<name>.npy.  Complex arrays are
+    stored as float64 with a trailing [re, im] axis; real arrays as float64.  Arrays of a batched path have the signal
+    as their leading axis: when all of them together exceed DUMP_BYTES, every array keeps the same fixed sample of
+    signals (drawn with DUMP_SEED, in ascending order), and DIR/signals.npy lists their indices.
+    Returns {name: shape} of the files written."""
+    real = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a)
+        real[name] = a.view(np.float64).reshape(a.shape + (2,)) if np.iscomplexobj(a) else a.astype(np.float64)
+    total = sum(a.nbytes for a in real.values())
+    if total > DUMP_BYTES:
+        n = {a.shape[0] for a in real.values()}
+        if len(n) != 1 or n.pop() < 2:
+            raise SystemExit("--dump-outputs: %d bytes of outputs without a common signal axis to sample" % total)
+        nsig = next(iter(real.values())).shape[0]
+        per_signal = total // nsig
+        keep = (DUMP_BYTES - 8 * nsig) // per_signal
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nsig, size=keep, replace=False))
+        real = {name: a[rows] for name, a in real.items()}
+        real["signals"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in real.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in real.items()}
 
 
 def launch_breakdown(plan, run_once, reps, B, D, deg0, sync=None):
@@ -138,7 +172,7 @@ def bench_cfg4(args, rank, world, local_rank):
     D = M = 1 << args.log2D
     T, XI = [-25.0, 25.0], [-7.0 / 5.0, 8.0 / 5.0]
     q = S.sech_focusing(D, amp=3.2 - 0.01 * rank)
-    steps, warm = max(1, min(args.steps, 10)), max(1, min(args.warmup, 2))
+    steps, warm = args.steps, max(1, min(args.warmup, 2))
 
     # the caller's arrays, allocated once as in the reference's example (examples/fnft_nsev_example.c)
     capK = 2 * D   # fnft_nsev_max_K for 2SPLIT4B
@@ -171,6 +205,10 @@ def bench_cfg4(args, rank, world, local_rank):
     ms_per_step = float(tt.item()) / steps
     if rank == 0:
         rc, bs, nc, res, cs = out
+        dumped = None
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, {"bound_states": bs, "normconsts": nc, "residues": res,
+                                                      "rho": cs[:M], "a": cs[M:2 * M], "b": cs[2 * M:]})
         exact = np.array([0.7j, 1.7j, 2.7j])
         # tree of the continuous-spectrum part (2SPLIT4B, deg 2) timed on a device plan, as in the headline workload
         plan = capi.Plan(D, M, batch=1, discretization="2SPLIT4B", device=local_rank)
@@ -236,6 +274,8 @@ def bench_cfg4(args, rank, world, local_rank):
                                                if bs.size else None)},
             "cpu_baseline": cpu, "build_id": bid4,
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -271,7 +311,7 @@ def bench_inverse(args, rank, world, local_rank):
         if rc != 0:
             raise RuntimeError("fnft_nsev_inverse rc=%d: %s" % (rc, capi.last_error()))
         return q
-    steps, warm = max(1, min(args.steps, 10)), max(1, min(args.warmup, 2))
+    steps, warm = args.steps, max(1, min(args.warmup, 2))
     for _ in range(warm):
         q = call()
     torch.cuda.synchronize()
@@ -289,6 +329,7 @@ def bench_inverse(args, rank, world, local_rank):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     ms_per_step = float(tt.item()) / steps
     if rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"q": q}) if args.dump_outputs else None
         cpu = None
         if not args.no_cpu_baseline and world == 1:
             from oracle import inverse as INV
@@ -331,6 +372,8 @@ def bench_inverse(args, rank, world, local_rank):
                          "rel_err_vs_exact_signal": float(S.rel_err(q, exact))},
             "cpu_baseline": cpu,
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -432,7 +475,13 @@ def main():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="N>1 control-flow rehearsal on a box with fewer GPUs than ranks: gloo backend, "
                          "host-staged gather, ranks share the visible GPUs (not a measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, "
+                         "complex values as a trailing [re, im] axis; rank 0's own signals; at most 64 MB, a fixed "
+                         "seeded sample of the signals of a larger batch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     workload_given = args.workload is not None
     if args.workload is None:
         args.workload = "cfg2"
@@ -574,6 +623,11 @@ def main():
     rc = plan.finish(stream)
     if rc != 0:
         raise RuntimeError("device status rc=%d: %s" % (rc, capi.last_error()))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the buffer of the last timed step, [signal][rho | a | b][M], before any later pass writes to it
+        res = outs[(args.steps - 1) % 2].view(B, nout, M).cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, {name: res[:, j] for j, name in enumerate(("rho", "a", "b")[:nout])})
 
     t_all = torch.tensor([wall_ms], dtype=torch.float64, device="cpu" if args.rehearse_gloo else "cuda")
     if world > 1:
@@ -763,6 +817,8 @@ def main():
         }
         if multi:
             line["multi_gpu"] = multi
+        if dumped:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
