@@ -740,8 +740,13 @@ class Plan:
     def transfer_matrix(self, b=0):
         deg = C.c_size_t(0)
         W = C.c_int32(0)
-        # deg is D*deg0; allocate for the largest supported deg0 = 4
-        buf = np.zeros(4 * (4 * self.D + 1), np.complex128)
+        # deg is (matrices in the tree) * (degree per matrix) = degree(discretization) * D * upsampling: the 4SPLIT
+        # schemes resample to two matrices per kept step (round(D / nskip) <= D of them); the order 5..8 schemes have
+        # degrees up to 105
+        opts = default_opts()
+        opts.discretization = self.disc
+        ups = 2 if self.disc in (NSE_DISC["4SPLIT4A"], NSE_DISC["4SPLIT4B"]) else 1
+        buf = np.zeros(4 * (ups * int(self.L.fnft_nsev_max_K(self.D, C.byref(opts))) + 1), np.complex128)
         rc = self.L.fnft_amd_plan_get_transfer_matrix(self.h, b, _ptr(buf), C.byref(deg), C.byref(W))
         d = deg.value
         return int(rc), d, buf[: 4 * (d + 1)].reshape(4, d + 1).copy(), int(W.value)

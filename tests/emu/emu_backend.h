@@ -3,13 +3,31 @@
 // block per workgroup.  It exists to check the index arithmetic of the kernel bodies in
 // fnft_amd/csrc/nft_kernels.h without a GPU; it is never part of libfnft_amd.so.
 #pragma once
+#include <cxxabi.h>
+
 #include <barrier>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
+#include <typeinfo>
 #include <vector>
 
 #include "../../fnft_amd/csrc/dev_compat.h"
+
+// schedule-only mode: while this points to a list, run<K> appends the demangled name of K ("KPairFft<2048, 4>") and
+// executes nothing.  Buffers come from calloc, whose large blocks are mapped lazily, so the schedule of a tree of any
+// supported size costs next to no memory or time.
+inline std::vector<std::string> *emu_schedule = nullptr;
+
+template <class K> std::string emu_kernel_name()
+{
+    int st = 0;
+    char *d = abi::__cxa_demangle(typeid(K).name(), nullptr, nullptr, &st);
+    std::string s = (st == 0 && d) ? d : typeid(K).name();
+    std::free(d);
+    return s;
+}
 
 struct EmuBackend {
     static constexpr size_t kTargetWorkgroups = 8;   // every emulated workgroup is a set of host threads
@@ -23,6 +41,10 @@ struct EmuBackend {
 
     template <class K> void run(int gx, int gy, const typename K::Params &p)
     {
+        if (emu_schedule) {
+            emu_schedule->push_back(emu_kernel_name<K>());
+            return;
+        }
         const int T = K::THREADS;
         const size_t lds = K::lds_bytes();
         std::vector<unsigned char> ldsbuf(lds + 64);

@@ -201,4 +201,60 @@ int emu_poly_roots(size_t deg, const std::complex<double> *p, std::complex<doubl
     return rc;
 }
 
+// Schedule of the product tree without executing it (schedule-only mode of EmuBackend): the names of every kernel
+// the plan launches, '\n'-separated, into out[cap].  Returns the plan's rc, or -1 if out is too small.
+//   entry 0: fnft__poly_fmult2x2, D matrices of degree `disc` (general form)
+//   entry 1: fnft_amd_plan / fnft_nsev, D samples per signal, `batch` signals, nse discretization `disc`
+//   entry 2: fnft__akns_fscatter with an explicit r (general form), akns discretization `disc`
+//   entry 3: fnft__kdv_fscatter, kdv discretization `disc`; real != 0: a real potential (real-coefficient tree)
+int emu_tree_schedule(int entry, size_t D, int disc, size_t batch, int real, char *out, size_t cap)
+{
+    EmuBackend be;
+    std::vector<std::string> names;
+    emu_schedule = &names;
+    int akns = -1, deg0 = disc, ups = 1;
+    size_t Dtree = D;
+    if (entry == 1) {
+        akns = nft_nse_to_akns(disc);
+        ups = nft_nse_upsampling(disc);
+        Dtree = (ups == 1) ? D : 2 * NftPlan<EmuBackend>::sub_count(D, 1);
+    } else if (entry == 2) {
+        akns = disc;
+    } else if (entry == 3) {
+        akns = disc + 1;
+    }
+    if (entry != 0) deg0 = akns >= 0 ? nft_akns_degree(akns) : 0;
+    int rc = NFT_EC_INVALID_ARGUMENT;
+    if (deg0 > 0 && D > 0 && batch > 0) {
+        NftPlan<EmuBackend> pl(be, Dtree, 0, entry == 1 ? batch : 1, akns, deg0);
+        if (entry == 1) pl.set_front(D, 1, ups);
+        pl.kdv = entry == 3;
+        pl.want_real = entry == 3 && real != 0;
+        rc = pl.init();
+        // any non-null address: the kernels that would read it are not executed
+        cplx *dummy = (cplx *)be.alloc(16);
+        const double T[2] = {-1.0, 1.0};
+        double Tsub[2];
+        if (rc == NFT_SUCCESS) {
+            switch (entry) {
+            case 0: rc = pl.load_level0_from_device(dummy); break;
+            case 1: rc = pl.run_front(dummy, T, 1, Tsub); break;
+            case 2: rc = pl.run_coeffs(dummy, dummy, 1e-3, 1); break;
+            case 3: rc = pl.run_coeffs(dummy, pl.rneg, 1e-3, 1); break;
+            default: rc = NFT_EC_INVALID_ARGUMENT;
+            }
+        }
+        if (rc == NFT_SUCCESS) rc = pl.run_tree();
+        if (rc == NFT_SUCCESS) pl.export_tm();
+        be.free(dummy);
+        pl.destroy();
+    }
+    emu_schedule = nullptr;
+    std::string s;
+    for (const auto &n : names) s += n + "\n";
+    if (s.size() + 1 > cap) return -1;
+    std::memcpy(out, s.c_str(), s.size() + 1);
+    return rc;
+}
+
 }  // extern "C"
