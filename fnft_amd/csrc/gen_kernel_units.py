@@ -8,9 +8,9 @@ is launched but missing here fails at link time (-z defs).  Run after changing a
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-N1_ALL = [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
+N1_ALL = [4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
 N1_CHIRP = [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
-N1_BR = [2, 4, 8, 16, 32, 64, 128, 256, 512]
+N1_BR = [4, 8, 16, 32, 64, 128, 256, 512]
 PF = [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096]
 
 groups = {}
@@ -21,22 +21,20 @@ g += ["KLeaf<%d>" % d for d in (1, 2, 3, 4)] + ["KPairSchool<%d>" % d for d in (
 groups["misc"] = g
 groups["pair4a"] = ["KPairFft<%d, 4>" % n for n in PF if n <= 256]
 groups["pair4b"] = ["KPairFft<%d, 4>" % n for n in PF if 256 < n <= 1024]
-groups["pair4c"] = ["KPairFft<%d, 4>" % n for n in PF if n > 1024] + ["KMid<4>"]
-groups["pair2"] = ["KPairFft<%d, 2>" % n for n in PF]
-groups["multi3a"] = ["KMulti<%d, 3>" % n for n in (16, 32, 64, 128)]
-groups["multi3b"] = ["KMulti<%d, 3>" % n for n in (256, 512, 1024)]
-groups["multi2"] = ["KMulti<%d, 2>" % n for n in (16, 32, 64, 128, 256, 512, 1024, 2048)]
+groups["pair4c"] = ["KPairFft<2048, 4>"]
+groups["pair2"] = ["KPairFft<%d, 2>" % n for n in PF if n >= 16]
+groups["multi3"] = ["KMulti<%d, 3>" % n for n in (128, 1024)]
+groups["multi2"] = ["KMulti<%d, 2>" % n for n in (128, 1024)]
 groups["leafmulti"] = ["KLeafMulti<%d, %d>" % (d, s) for s in (3, 2) for d in (1, 2, 4)]
 groups["mid"] = ["KMidSym<true>", "KMidSym<false>"]
 groups["col"] = ["KColFwd<%d>" % n for n in N1_ALL] + ["KColInv<%d>" % n for n in N1_ALL]
-groups["bridge"] = ["KColBridge<%d>" % n for n in N1_BR] + ["KColBridge2<%d>" % n for n in N1_BR + [1024, 2048, 4096]]
-groups["realpair"] = ["KRealCheck", "KRCoeffsStrang<6, false>", "KRCoeffsStrang<6, true>", "KRCoeffsStrang<8, false>", "KRCoeffsStrang<8, true>"] + ["KRPairSchool<%d>" % d for d in (1, 2, 3)] + ["KRPair<%d>" % m for m in (4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048)]
+groups["bridge"] = ["KColBridge2<%d>" % n for n in N1_BR + [1024, 2048, 4096]]
+groups["realpair"] = ["KRealCheck", "KRCoeffsStrang<6, false>", "KRCoeffsStrang<6, true>", "KRCoeffsStrang<8, false>", "KRCoeffsStrang<8, true>"] + ["KRPairSchool<%d>" % d for d in (1, 2)] + ["KRPair<%d>" % m for m in (8, 16, 1024, 2048)]
 groups["realpair4"] = ["KRPair4<%d>" % m for m in (32, 64, 128, 256, 512)]
-N1_RCOL = [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096]
-groups["realcol"] = ["KRColFwd<%d>" % n for n in N1_RCOL] + ["KRColInv<%d>" % n for n in N1_RCOL]
+groups["realcol"] = ["KRColFwd<4>", "KRColFwd<4096>"] + ["KRColInv<%d>" % n for n in N1_ALL if n <= 4096]
 groups["realbridge"] = ["KRBridge<%d>" % n for n in N1_BR + [1024]] + ["KMidGen<1024>", "KMidGen<2048>"]
 K3 = [1, 2, 4, 8, 16, 32, 64, 128, 256]
-groups["real3col"] = ["KR3ColFwd<%d>" % k for k in K3 + [512]] + ["KR3ColInv<%d>" % k for k in K3 + [512]]
+groups["real3col"] = ["KR3ColFwd<1>"] + ["KR3ColInv<%d>" % k for k in K3 + [512]]
 groups["real3bridge"] = ["KR3Bridge<%d>" % k for k in K3]
 groups["realleaf"] = ["KRLeafStrang<6, false>", "KRLeafStrang<6, true>", "KRLeafStrang<8, false>", "KRLeafStrang<8, true>"]
 groups["chirpa"] = ["KChirpRows"] + ["KChirpColFwd<%d, false>" % n for n in N1_CHIRP] + ["KChirpColFwd<%d, true>" % n for n in N1_CHIRP]

@@ -318,7 +318,7 @@ double fnft_amd_plan_launch_ms(const fnft_amd_plan_t *plan, FNFT_UINT i, char *n
     if (!plan || i >= plan->be.launches_used) return -1.0;
     const HipBackend::LaunchRec &r = plan->be.launches[i];
     if (name && name_cap) {
-        // __PRETTY_FUNCTION__ of run<K>: "... [K = KMid<2>]"
+        // __PRETTY_FUNCTION__ of run<K>: "... [K = KMidSym<true>]"
         const char *k = strstr(r.name, "K = ");
         k = k ? k + 4 : r.name;
         size_t n = strlen(k);

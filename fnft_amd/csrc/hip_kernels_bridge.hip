@@ -2,16 +2,6 @@
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
 
-FA_INST(KColBridge<2>)
-FA_INST(KColBridge<4>)
-FA_INST(KColBridge<8>)
-FA_INST(KColBridge<16>)
-FA_INST(KColBridge<32>)
-FA_INST(KColBridge<64>)
-FA_INST(KColBridge<128>)
-FA_INST(KColBridge<256>)
-FA_INST(KColBridge<512>)
-FA_INST(KColBridge2<2>)
 FA_INST(KColBridge2<4>)
 FA_INST(KColBridge2<8>)
 FA_INST(KColBridge2<16>)

@@ -2,7 +2,6 @@
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
 
-FA_INST(KPairFft<8, 2>)
 FA_INST(KPairFft<16, 2>)
 FA_INST(KPairFft<32, 2>)
 FA_INST(KPairFft<64, 2>)

@@ -3,5 +3,3 @@
 #include "hip_be.h"
 
 FA_INST(KPairFft<2048, 4>)
-FA_INST(KPairFft<4096, 4>)
-FA_INST(KMid<4>)

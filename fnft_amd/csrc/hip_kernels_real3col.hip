@@ -3,15 +3,6 @@
 #include "hip_be.h"
 
 FA_INST(KR3ColFwd<1>)
-FA_INST(KR3ColFwd<2>)
-FA_INST(KR3ColFwd<4>)
-FA_INST(KR3ColFwd<8>)
-FA_INST(KR3ColFwd<16>)
-FA_INST(KR3ColFwd<32>)
-FA_INST(KR3ColFwd<64>)
-FA_INST(KR3ColFwd<128>)
-FA_INST(KR3ColFwd<256>)
-FA_INST(KR3ColFwd<512>)
 FA_INST(KR3ColInv<1>)
 FA_INST(KR3ColInv<2>)
 FA_INST(KR3ColInv<4>)

@@ -2,7 +2,6 @@
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
 
-FA_INST(KRBridge<2>)
 FA_INST(KRBridge<4>)
 FA_INST(KRBridge<8>)
 FA_INST(KRBridge<16>)

@@ -2,19 +2,8 @@
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
 
-FA_INST(KRColFwd<2>)
 FA_INST(KRColFwd<4>)
-FA_INST(KRColFwd<8>)
-FA_INST(KRColFwd<16>)
-FA_INST(KRColFwd<32>)
-FA_INST(KRColFwd<64>)
-FA_INST(KRColFwd<128>)
-FA_INST(KRColFwd<256>)
-FA_INST(KRColFwd<512>)
-FA_INST(KRColFwd<1024>)
-FA_INST(KRColFwd<2048>)
 FA_INST(KRColFwd<4096>)
-FA_INST(KRColInv<2>)
 FA_INST(KRColInv<4>)
 FA_INST(KRColInv<8>)
 FA_INST(KRColInv<16>)

@@ -9,14 +9,7 @@ FA_INST(KRCoeffsStrang<8, false>)
 FA_INST(KRCoeffsStrang<8, true>)
 FA_INST(KRPairSchool<1>)
 FA_INST(KRPairSchool<2>)
-FA_INST(KRPairSchool<3>)
-FA_INST(KRPair<4>)
 FA_INST(KRPair<8>)
 FA_INST(KRPair<16>)
-FA_INST(KRPair<32>)
-FA_INST(KRPair<64>)
-FA_INST(KRPair<128>)
-FA_INST(KRPair<256>)
-FA_INST(KRPair<512>)
 FA_INST(KRPair<1024>)
 FA_INST(KRPair<2048>)

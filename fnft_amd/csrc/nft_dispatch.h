@@ -291,27 +291,7 @@ template <int N1> struct KColInv {
     static constexpr size_t lds_bytes() { return C::lds_bytes(); }
     static FA_DEV void body(const Params &p) { body_col_inv<N1, C::R, C::BC, C::DB>(p); }
 };
-#ifndef FA_BRIDGE_R
-#define FA_BRIDGE_R 16
-#endif
-#ifndef FA_BRIDGE_T
-#define FA_BRIDGE_T 256
-#endif
-template <int N1> struct BridgeCfg {
-    static constexpr int R = (N1 <= 16) ? N1 : FA_BRIDGE_R;
-    static constexpr int THREADS = (N1 <= 16) ? 256 : FA_BRIDGE_T;
-    static constexpr int BC = THREADS / (N1 / R);
-    static constexpr bool DB = false;
-    static constexpr size_t lds_bytes() { return (N1 > R) ? (size_t)2 * N1 * BC * sizeof(cplx) : 0; }
-};
-template <int N1> struct KColBridge {
-    using Params = BigLevel;
-    using C = BridgeCfg<N1>;
-    static constexpr int THREADS = C::THREADS;
-    static constexpr size_t lds_bytes() { return C::lds_bytes(); }
-    static FA_DEV void body(const Params &p) { body_col_bridge<N1, C::R, C::BC, C::DB>(p); }
-};
-template <int N1> struct KColBridge2 {   // spectral doubling: same tiling as the plain column steps
+template <int N1> struct KColBridge2 {   // bridge with spectral doubling: same tiling as the plain column steps
     using Params = BigLevel;
     using C = ColCfg<N1>;
     static constexpr int THREADS = C::THREADS;
@@ -321,21 +301,6 @@ template <int N1> struct KColBridge2 {   // spectral doubling: same tiling as th
 #ifndef FA_MID_R
 #define FA_MID_R 8   // points per lane of the row kernel (4: 512 lanes per row, 4 waves per SIMD)
 #endif
-#ifndef FA_MID4_R
-#define FA_MID4_R 4   // points per lane of the general 4-entry row kernel: 512 lanes per row, 232 VGPRs, 2 waves per SIMD
-                     // (8: 256 lanes, 394-410 VGPRs, 1 wave per SIMD; cfg 5 row kernel 390 -> 345 us)
-#endif
-template <int NE> struct KMid {
-    using Params = BigLevel;
-    static constexpr int R = (NE == 4) ? FA_MID4_R : FA_MID_R;
-    static constexpr int THREADS = kRowTree / R;
-#ifndef FA_MID4_WAVES
-#define FA_MID4_WAVES 1   // general 4-entry form: 1 = 394 VGPRs, no spills (2: 186 spilled); cfg 5 split levels 6.35 -> 6.17 ms
-#endif
-    static constexpr int MIN_WAVES = (NE == 4) ? (R == 4 ? 2 : FA_MID4_WAVES) : (R == 4 ? 4 : 2);
-    static constexpr size_t lds_bytes() { return (size_t)2 * kRowTree * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_mid<kRowTree, R, NE>(p); }
-};
 template <int N1, bool DFT = false> struct KChirpColFwd {
     using Params = ChirpParams;
     using C = ChirpColCfg<N1>;
@@ -415,12 +380,23 @@ template <class BE> bool dispatch_pair_school(BE &be, const TreeLevel &L)
     }
 }
 
-template <class BE, int N> void run_pair_fft(BE &be, const TreeLevel &L)
+// the general form fuses pair products up to N = 2048 (NftPlan::fused_max_len); the symmetric form starts at degree
+// >= 6 (leaf kernel or coefficient program), so at N >= 16
+template <class BE, int N> bool run_pair_fft(BE &be, const TreeLevel &L)
 {
     const int pairs = L.n_in / 2;
-    constexpr int B4 = PairCfg<N, 4>::B, B2 = PairCfg<N, 2>::B;
-    if (L.ne == 4) be.template run<KPairFft<N, 4>>((pairs + B4 - 1) / B4, 1, L);
-    else be.template run<KPairFft<N, 2>>((pairs + B2 - 1) / B2, 1, L);
+    if (L.ne == 4) {
+        if constexpr (N <= 2048) {
+            constexpr int B = PairCfg<N, 4>::B;
+            be.template run<KPairFft<N, 4>>((pairs + B - 1) / B, 1, L);
+            return true;
+        }
+    } else if constexpr (N >= 16) {
+        constexpr int B = PairCfg<N, 2>::B;
+        be.template run<KPairFft<N, 2>>((pairs + B - 1) / B, 1, L);
+        return true;
+    }
+    return false;
 }
 // STAGES levels in one launch (symmetric form): T = 256 lanes (512 when the last stage is 4096 long)
 template <int N0, int STAGES> struct MultiCfg {
@@ -479,12 +455,12 @@ template <class BE> bool dispatch_leaf_multi(BE &be, const LeafMultiParams &Q, i
 #undef X
     return false;
 }
-// N: transform length of the first of the `stages` levels
+// N: transform length of the first of the `stages` levels.  The leaf kernel fused into the first launch
+// (KLeafMulti) takes the levels from N = 16, so the launches that follow start at N = 128 and 1024
 template <class BE> bool dispatch_multi(BE &be, const TreeLevel &L, int N, int stages)
 {
 #define X(n0, st) if (N == n0 && stages == st) { be.template run<KMulti<n0, st>>((L.n_in + 2 * MultiCfg<n0, st>::P0 - 1) / (2 * MultiCfg<n0, st>::P0), 1, L); return true; }
-    X(16, 3) X(32, 3) X(64, 3) X(128, 3) X(256, 3) X(512, 3) X(1024, 3)
-    X(16, 2) X(32, 2) X(64, 2) X(128, 2) X(256, 2) X(512, 2) X(1024, 2) X(2048, 2)
+    X(128, 3) X(1024, 3) X(128, 2) X(1024, 2)
 #undef X
     return false;
 }
@@ -497,42 +473,33 @@ template <bool DIRECT> struct KMidSym {
     static constexpr size_t lds_bytes() { return (size_t)2 * kRowTree * sizeof(cplx); }
     static FA_DEV void body(const Params &p) { body_mid_sym<kRowTree, R, DIRECT>(p); }
 };
-#ifndef FA_MID_SYM
-#define FA_MID_SYM 1   // 0: the generic-IO row kernel (KMid<2>) for the symmetric form as well
-#endif
-#ifndef FA_MID_GEN
-#define FA_MID_GEN 1   // 0: the generic-IO row kernel KMid<4> for the general form
-#endif
 template <class BE> void run_mid_gen(BE &be, int g, const BigLevel &G);
 template <class BE> void run_mid(BE &be, const BigLevel &G)
 {
     const int g = (G.L.n_in / 2) * G.N1;
-    if (G.L.ne == 4) {
-        if constexpr (FA_MID_GEN) run_mid_gen(be, g, G);
-        else be.template run<KMid<4>>(g, 1, G);
-    }
-    else if constexpr (!FA_MID_SYM) be.template run<KMid<2>>(g, 1, G);
+    if (G.L.ne == 4) run_mid_gen(be, g, G);
     else if (G.y_direct) be.template run<KMidSym<true>>(g, 1, G);
     else be.template run<KMidSym<false>>(g, 1, G);
 }
 template <class BE> bool dispatch_pair_fft(BE &be, const TreeLevel &L, int N)
 {
     switch (N) {
-    case 8: run_pair_fft<BE, 8>(be, L); return true;
-    case 16: run_pair_fft<BE, 16>(be, L); return true;
-    case 32: run_pair_fft<BE, 32>(be, L); return true;
-    case 64: run_pair_fft<BE, 64>(be, L); return true;
-    case 128: run_pair_fft<BE, 128>(be, L); return true;
-    case 256: run_pair_fft<BE, 256>(be, L); return true;
-    case 512: run_pair_fft<BE, 512>(be, L); return true;
-    case 1024: run_pair_fft<BE, 1024>(be, L); return true;
-    case 2048: run_pair_fft<BE, 2048>(be, L); return true;
-    case 4096: run_pair_fft<BE, 4096>(be, L); return true;
+    case 8: return run_pair_fft<BE, 8>(be, L);
+    case 16: return run_pair_fft<BE, 16>(be, L);
+    case 32: return run_pair_fft<BE, 32>(be, L);
+    case 64: return run_pair_fft<BE, 64>(be, L);
+    case 128: return run_pair_fft<BE, 128>(be, L);
+    case 256: return run_pair_fft<BE, 256>(be, L);
+    case 512: return run_pair_fft<BE, 512>(be, L);
+    case 1024: return run_pair_fft<BE, 1024>(be, L);
+    case 2048: return run_pair_fft<BE, 2048>(be, L);
+    case 4096: return run_pair_fft<BE, 4096>(be, L);
     default: return false;
     }
 }
 
-#define FA_FOR_EACH_N1(X) X(2) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
+// N1 = 2 would be a product of length 2*N2 <= 4096, which is fused (kFusedMaxN)
+#define FA_FOR_EACH_N1(X) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
 #define FA_FOR_EACH_CHIRP_N1(X) X(2) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
 
 template <class BE> bool dispatch_col_fwd(BE &be, const BigLevel &G)
@@ -555,17 +522,7 @@ template <class BE> bool dispatch_col_inv(BE &be, const BigLevel &G)
     default: return false;
     }
 }
-#define FA_FOR_EACH_BRIDGE_N1(X) X(2) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512)
-template <class BE> bool dispatch_col_bridge(BE &be, const BigLevel &G)
-{
-    const int polys = G.L.ne * (G.L.n_in / 2);
-    switch (G.N1) {
-#define X(n1) case n1: be.template run<KColBridge<n1>>(G.N2 / BridgeCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_BRIDGE_N1(X)
-#undef X
-    default: return false;
-    }
-}
+#define FA_FOR_EACH_BRIDGE_N1(X) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512)
 template <class BE> bool dispatch_col_bridge2(BE &be, const BigLevel &G)
 {
     const int polys = G.L.ne * (G.L.n_in / 2);
@@ -626,10 +583,7 @@ template <int M> struct KRPair {
     static FA_DEV void body(const Params &p) { body_rpair<M, C::R, C::B, C::DB>(p); }
 };
 // pair product with the four entries of a factor transformed at once (body_rpair4): M = 32 ... 512
-#ifndef FA_RPAIR4
-#define FA_RPAIR4 1
-#endif
-constexpr int kRPair4MinM = 32, kRPair4MaxM = 512;   // (1024 at 8 points per lane: 168 us against 133 for KRPair<1024>)
+// (1024 at 8 points per lane: 168 us against 133 for KRPair<1024>)
 template <int M> struct RPair4Cfg {
     static constexpr int R = (M >= 1024) ? 8 : 4;
     static constexpr int LANES = 4 * (M / R);                              // of one pair
@@ -686,36 +640,32 @@ template <class BE> bool dispatch_rpair_school(BE &be, const TreeLevel &L)
     switch (L.d) {
     case 1: be.template run<KRPairSchool<1>>(g, 1, L); return true;
     case 2: be.template run<KRPairSchool<2>>(g, 1, L); return true;
-    case 3: be.template run<KRPairSchool<3>>(g, 1, L); return true;
-    default: return false;
+    default: return false;   // no d = 3: the leaf kernel starts a tree of degree-3 factors at d = 6
     }
 }
-#define FA_FOR_EACH_RPAIR_M(X) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048)
+// the first FFT level of the real path has M >= 8; KRPair4 takes M = 32 ... 512
 template <class BE> bool dispatch_rpair(BE &be, const TreeLevel &L, int M)
 {
     const int pairs = L.n_in / 2;
-    if (FA_RPAIR4 && M >= kRPair4MinM && M <= kRPair4MaxM) {
-        switch (M) {
-#define X(m) case m: be.template run<KRPair4<m>>((pairs + RPair4Cfg<m>::BP - 1) / RPair4Cfg<m>::BP, 1, L); return true;
-            X(32) X(64) X(128) X(256) X(512)
-#undef X
-        default: break;
-        }
-    }
     switch (M) {
+#define X(m) case m: be.template run<KRPair4<m>>((pairs + RPair4Cfg<m>::BP - 1) / RPair4Cfg<m>::BP, 1, L); return true;
+        X(32) X(64) X(128) X(256) X(512)
+#undef X
 #define X(m) case m: be.template run<KRPair<m>>((pairs + RPairCfg<m>::B - 1) / RPairCfg<m>::B, 1, L); return true;
-        FA_FOR_EACH_RPAIR_M(X)
+        X(8) X(16) X(1024) X(2048)
 #undef X
     default: return false;
     }
 }
-#define FA_FOR_EACH_RCOL_N1(X) X(2) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
+// a forward column step of the real path runs on the first split level, whose length is the first above the fused
+// limit (N1 = 4), and after a level without a bridge, which only the bridge limit kRBridgeMaxN1 causes (KRColInv<2048>,
+// then KRColFwd<4096>)
 template <class BE> bool dispatch_rcol_fwd(BE &be, const BigLevel &G)
 {
     const int polys = 4 * G.L.n_in;
     switch (G.N1) {
 #define X(n1) case n1: be.template run<KRColFwd<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_RCOL_N1(X)
+        X(4) X(4096)
 #undef X
     default: return false;
     }
@@ -725,7 +675,7 @@ template <class BE> bool dispatch_rcol_inv(BE &be, const BigLevel &G)
     const int polys = 4 * (G.L.n_in / 2);
     switch (G.N1) {
 #define X(n1) case n1: be.template run<KRColInv<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_RCOL_N1(X)
+        X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
 #undef X
     default: return false;
     }
@@ -842,7 +792,7 @@ template <class BE> bool dispatch_r3col_fwd(BE &be, const BigLevel &G)
     const int polys = 4 * G.L.n_in;
     switch (G.N1 / 3) {
 #define X(k) case k: be.template run<KR3ColFwd<k>>(G.N2 / R3ColCfg<k>::BC, polys, G); return true;
-        FA_FOR_EACH_R3_K(X) X(512)
+        X(1)   // only the first split level (K = 1): a level without a bridge (K = 512) is the last
 #undef X
     default: return false;
     }

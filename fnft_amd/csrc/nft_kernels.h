@@ -666,8 +666,7 @@ template <int DEG> FA_DEV void body_pair_school(const TreeLevel &L)
 // the HBM traffic, half the registers.  The numbers produced are the ones the general form
 // produces up to rounding (tests compare both with the oracle).
 //
-// IO supplies the loads/stores so that the same body serves a whole tree level (TreeIO) and the
-// row step of a transform that is split across workgroups (MidIO).
+// IO supplies the loads/stores of a whole tree level (TreeIO).
 // ---------------------------------------------------------------------------------------------
 // Twiddle tables are copied into LDS once per workgroup: every radix pass needs r-1 table
 // entries per butterfly, and at 1-2 waves per SIMD a global (L2) fetch per pass is pure stall.
@@ -1327,7 +1326,8 @@ struct BigLevel {
     const cplx *tw1; // table for N1
     const cplx *tw2; // table for N2
     int N1, N2;
-    // bridge to the next level (body_col_bridge): tables for 2*N1 and 2*N, Y holds unscaled data
+    // bridge to the next level (body_col_bridge2, body_rbridge): table for 2*N1, Y holds unscaled data.
+    // btw2 (2*N) is read by no kernel; it stays so that the argument layout of every kernel is unchanged
     const cplx *tw1x2;
     BigTwiddle btw2;
     int y_unscaled;  // row kernel multiplies by scale_in on load
@@ -1436,120 +1436,6 @@ FA_DEV unsigned row_tw_index(const BigLevel &G, int k1, int x)
     return (unsigned)((c1 * (unsigned long long)x) & (len4 - 1ull));                               // a power of two
 }
 
-template <int N2, int R> struct MidIO {
-    const BigLevel &G;
-    long long P;
-    int k1;
-    double sc[2];
-    cplx wu[R];   // workgroup-uniform factors w^{k1 (N2/R) i}: scalar registers
-    cplx wbase;   // per-lane w^{k1 v}
-    FA_DEV MidIO(const BigLevel &G_) : G(G_)
-    {
-        P = FA_BID / G.N1;
-        k1 = FA_BID % G.N1;
-#pragma unroll
-        for (int i = 1; i < R; i++) {
-            const cplx w = big_twiddle(G.btw, row_tw_index(G, k1, (N2 / R) * i));
-            wu[i] = cmake(fa_uniform(w.x), fa_uniform(w.y));
-        }
-        wu[0] = cmake(1.0, 0.0);
-        wbase = big_twiddle(G.btw, row_tw_index(G, k1, FA_TID));
-        sc[0] = (G.y_unscaled || G.y_direct) ? level_in_scale(G.L, 2 * P) : 1.0;
-        sc[1] = (G.y_unscaled || G.y_direct) ? level_in_scale(G.L, 2 * P + 1) : 1.0;
-        // bookkeeping of the level, done once per pair before the column kernel that follows:
-        // exponent carried so far (this level's own is added by the consumer / the final
-        // finalize) and a clean slot for this level's maximum
-        const int wsum = level_in_wexp(G.L, 2 * P) + level_in_wexp(G.L, 2 * P + 1);   // wave-uniform
-        if (k1 == 0 && FA_TID == 0) G.L.wexp_out[P] = wsum;
-        if (k1 == 0 && FA_TID < kMax2Slots) G.L.max2_out[(size_t)P * kMax2Slots + FA_TID] = 0u;
-    }
-    // w_N^{k1 n2} for element n2 = v + (N2/R)*i of this lane (same for every polynomial) =
-    // per-lane look-up w^{k1 v} times the workgroup-uniform factor w^{k1 (N2/R) i}; formed per
-    // element (no register array: the row kernel is at its VGPR budget)
-    FA_DEV cplx twiddle(cplx base, int i) const
-    {
-        return (i == 0) ? base : base * wu[i];
-    }
-    FA_DEV void load(int which, int e, cplx (&x)[R], int v, int)
-    {
-        const int n_in = G.L.n_in;
-        const size_t pi = (size_t)e * n_in + 2 * P + which;
-        if (G.y_direct) {
-            // w_4^{k1} = (-i)^{k1}; element n1 = 2 exists only as the constant term (index 2*N2 = d)
-            const size_t mat = (size_t)(2 * P + which);
-            const cplx *b0 = G.L.body_in + (size_t)e * G.L.plane + mat * (size_t)G.L.d;
-            const cplx tl = G.L.tail_in[(size_t)e * n_in + mat];
-            const cplx base = wbase * sc[which];
-#pragma unroll
-            for (int i = 0; i < R; i++) {
-                const int n2 = v + (N2 / R) * i;
-                const cplx x0 = b0[n2], x1 = b0[N2 + n2];
-                cplx r1;   // x1 * (-i)^k1
-                switch (k1 & 3) {
-                case 0: r1 = x1; break;
-                case 1: r1 = cmake(x1.y, -x1.x); break;
-                case 2: r1 = cmake(-x1.x, -x1.y); break;
-                default: r1 = cmake(-x1.y, x1.x); break;
-                }
-                cplx y = x0 + r1;
-                if (n2 == 0) y = (k1 & 1) ? y - tl : y + tl;
-                x[i] = y * twiddle(base, i);
-            }
-            return;
-        }
-        const cplx *src;
-        int rows, row;
-        if (G.y_split) {
-            const cplx *half = (k1 & 1) ? G.Y : G.Zprev;
-            rows = G.N1 / 2;
-            row = k1 >> 1;
-            src = half + pi * (size_t)rows * N2;
-        } else {
-            rows = G.N1;
-            row = k1;
-            src = G.Y + pi * (size_t)rows * N2;
-        }
-        const cplx base = wbase * sc[which];
-#pragma unroll
-        for (int i = 0; i < R; i++) x[i] = src[yz_index(rows, N2, row, v + (N2 / R) * i)] * twiddle(base, i);
-    }
-    FA_DEV int dbg() const { return FA_DBG(G.L.dbg); }
-    FA_DEV void sink(cplx (&x)[R], cplx (&y)[R])
-    {
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < R; i++) s += x[i].x + y[i].y;
-        if (s == 1.2345e301) G.Z[0] = cmake(s, s);
-    }
-    // g = exp(-2 pi i d k / N) at bin k = k1 + N1*k2, k2 = v + (N2/R)*i
-    FA_DEV cplx gfac(int v, int i, const cplx *) const
-    {
-        const long long N = (long long)G.N1 * N2;
-        const long long kbin = (long long)k1 + (long long)G.N1 * (v + (N2 / R) * i);
-        const long long j = ((long long)G.L.d * kbin) % N;
-        return big_twiddle(G.btw, (unsigned)j);
-    }
-    FA_DEV void store(int e, cplx (&x)[R], int v, int, cplx *, int &)
-    {
-        const int n_out = G.L.n_in / 2;
-        cplx *dst = G.Z + (size_t)((size_t)e * n_out + P) * G.N1 * N2;
-        const cplx base = wbase * (1.0 / (double)N2);
-#pragma unroll
-        for (int i = 0; i < R; i++) dst[yz_index(G.N1, N2, k1, v + (N2 / R) * i)] = x[i] * cconj(twiddle(base, i));
-    }
-};
-
-template <int N2, int R, int NE> FA_DEV void body_mid(const BigLevel &G)
-{
-    FA_LDS_DECL
-    cplx *lds = (cplx *)FA_LDS_PTR;
-    MidIO<N2, R> io(G);
-    const cplx *tw = G.tw2;
-    // the 2048-entry table stays in L2: three reads per butterfly, other powers by multiplication
-    if (NE == 4) pair_product_core<N2, R, 1, true, true>(io, lds, tw);
-    else pair_product_core_sym<N2, R, 1, true, true>(io, lds, tw, G.L.kappa);
-}
-
 // loads of the right factor's two rows, FA_MID_BSTEP elements per barrier interval of the left factor's
 // transforms (fft_wg2 hook)
 #ifndef FA_MID_BSTEP
@@ -1574,8 +1460,8 @@ template <int N2, int R> struct MidBLoader {
 
 // Row step of the symmetric form, written for memory-level parallelism: the row pointers of the four
 // input polynomials are formed without branches, all 4*R (DIRECT: 2 x 4*R) 16-byte loads of the lane
-// are issued back to back before anything consumes them (the generic IO object above branches per
-// polynomial on the level's flags, which made every polynomial its own memory round trip), the
+// are issued back to back before anything consumes them (a generic IO object that branches per
+// polynomial on the level's flags makes every polynomial its own memory round trip), the
 // transforms run in pairs (fft_wg2: a11 with a21, b11 with b21, c11 with c21), and every barrier is
 // an LDS-only one, so the stores of c11 stay in flight under the tail of the c21 transform.
 //   DIRECT: first split level with N1 = 4 and N = 2d -- the row kernel forms the length-4 column
@@ -1804,84 +1690,12 @@ template <int N1, int R, int BC, bool DB> FA_DEV void body_col_inv(const BigLeve
     fa_wave_atomic_max_hi32(&L.max2_out[(size_t)P * kMax2Slots + max2_slot()], m2);   // P is uniform in the workgroup
 }
 
-// Bridge between two consecutive split levels: inverse column step of level l (N = N1*N2)
-// immediately followed by the forward column step of level l+1 (2N = 2N1*N2) of the same
-// polynomial, in registers.  The degree-2d coefficients never go to HBM: only their maximum
-// (for the pending scale), the new tail, and coefficient 0 (the next level's "lead") are kept.
-// The pending scale is not known here, so Y' is written unscaled and the row kernel of level
-// l+1 applies scale_in on load (BigLevel::y_unscaled).
-//   grid.x = N2/BC tiles, grid.y = ne*n_out polynomials;  lanes hold R points of the inverse and
-//   2R points (upper half zero) of the forward transform.
-template <int N1, int R, int BC, bool DB> FA_DEV void body_col_bridge(const BigLevel &G)
-{
-    FA_LDS_DECL
-    cplx *lds = (cplx *)FA_LDS_PTR;
-    const TreeLevel &L = G.L;
-    const int tid = FA_TID;
-    const int c = tid % BC, v = tid / BC;
-    const int n2 = FA_BID * BC + c;
-    const int poly = FA_BID_Y;
-    const int n_out = L.n_in / 2;
-    const int e = poly / n_out, P = poly % n_out;
-    const int N2 = G.N2;
-    const long long N = (long long)N1 * N2;
-    const int d2 = 2 * L.d;
-    const cplx *src = G.Z + (size_t)poly * N1 * N2;
-    const double sA = level_in_scale(L, 2 * P), sB = level_in_scale(L, 2 * P + 1);   // wave-uniform
-    cplx x[2 * R];
-#pragma unroll
-    for (int i = 0; i < R; i++) {
-        const int k1 = v + (N1 / R) * i;
-        x[i] = src[yz_index(N1, N2, k1, n2)];   // conj twiddle already applied by the row kernel
-    }
-    int parity = 0;
-    {
-        cplx lo[R];
-#pragma unroll
-        for (int i = 0; i < R; i++) lo[i] = x[i];
-        fft_wg<N1, R, BC, +1, DB, true>(lo, lds, v, c, G.tw1, parity);
-#pragma unroll
-        for (int i = 0; i < R; i++) x[i] = lo[i];
-    }
-    const double inv = 1.0 / (double)N1;
-    double m2 = 0.0;
-    // constant term of the product (needed by the lanes holding index 0 and index 2d)
-    auto tail_prod = [&]() -> cplx { return split_tail_product(L, P, e, sA, sB); };
-#pragma unroll
-    for (int i = 0; i < R; i++) {
-        const int n1 = v + (N1 / R) * i;
-        const long long idx = (long long)n1 * N2 + n2;
-        cplx val = x[i] * inv;
-        cplx up = cmake(0.0, 0.0);   // element n1 + N1 of the zero-padded next-level column
-        if (idx == 0) {
-            const cplx tp = tail_prod();
-            if (N == d2) {
-                val = val - tp;      // un-alias coefficient 2d folded onto 0
-                up = tp;             // index 2d = N of the degree-2d polynomial: its tail
-            }
-            L.tail_out[(size_t)e * n_out + P] = tp;
-            // coefficient 0 is the only body element later levels read (tail products)
-            L.body_out[(size_t)e * L.plane + (size_t)P * d2] = val;
-            m2 = fmax(m2, cnorm2(tp));
-        }
-        if (idx < d2) m2 = fmax(m2, cnorm2(val));
-        else if (idx == d2) val = tail_prod();   // N > 2d: the tail sits inside the lower half
-        else val = cmake(0.0, 0.0);
-        x[i] = val;
-        x[R + i] = up;
-    }
-    fa_wave_atomic_max_hi32(&L.max2_out[(size_t)P * kMax2Slots + max2_slot()], m2);   // P is uniform in the workgroup
-    // forward column step of the next level: length 2*N1, 2R points per lane
-    fft_wg<2 * N1, 2 * R, BC, -1, DB>(x, lds, v, c, G.tw1x2, parity);
-    cplx *dst = G.Y + (size_t)poly * (2 * N1) * N2;
-#pragma unroll
-    for (int i = 0; i < 2 * R; i++) {
-        const int k1 = v + (N1 / R) * i;   // (2N1)/(2R) = N1/R
-        dst[yz_index(2 * N1, N2, k1, n2)] = x[i];  // twiddle applied by the next level's row kernel
-    }
-}
-
-// Bridge with spectral doubling.  The next level's column transform of length 2*N1
+// Bridge between two consecutive split levels: inverse column step of level l (N = N1*N2) immediately followed by
+// the forward column step of level l+1 (2N = 2N1*N2) of the same polynomial, in registers.  The degree-2d
+// coefficients never go to HBM: only their maximum (for the pending scale), the new tail, and coefficient 0 (the
+// next level's "lead") are kept.  The pending scale is not known here, so Y' is written unscaled and the row kernel
+// of level l+1 applies scale_in on load (BigLevel::y_unscaled).
+// Spectral doubling: the next level's column transform of length 2*N1
 // of a column whose upper half is zero has, exactly,
 //     even rows  Y'[2j]   = this level's Z row j                     (nothing to compute or move),
 //     odd rows   Y'[2j+1] = DFT_N1( x[n1] * w_{2N1}^{n1} )[j]  (- t for column 0, t = product tail),

@@ -141,15 +141,13 @@ public:
     // the current level arrays hold
     bool want_real = false;
     bool real_run = false;
-    bool use_r3 = true;      // column lengths 3*2^j on the split levels of the real path
-    bool use_rleaf = true;   // real even-order schemes: leaf kernel with direct products (body_rleaf_strang)
     // 4SPLIT4A/B front end (set_front): Din input samples per signal, every nskip-th step kept,
     // ups preprocessed samples per kept step; D = ups * Dsub matrices enter the tree
     size_t Din = 0, nskip = 1;
     int ups = 1;
     cplx *qpre = nullptr, *rsX = nullptr, *rsX12 = nullptr, *rsQ12 = nullptr, *rsY = nullptr, *rsV = nullptr;
     size_t Lr = 0;
-    cplx *Y = nullptr, *Z = nullptr, *Z2 = nullptr;   // Z ping-pongs when spectral doubling is on
+    cplx *Y = nullptr, *Z = nullptr, *Z2 = nullptr;   // Z ping-pongs: spectral doubling reads the previous level's Z
     cplx *chY = nullptr, *chV = nullptr, *chH = nullptr;
     cplx *chVS = nullptr;                 // cached spectrum of the chirp filter
     double vs_key[4] = {0, 0, 0, 0};      // log W (re, im), M, deg+1 it was computed for
@@ -181,13 +179,6 @@ public:
     }
     size_t res_deg = 0;      // degree of the transfer matrix of the last tree run
     size_t start_n = 0, start_d = 0;  // matrices (all signals) / degree the tree run starts from
-    bool use_leaf = true;    // fuse coefficients + first levels (nft_kernels.h body_leaf)
-    bool use_bridge = true;  // fuse inverse/forward column steps of consecutive split levels
-    bool use_doubling = true; // ... with spectral doubling when N = 2d (body_col_bridge2)
-    bool use_sym = true;     // NSE symmetry: store/transform only the first column (ne = 2)
-    bool use_multi = true;   // several consecutive fused levels per launch (body_multi_fft)
-    bool use_direct4 = true; // first split level: row kernel forms the length-4 column transform itself
-    bool use_leaf_multi = true;   // ... with the leaf kernel in front of the first of them (body_leaf_multi)
     bool leaf_pending = false;    // run_coeffs left the leaf to the first launch of run_tree
     LeafParams leaf_lp;
     int ne = 4;              // stored entries per matrix in the current tree run
@@ -255,7 +246,7 @@ public:
     // largest pair product done by one workgroup.  General (4-entry) form: 2048 -- a 4096-point pair needs 8 + 4
     // transforms of 16 points per lane in one workgroup (616 B of scratch per lane, 75 us for ONE pair); as a split
     // transform of 4 columns x 1024-point rows it is three small launches (~30 us for one pair, rows over 4 CUs)
-    size_t fused_max_len() const { return (ne == 4 && FA_MID_GEN) ? (size_t)2048 : (size_t)kFusedMaxN; }
+    size_t fused_max_len() const { return (ne == 4) ? (size_t)2048 : (size_t)kFusedMaxN; }
 
     int init()
     {
@@ -476,11 +467,12 @@ public:
         p.real_out = real_run ? 1 : 0;
         cur = 0;
         kappa_run = kappa;
-        const int spt = use_leaf ? leaf_spt(deg0) : 0;
+        // leaf kernel: coefficients and the first levels fused (nft_kernels.h body_leaf)
+        const int spt = leaf_spt(deg0);
         const bool leaf = spt > 1 && Dpad >= (size_t)spt;
-        // the symmetric form needs r = -kappa*conj(q) (no explicit r) and starts above the
-        // direct-product levels, which the leaf kernel guarantees
-        ne = (use_sym && leaf && d_r == nullptr && (size_t)deg0 * spt > (size_t)kSchoolMaxDeg) ? 2 : 4;
+        // NSE symmetry, only the first column stored and transformed (ne = 2): the symmetric form needs
+        // r = -kappa*conj(q) (no explicit r) and starts above the direct-product levels, which the leaf kernel guarantees
+        ne = (leaf && d_r == nullptr && (size_t)deg0 * spt > (size_t)kSchoolMaxDeg) ? 2 : 4;
         p.ne = ne;
         leaf_pending = false;
         if (leaf) {
@@ -489,8 +481,8 @@ public:
             lp.spt = spt;
             start_n = n0 / (size_t)spt;
             start_d = (size_t)deg0 * (size_t)spt;
-            // symmetric form with d = 8: the leaf is computed inside the first multi-level launch
-            if (use_leaf_multi && use_multi && ne == 2 && start_d == 8 && dbg_flags == 0 && start_n / batch >= 4) {
+            // symmetric form with d = 8: the leaf is computed inside the first multi-level launch (body_leaf_multi)
+            if (ne == 2 && start_d == 8 && dbg_flags == 0 && start_n / batch >= 4) {
                 leaf_lp = lp;
                 leaf_pending = true;
                 return NFT_SUCCESS;
@@ -498,7 +490,7 @@ public:
             if (!dispatch_leaf(be, lp)) return NFT_EC_NOT_YET_IMPLEMENTED;
             return NFT_SUCCESS;
         }
-        const int rl_spt = (real_run && use_rleaf) ? rleaf_strang_samples(akns_disc) : 0;
+        const int rl_spt = real_run ? rleaf_strang_samples(akns_disc) : 0;
         if (rl_spt > 1 && Dpad >= (size_t)rl_spt) {
             // even-order splitting schemes on the real path: coefficients from their elementary factors AND the ordered
             // product of rl_spt consecutive samples by direct multiplication (body_rleaf_strang, nft_real.h)
@@ -518,7 +510,7 @@ public:
         } else if (prog_ptr != nullptr) {
             // schemes of order 5..8: generated coefficient program; the symmetric form can start at
             // level 0 because every level is an FFT level (deg0 > kSchoolMaxDeg)
-            ne = (use_sym && d_r == nullptr) ? 2 : 4;
+            ne = (d_r == nullptr) ? 2 : 4;
             CoeffProgParams pp;
             pp.c = p;
             pp.c.ne = ne;
@@ -592,7 +584,7 @@ public:
         // degrees 3*2^a: the split levels take columns of 3*K rows of kRowGen points -- transform length M = d exactly
         // (nft_real.h) -- when the last level's column length is instantiated
         bool r3 = false;
-        if (use_r3 && tw3tab) {
+        if (tw3tab) {
             size_t odd = start_d;
             while (odd % 2 == 0) odd /= 2;
             const size_t dtop = start_d * (start_n / batch) / 2;   // degree of the last level's factors
@@ -641,7 +633,7 @@ public:
                 ok = true;
                 if (!y_from_bridge) ok = dispatch_r3col_fwd(be, G);
                 if (ok) run_mid(be, G);
-                const bool next_split = use_bridge && (n / 2 / batch > 1) && K <= (size_t)kR3BridgeMaxK;
+                const bool next_split = (n / 2 / batch > 1) && K <= (size_t)kR3BridgeMaxK;
                 if (ok) ok = next_split ? dispatch_r3bridge(be, G) : dispatch_r3col_inv(be, G);
                 zcur ^= 1;
                 y_from_bridge = ok && next_split;
@@ -673,7 +665,7 @@ public:
                 ok = true;
                 if (!y_from_bridge) ok = dispatch_rcol_fwd(be, G);
                 if (ok) run_mid(be, G);
-                const bool next_split = use_bridge && (n / 2 / batch > 1) && G.N1 <= kRBridgeMaxN1
+                const bool next_split = (n / 2 / batch > 1) && G.N1 <= kRBridgeMaxN1
                                         && row_len_gen(2 * M) == G.N2;
                 if (ok) ok = next_split ? dispatch_rbridge(be, G) : dispatch_rcol_inv(be, G);
                 zcur ^= 1;
@@ -700,7 +692,6 @@ public:
         size_t n = start_n;     // matrices at the current level, all signals
         size_t d = start_d;
         bool y_from_bridge = false;
-        bool y_split = false;      // Y holds odd rows only, even rows are the previous Z
         int zcur = 0;
         bool in_pending = false;   // previous level was split: its rescale is still pending
         int mcur = 0;
@@ -726,7 +717,7 @@ public:
             bool ok;
             // consecutive fused levels of the symmetric form in one launch: as many as fit (<= 3)
             int stages = 1;
-            if (use_multi && ne == 2 && d > (size_t)kSchoolMaxDeg && N == 2 * d && N >= 16 && dbg_flags == 0) {
+            if (ne == 2 && d > (size_t)kSchoolMaxDeg && N == 2 * d && N >= 16 && dbg_flags == 0) {
                 while (stages < 3 && (N << stages) <= (size_t)kFusedMaxN && ((n / batch) >> (stages + 1)) >= 1) stages++;
             }
             if (leaf_pending && stages < 2) {   // cannot happen (start_n/batch >= 4), but never skip the leaf
@@ -741,10 +732,6 @@ public:
                     Q.L = L;
                     ok = dispatch_leaf_multi(be, Q, stages);
                     leaf_pending = false;
-                    if (!ok) {   // configuration without a fused instantiation: leaf, then the levels
-                        if (!dispatch_leaf(be, leaf_lp)) return NFT_EC_NOT_YET_IMPLEMENTED;
-                        ok = dispatch_multi(be, L, (int)N, stages);
-                    }
                 } else {
                     ok = dispatch_multi(be, L, (int)N, stages);
                 }
@@ -764,8 +751,8 @@ public:
                 G.Y = Y;
                 G.Z = zcur ? Z2 : Z;
                 G.Zprev = zcur ? Z : Z2;
-                G.y_split = y_split ? 1 : 0;
-                G.N2 = (ne == 4 && FA_MID_GEN) ? row_len_gen(N) : kRowTree;
+                G.y_split = y_from_bridge ? 1 : 0;   // every bridge doubles: Y holds the odd rows only
+                G.N2 = (ne == 4) ? row_len_gen(N) : kRowTree;
                 G.N1 = (int)(N / (size_t)G.N2);
                 G.btw = big_tw(N);
                 G.tw1 = (G.N1 >= 2) ? tw_table((size_t)G.N1) : nullptr;
@@ -773,27 +760,20 @@ public:
                 G.tw1x2 = tw_table((size_t)2 * G.N1);
                 G.btw2 = big_tw(2 * N);
                 G.y_unscaled = y_from_bridge ? 1 : 0;
-                // first split level: a length-4 column transform of two non-zero rows is done by the row
-                // kernel on the fly (saves the column launch and its 32 + 64 MB)
-                G.y_direct = (use_direct4 && !y_from_bridge && G.N1 == 4 && N == 2 * d && dbg_flags == 0 && (ne == 2 || !FA_MID_GEN)) ? 1 : 0;
+                // first split level of the symmetric form: a length-4 column transform of two non-zero rows is done
+                // by the row kernel on the fly (saves the column launch and its 32 + 64 MB)
+                G.y_direct = (!y_from_bridge && G.N1 == 4 && N == 2 * d && dbg_flags == 0 && ne == 2) ? 1 : 0;
                 G.stagger = (n / 2 * (size_t)G.N1 == 512) ? tune_stagger : 0;   // exactly one round of workgroups
                 G.stamps = (dbg_stamps && split_idx == stamp_level) ? dbg_stamps : nullptr;
                 split_idx++;
                 ok = true;
                 if (!y_from_bridge && !G.y_direct) ok = dispatch_col_fwd(be, G);
                 if (ok) run_mid(be, G);
-                // bridge straight into the next level's column step when that level is split too
-                const bool can_double = use_doubling;   // N = 2d and N > 2d alike (body_col_bridge2)
-                const bool next_split = use_bridge && (n / 2 / batch > 1) && G.N1 <= (can_double ? 4096 : 512)
-                                        && nft_product_len(2 * d) == 2 * N
-                                        && ((ne == 4 && FA_MID_GEN) ? row_len_gen(2 * N) : kRowTree) == G.N2;
-                const bool doubling = next_split && can_double;
-                if (ok) {
-                    if (doubling) ok = dispatch_col_bridge2(be, G);
-                    else if (next_split) ok = dispatch_col_bridge(be, G);
-                    else ok = dispatch_col_inv(be, G);
-                }
-                y_split = ok && doubling;
+                // bridge straight into the next level's column step when that level is split too, with spectral
+                // doubling (body_col_bridge2; N = 2d and N > 2d alike)
+                const bool next_split = (n / 2 / batch > 1) && G.N1 <= 4096 && nft_product_len(2 * d) == 2 * N
+                                        && ((ne == 4) ? row_len_gen(2 * N) : kRowTree) == G.N2;
+                if (ok) ok = next_split ? dispatch_col_bridge2(be, G) : dispatch_col_inv(be, G);
                 zcur ^= 1;
                 y_from_bridge = ok && next_split;
                 // the consumer of the next level finalizes this one; the last level needs a kernel

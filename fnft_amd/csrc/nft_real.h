@@ -347,7 +347,7 @@ template <int M, int R, int BP, bool TWLDS> FA_DEV void body_rpair4(const TreeLe
 // ---------------------------------------------------------------------------------------------
 // split transforms, M = N1*N2 (element n = n1*N2 + n2, bin k = k1 + N1*k2).  The twist factors as
 // zeta^n = exp(2 pi i n1/(4 N1)) * exp(2 pi i n2/(4M)): the column kernels apply the first factor, the row kernel
-// (body_mid with BigLevel::rtwist) the second together with its own twiddle.  Y / Z scratch as in nft_kernels.h.
+// (body_mid_gen with BigLevel::rtwist) the second together with its own twiddle.  Y / Z scratch as in nft_kernels.h.
 // ---------------------------------------------------------------------------------------------
 // first split level: real coefficients -> column transform of the folded, twisted sequence
 //   grid.x = N2/BC tiles, grid.y = 4*n_in polynomials

@@ -1,6 +1,6 @@
 """ISA summary of one kernel of the built library: the order of global loads / stores, s_waitcnt vmcnt and
 s_barrier, run-length compressed -- shows whether loads are issued back to back or one round trip at a time.
-usage: python tests/gpu_debug/isa_summary.py 'KMid<2>' [--full]"""
+usage: python tests/gpu_debug/isa_summary.py 'KMidSym<true>' [--full]"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 LIB = os.path.join(ROOT, "fnft_amd", "lib", "libfnft_amd.so")

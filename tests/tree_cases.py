@@ -122,53 +122,35 @@ CASES = [
 
 
 # Every instantiation of a product-tree kernel in the dispatch switches of nft_dispatch.h (dispatch_leaf, _pair_school,
-# _pair_fft, _multi, _leaf_multi, run_mid, _col_fwd, _col_inv, _col_bridge, _col_bridge2, _rpair_school, _rpair,
+# _pair_fft, _multi, _leaf_multi, run_mid, _col_fwd, _col_inv, _col_bridge2, _rpair_school, _rpair,
 # _rcol_fwd, _rcol_inv, _rbridge, _r3col_fwd, _r3col_inv, _r3bridge, _rleaf_strang).
 def _l(fmt, xs):
     return [fmt % x for x in xs]
 
 
-N1 = [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
-N1BR = [2, 4, 8, 16, 32, 64, 128, 256, 512]
+N1 = [4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
+N1BR = [4, 8, 16, 32, 64, 128, 256, 512]
 K3 = [1, 2, 4, 8, 16, 32, 64, 128, 256]
 TREE_INSTANTIATIONS = (
     _l("KLeaf<%d>", [1, 2, 3, 4]) + _l("KPairSchool<%d>", [1, 2, 3])
-    + _l("KPairFft<%d,4>", P2 + [4096]) + _l("KPairFft<%d,2>", P2 + [4096])
-    + _l("KMulti<%d,3>", [16, 32, 64, 128, 256, 512, 1024]) + _l("KMulti<%d,2>", [16, 32, 64, 128, 256, 512, 1024, 2048])
+    + _l("KPairFft<%d,4>", P2) + _l("KPairFft<%d,2>", P2[1:] + [4096])
+    + _l("KMulti<%d,3>", [128, 1024]) + _l("KMulti<%d,2>", [128, 1024])
     + ["KLeafMulti<%d,%d>" % (d, s) for s in (3, 2) for d in (1, 2, 4)]
-    + ["KMid<4>", "KMid<2>", "KMidSym<true>", "KMidSym<false>", "KMidGen<1024>", "KMidGen<2048>"]
-    + _l("KColFwd<%d>", N1) + _l("KColInv<%d>", N1) + _l("KColBridge<%d>", N1BR) + _l("KColBridge2<%d>", N1BR + [1024, 2048, 4096])
-    + _l("KRPairSchool<%d>", [1, 2, 3]) + _l("KRPair<%d>", [4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048])
+    + ["KMidSym<true>", "KMidSym<false>", "KMidGen<1024>", "KMidGen<2048>"]
+    + _l("KColFwd<%d>", N1) + _l("KColInv<%d>", N1) + _l("KColBridge2<%d>", N1BR + [1024, 2048, 4096])
+    + _l("KRPairSchool<%d>", [1, 2]) + _l("KRPair<%d>", [8, 16, 1024, 2048])
     + _l("KRPair4<%d>", [32, 64, 128, 256, 512])
-    + _l("KRColFwd<%d>", N1[:-1]) + _l("KRColInv<%d>", N1[:-1]) + _l("KRBridge<%d>", N1BR + [1024])
-    + _l("KR3ColFwd<%d>", K3 + [512]) + _l("KR3ColInv<%d>", K3 + [512]) + _l("KR3Bridge<%d>", K3)
+    + _l("KRColFwd<%d>", [4, 4096]) + _l("KRColInv<%d>", N1[:-1]) + _l("KRBridge<%d>", N1BR + [1024])
+    + _l("KR3ColFwd<%d>", [1]) + _l("KR3ColInv<%d>", K3 + [512]) + _l("KR3Bridge<%d>", K3)
     + ["KRLeafStrang<%d,%s>" % (o, b) for o in (6, 8) for b in ("false", "true")])
 
-_NEVER = "not reachable with the product's settings: "
 EXCLUDED = {}
-EXCLUDED.update({k: _NEVER + "the general form fuses pair products up to N = 2048 (fused_max_len)" for k in ["KPairFft<4096,4>"]})
-EXCLUDED.update({k: _NEVER + "FA_MID_GEN / FA_MID_SYM select KMidGen / KMidSym" for k in ["KMid<4>", "KMid<2>"]})
-EXCLUDED.update({k: _NEVER + "the symmetric form starts at degree >= 6 (leaf kernel), so N >= 16" for k in ["KPairFft<8,2>"]})
-EXCLUDED.update({k: _NEVER + "with the leaf fused into the first launch, multi-level launches start at N = 16 (KLeafMulti), "
-                 "128 and 1024; other N0 only with use_leaf_multi off"
-                 for k in _l("KMulti<%d,3>", [16, 32, 64, 256, 512]) + _l("KMulti<%d,2>", [16, 32, 64, 256, 512, 2048])})
-EXCLUDED.update({k: _NEVER + "N1 = 2 would be a product of length 2*N2 <= 4096, which is fused"
-                 for k in ["KColFwd<2>", "KColInv<2>", "KColBridge2<2>", "KRColFwd<2>", "KRColInv<2>", "KRBridge<2>"]})
-EXCLUDED.update({k: _NEVER + "spectral doubling (use_doubling) is always on, so KColBridge2 replaces it" for k in _l("KColBridge<%d>", N1BR)})
-EXCLUDED.update({k: _NEVER + "a forward column step of the real tree runs on the first split level, whose length is "
-                 "the first above the fused limit (N1 = 4, or K = 1 on the radix-3 columns), and after a level without a "
-                 "bridge, which only the bridge limit N1 = 1024 causes (KRColInv<2048>, then KRColFwd<4096>)" for k in _l("KRColFwd<%d>", [8, 16, 32, 64, 128, 256, 512, 1024, 2048])
-                 + _l("KR3ColFwd<%d>", [2, 4, 8, 16, 32, 64, 128, 256, 512])})
 _BIG = "reachable, but only by a tree of transform length 2^24 (1 GB of coefficients per side plus the reference " \
        "work of 2^24 terms); the same template body runs at every shorter column length in the cases"
 EXCLUDED.update({"KColFwd<8192>": _BIG + " (two factors of degree 2^23; KColInv<8192> runs in plan_4A_D4194304_max)"})
 EXCLUDED.update({k: "reachable, but only from 2^22 + 1 real samples (4M factors): the reference work alone would take "
                  "most of the time allowed for these tests; KRColFwd<4> / KRColInv<2048> run the same bodies"
                  for k in ["KRColFwd<4096>", "KRColInv<4096>"]})
-EXCLUDED.update({k: _NEVER + "the real tree's school products stop at degree 2 (KRPairSchool<3> needs d = 3 in a "
-                 "real run, which the leaf kernels skip)" for k in ["KRPairSchool<3>"]})
-EXCLUDED.update({k: _NEVER + "KRPair4 takes M = 32..512 and the first real FFT level has M >= 8"
-                 for k in _l("KRPair<%d>", [4, 32, 64, 128, 256, 512])})
 
 
 def case_ids():
