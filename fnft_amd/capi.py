@@ -103,6 +103,8 @@ EXPORTED = [
     "fnft_kdvv", "fnft_kdvv_default_opts", "fnft__kdv_fscatter_numel", "fnft__kdv_fscatter",
     "fnft_amd_kdvv_plan_create", "fnft_amd_kdvv_contspec_device", "fnft_amd_kdvv_plan_set_real_mode",
     "fnft_amd_release_cached", "fnft_nsep", "fnft_nsep_default_opts", "fnft_amd_poly_fmult2x2_device",
+    "fnft_amd_inverse_plan_create", "fnft_amd_inverse_plan_destroy", "fnft_amd_inverse_plan_workspace_bytes",
+    "fnft_amd_nsev_inverse_device", "fnft_amd_inverse_plan_finish",
 ]
 
 _lib = None
@@ -234,6 +236,16 @@ def load(path=None):
     L.fnft_amd_plan_device.restype = C.c_int
     L.fnft_amd_plan_device.argtypes = [vp]
     L.fnft_amd_current_device.restype = C.c_int
+    L.fnft_amd_inverse_plan_create.restype = i32
+    L.fnft_amd_inverse_plan_create.argtypes = [C.POINTER(vp), sz, sz, sz, C.POINTER(NsevInverseOpts), C.c_int]
+    L.fnft_amd_inverse_plan_destroy.restype = None
+    L.fnft_amd_inverse_plan_destroy.argtypes = [vp]
+    L.fnft_amd_inverse_plan_workspace_bytes.restype = sz
+    L.fnft_amd_inverse_plan_workspace_bytes.argtypes = [vp]
+    L.fnft_amd_nsev_inverse_device.restype = i32
+    L.fnft_amd_nsev_inverse_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    L.fnft_amd_inverse_plan_finish.restype = i32
+    L.fnft_amd_inverse_plan_finish.argtypes = [vp, vp, vp, vp]
     if path is None:
         _lib = L
     return L
@@ -419,12 +431,10 @@ def nsev_inverse_XI(D, T, M, discretization="2SPLIT2A"):
     return int(rc), [float(XI[0]), float(XI[1])]
 
 
-def fnft_nsev_inverse(M, contspec, XI, bound_states, normconsts_or_residues, D, T, kappa, opts=None, q_seed=None):
-    """fnft_nsev_inverse() through the C ABI with host (numpy) buffers: (rc, q[D]).  opts: dict with the names of the
-    reference's option fields (strings for the enums).  contspec, if a complex128 array, is modified in place as the
-    reference modifies its argument; q_seed: the seed potential of USE_SEED_POTENTIAL_INSTEAD."""
-    L = load()
-    o = L.fnft_nsev_inverse_default_opts()
+def inverse_opts(opts=None):
+    """fnft_nsev_inverse_opts_t: the defaults, with the fields of the dict `opts` (reference names; strings for the
+    enums) replaced."""
+    o = load().fnft_nsev_inverse_default_opts()
     for k, v in (opts or {}).items():
         if k == "discretization":
             v = NSE_DISC[v] if isinstance(v, str) else int(v)
@@ -435,6 +445,15 @@ def fnft_nsev_inverse(M, contspec, XI, bound_states, normconsts_or_residues, D, 
         elif k == "discspec_type":
             v = INV_DSTYPE[v] if isinstance(v, str) else int(v)
         setattr(o, k, v)
+    return o
+
+
+def fnft_nsev_inverse(M, contspec, XI, bound_states, normconsts_or_residues, D, T, kappa, opts=None, q_seed=None):
+    """fnft_nsev_inverse() through the C ABI with host (numpy) buffers: (rc, q[D]).  opts: dict with the names of the
+    reference's option fields (strings for the enums).  contspec, if a complex128 array, is modified in place as the
+    reference modifies its argument; q_seed: the seed potential of USE_SEED_POTENTIAL_INSTEAD."""
+    L = load()
+    o = inverse_opts(opts)
     cs = None if contspec is None else (contspec if (isinstance(contspec, np.ndarray) and contspec.dtype == np.complex128
                                                      and contspec.flags.c_contiguous) else _c128(contspec))
     Tn = None if T is None else np.ascontiguousarray(T, np.float64)
@@ -750,6 +769,52 @@ class Plan:
         rc = self.L.fnft_amd_plan_get_transfer_matrix(self.h, b, _ptr(buf), C.byref(deg), C.byref(W))
         d = deg.value
         return int(rc), d, buf[: 4 * (d + 1)].reshape(4, d + 1).copy(), int(W.value)
+
+
+class InversePlan:
+    """fnft_amd_inverse_plan_t: `batch` inverse transforms (continuous part) of M spectral values to D samples each,
+    one set of options (dict as for fnft_nsev_inverse), device-resident.  Raises RuntimeError (attribute rc) if the
+    plan cannot be created."""
+
+    def __init__(self, D, M, batch=1, opts=None, device=0):
+        self.L = load()
+        self.D, self.M, self.batch = int(D), int(M), int(batch)
+        self.opts = inverse_opts(opts)
+        self.h = C.c_void_p()
+        rc = self.L.fnft_amd_inverse_plan_create(C.byref(self.h), self.D, self.M, self.batch, C.byref(self.opts),
+                                                 int(device))
+        if rc != FNFT_SUCCESS:
+            err = RuntimeError("fnft_amd_inverse_plan_create rc=%d (%s)" % (rc, last_error()))
+            err.rc = int(rc)
+            raise err
+
+    def close(self):
+        if self.h:
+            self.L.fnft_amd_inverse_plan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self):
+        return int(self.L.fnft_amd_inverse_plan_workspace_bytes(self.h))
+
+    def run_device(self, cs_ptr, q_ptr, XI, T, kappa, stream=0):
+        """Enqueue one call: cs_ptr (batch*M complex128) -> q_ptr (batch*D complex128), raw device addresses (e.g.
+        tensor.data_ptr()).  XI may be None (B_OF_TAU)."""
+        return int(self.L.fnft_amd_nsev_inverse_device(self.h, C.c_void_p(cs_ptr), None if XI is None else _d2(XI),
+                                                       C.c_void_p(q_ptr), None if T is None else _d2(T), int(kappa),
+                                                       C.c_void_p(stream)))
+
+    def finish(self, stream=0):
+        """Waits for `stream`: (rc, status[batch], warnings[batch])."""
+        st = np.zeros(self.batch, np.int32)
+        wn = np.zeros(self.batch, np.int32)
+        rc = self.L.fnft_amd_inverse_plan_finish(self.h, C.c_void_p(stream), _ptr(st), _ptr(wn))
+        return int(rc), st, wn
 
 
 def poly_fmult2x2_device(deg, n, p_ptr, out_ptr, stream=0):

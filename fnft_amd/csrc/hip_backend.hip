@@ -818,6 +818,150 @@ extern "C" FNFT_INT fnft_amd__inverse_add_discrete(FNFT_UINT K, const FNFT_COMPL
     return rc;
 }
 
+// ---- batched, device-resident fnft_nsev_inverse (continuous part) ----------------------------------------------------
+// Argument checks follow fnft_nsev_inverse (fnft_nsev_inverse_host.c) in its order and with its codes; those that only
+// depend on sizes and options run at create time, before any HIP call.
+struct fnft_amd_inverse_plan {
+    HipBackend be;
+    NftInverseBatch<HipBackend> *inv = nullptr;
+    int device = 0;
+    int cstype = 0;
+    hipStream_t last_stream = nullptr;
+    std::vector<int> st;
+    std::mutex mtx;
+};
+
+static FNFT_INT inv_subroutine(const char *func, int line, FNFT_INT ec)
+{
+    return fnft_amd__raise(-std::abs((int)ec), func, line, "Subroutine failure.");
+}
+
+FNFT_INT fnft_amd_inverse_plan_create(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
+                                      fnft_nsev_inverse_opts_t const *opts, int device)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(M % 2 != 0, M);                                        // fnft_nsev_inverse_host.c, in its order
+    SEAM_CHECK(M < D, M);
+    SEAM_CHECK(D < 2 || (D & (D - 1)) != 0, D);
+    SEAM_CHECK(batch == 0, batch);
+    const fnft_nsev_inverse_opts_t o = opts ? *opts : fnft_nsev_inverse_default_opts();
+    SEAM_CHECK(o.discretization != fnft_nse_discretization_2SPLIT2A
+               && o.discretization != fnft_nse_discretization_2SPLIT2_MODAL, opts->discretization);
+    if (o.contspec_inversion_method == fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_AB_FROM_ITER
+        || o.contspec_inversion_method == fnft_nsev_inverse_csmethod_USE_SEED_POTENTIAL_INSTEAD)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched inverse: iterative or seed-potential method).");
+    int cstype = 0;
+    switch (o.contspec_type) {
+    case fnft_nsev_inverse_cstype_REFLECTION_COEFFICIENT:
+        if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT
+            && o.contspec_inversion_method != fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_REFL_COEFF)
+            return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
+        break;
+    case fnft_nsev_inverse_cstype_B_OF_XI:
+        cstype = 1;
+        break;
+    case fnft_nsev_inverse_cstype_B_OF_TAU:
+        cstype = 2;
+        if (M != D) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "M"));
+        if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT)
+            return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
+        break;
+    default:
+        return seam_invalid(__func__, __LINE__, "opts->contspec_type");
+    }
+    if (cstype != 0 && o.oversampling_factor == 0)                    // fnft__poly_specfact.c:37-38
+        return inv_subroutine(__func__, __LINE__, FNFT_EC_INVALID_ARGUMENT);
+    DeviceGuard dg(device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    fnft_amd_inverse_plan *P = new (std::nothrow) fnft_amd_inverse_plan();
+    if (!P) return FNFT_EC_NOMEM;
+    P->device = device;
+    P->cstype = cstype;
+    P->inv = new (std::nothrow) NftInverseBatch<HipBackend>(
+        P->be, (size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
+        o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0);
+    if (!P->inv) { delete P; return FNFT_EC_NOMEM; }
+    const int rc = P->inv->init();
+    if (rc != NFT_SUCCESS || P->be.failed) {
+        (void)P->be.sync();
+        delete P->inv;
+        delete P;
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = P;
+    return FNFT_SUCCESS;
+}
+
+void fnft_amd_inverse_plan_destroy(fnft_amd_inverse_plan_t *plan)
+{
+    if (!plan) return;
+    {
+        DeviceGuard dg(plan->device);
+        // the pool hands these blocks to the next allocation: nothing the plan enqueued may still be writing them
+        if (plan->last_stream) (void)hipStreamSynchronize(plan->last_stream);
+        (void)hipDeviceSynchronize();
+        delete plan->inv;
+        plan->be.destroy_events();
+    }
+    delete plan;
+}
+
+FNFT_UINT fnft_amd_inverse_plan_workspace_bytes(const fnft_amd_inverse_plan_t *plan)
+{
+    return plan ? plan->inv->bytes : 0;
+}
+
+FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void *d_contspec, const FNFT_REAL *XI,
+                                      void *d_q, const FNFT_REAL *T, FNFT_INT kappa, void *stream)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(!d_contspec, contspec);
+    SEAM_CHECK(!d_q, q);
+    SEAM_CHECK(T == NULL || !(T[0] < T[1]), T);
+    SEAM_CHECK(kappa != +1 && kappa != -1, kappa);
+    SEAM_CHECK(XI == NULL && plan->cstype != 2, XI);
+    if (plan->cstype == 2 && T[0] != -T[1])                           // :643-647
+        return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "T"));
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    DeviceGuard dg(plan->device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    NftInverseBatch<HipBackend> &inv = *plan->inv;
+    plan->be.stream = (hipStream_t)stream;
+    plan->last_stream = (hipStream_t)stream;
+    plan->be.failed = false;
+    // step size and phase factors exactly as the host driver forms them (fnft_nsev_inverse_host.c)
+    const size_t D = inv.D;
+    const FNFT_REAL eps_t = (T[1] - T[0]) / (D - 1);
+    const FNFT_REAL pf_rho = -2.0 * (T[1] + eps_t * 0.5) + eps_t;
+    const FNFT_REAL pf_b = -eps_t * D - (T[1] + eps_t * 0.5) - (T[0] - eps_t * 0.5) + eps_t;
+    const int rc = inv.run((const cplx *)d_contspec, XI, (cplx *)d_q, eps_t, (int)kappa,
+                           plan->cstype == 0 ? pf_rho : pf_b);
+    if (plan->be.failed) return FNFT_EC_OTHER;
+    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+}
+
+FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *stream, FNFT_INT *status, int *warnings)
+{
+    SEAM_CHECK(!plan, plan);
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    DeviceGuard dg(plan->device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    plan->be.stream = (hipStream_t)stream;
+    const int rc = plan->inv->read_status(plan->st);
+    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
+    FNFT_INT first = FNFT_SUCCESS;
+    for (size_t b = 0; b < plan->st.size(); b++) {
+        const int h = plan->st[b];
+        // the drop-in: fnft__nse_finvscatter fails with FNFT_EC_OTHER (bits 4, 5), returned as a subroutine failure
+        const FNFT_INT s = (h & 48) ? -FNFT_EC_OTHER : FNFT_SUCCESS;
+        if (status) status[b] = s;
+        if (warnings) warnings[b] = (h & 8) ? 1 : 0;
+        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
+    }
+    return first;
+}
+
 FNFT_INT fnft_amd_poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const double *A,
                               const double *W, const FNFT_UINT M, FNFT_COMPLEX *const result)
 {

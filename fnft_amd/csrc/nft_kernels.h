@@ -1822,8 +1822,9 @@ struct ExportParams {
     int batch;
     int ne;             // 4 general, 2 symmetric
     int kappa;
-    long long out_stride = 0;   // != 0 (batch 1): entry e goes to out[e*out_stride + k] instead of out[e*(deg+1) + k]
-    const int *W = nullptr;     // != NULL: values are multiplied by 2^W[0] (un-normalised result)
+    long long out_stride = 0;   // != 0: entry e of signal b goes to out[b*out_bstride + e*out_stride + k] instead of
+    long long out_bstride = 0;  //       out[(4 b + e)*(deg+1) + k]
+    const int *W = nullptr;     // != NULL: values of signal b are multiplied by 2^W[b] (un-normalised result)
     int real_layout = 0;        // body/tail are arrays of double (real-coefficient path, nft_real.h)
 };
 // coefficient k (highest power first, k <= deg) of stored plane s of signal b.  General form:
@@ -1867,8 +1868,8 @@ FA_DEV void body_export_tm(const ExportParams &E)
         val = cconj(stored_coef(E.body, E.tail, E.plane, E.deg_tot, E.deg, E.batch, 2, 1, b, E.deg - k))
               * (double)(-E.kappa);
     }
-    const double sw = E.W ? sc * pow2i(E.W[0]) : sc;
-    if (E.out_stride != 0) E.out[(long long)e * E.out_stride + k] = val * sw;
+    const double sw = E.W ? sc * pow2i(E.W[b]) : sc;
+    if (E.out_stride != 0) E.out[(long long)b * E.out_bstride + (long long)e * E.out_stride + k] = val * sw;
     else E.out[gid] = val * sw;
 }
 
@@ -2791,6 +2792,11 @@ enum InvOpCode {
     INV_ITER_PHASE,    // :462-469  phase = arg(a[i]); out[i] = reordered(b)[i] * exp(i phase); block sums of |phase|
     INV_BTAU,          // :654-657  b = 2 eps contspec / degree1step, end points halved
     INV_DOUBLE_Q,      // q'[2m] = q[m], q'[2m+1] = q[m+1]: the half steps of compute_eigenfunctions as a signal
+    // transfer matrix (n = 4 (deg+1) elements, [11|12|21|22]) of the continuous part, formed on the device (the batched
+    // call; the host-pointer driver forms the same values on the host, nft_nsev_inverse.h: transfer_matrix)
+    INV_TM_B,          // :340-364 / :594-614  from a = FFT of the M = i1 values: 12, 21 for k >= i0 (scaled by s0 = 1/M);
+                       //                      11, 22 = 1 if s1 != 0 (A = 1), else 0 (the spectral factorization follows)
+    INV_TM_AB,         // :660-676  from a = A, b = B (deg = D values each)
 };
 struct InvOpParams {
     int op;
@@ -2804,6 +2810,11 @@ struct InvOpParams {
     const cplx *bs;          // K bound states (INV_PREP)
     int *status;             // bit 3: ill-posed spectral factorization (a warning)
     double *accum;           // INV_ITER_PHASE: one partial sum per workgroup
+    long long i1;            // INV_TM_B: M
+    // batch (grid.y = signal): per-signal strides of a, b, out, out2 (elements) and of the status word (ints); all 0
+    // for one signal.  INV_ITER_PHASE is never batched (its block sums are indexed by FA_BID alone).
+    long long sa, sb, sout, sout2;
+    int sst;
 };
 FA_DEV void body_inv_op(const InvOpParams &P)
 {
@@ -2811,12 +2822,16 @@ FA_DEV void body_inv_op(const InvOpParams &P)
     double *red = (double *)FA_LDS_PTR;
     const long long i = (long long)FA_BID * FA_BDIM + FA_TID;
     const bool act = i < P.n;
+    const long long sg = FA_BID_Y;   // signal of the batch
+    const cplx *Pa = P.a + sg * P.sa, *Pb = P.b + sg * P.sb;
+    cplx *Pout = P.out + sg * P.sout, *Pout2 = P.out2 + sg * P.sout2;
+    int *Pst = P.status + sg * P.sst;
     double mine = 0.0;
     if (act) {
         switch (P.op) {
         case INV_PREP: {
             const double xi = P.s0 + (double)i * P.s1;
-            cplx c = P.a[i];
+            cplx c = Pa[i];
             for (int k = 0; k < P.K; k++) {
                 const cplx bk = P.bs[k];
                 c = c * c_div(cmake(xi - bk.x, -bk.y), cmake(xi - bk.x, bk.y));
@@ -2824,69 +2839,92 @@ FA_DEV void body_inv_op(const InvOpParams &P)
             double sn, cs;
             fa_sincos(-xi * P.s2, &sn, &cs);
             c = c * cmake(cs, sn);
-            P.out[i] = c;
+            Pout[i] = c;
             const long long h = P.n / 2;
-            P.out2[(i >= h - 1) ? i - (h - 1) : i + (h + 1)] = c;
+            Pout2[(i >= h - 1) ? i - (h - 1) : i + (h + 1)] = c;
         } break;
-        case INV_PAD: P.out[i] = (i <= P.i0) ? P.a[i] : cmake(0.0, 0.0); break;
+        case INV_PAD: Pout[i] = (i <= P.i0) ? Pa[i] : cmake(0.0, 0.0); break;
         case INV_SPEC_X: {
             const double tol = 1.4901161193847656e-08;   // sqrt(eps)
-            const double a2 = cnorm2(P.a[i]);
+            const double a2 = cnorm2(Pa[i]);
             cplx x;
             if (P.kappa == 0) {
                 const double ab = sqrt(a2);
-                if (ab < tol) fa_atomic_or_i32(P.status, 8);
+                if (ab < tol) fa_atomic_or_i32(Pst, 8);
                 x = cmake(log(ab), 0.0);
             } else if (P.kappa == -1) {
                 x = cmake(0.5 * log(1.0 + a2), 0.0);
             } else {
-                if (a2 > 1.0 - tol) fa_atomic_or_i32(P.status, 8);
+                if (a2 > 1.0 - tol) fa_atomic_or_i32(Pst, 8);
                 const double v = 1.0 - a2;   // 0.5*clog(v): log|v| + i*pi for v < 0
                 x = cmake(0.5 * log(fabs(v)), v < 0.0 ? 0.5 * 3.14159265358979323846 : 0.0);
             }
-            P.out[i] = x;
+            Pout[i] = x;
         } break;
         case INV_HILBERT: {
             const long long h = P.n / 2;
-            const cplx v = P.a[i];
+            const cplx v = Pa[i];
             const double m = 1.0 / (double)P.n;
             cplx r;
             if (i == 0 || i == h - 1) r = cmake(0.0, 0.0);
             else if (i < h - 1) r = cmake(v.y * m, -v.x * m);      // * (-i/M)
             else r = cmake(-v.y * m, v.x * m);                     // * (+i/M)
-            P.out[i] = r;
+            Pout[i] = r;
         } break;
         case INV_SPEC_RESP: {
-            const cplx x = P.a[i], y = P.b[i];
+            const cplx x = Pa[i], y = Pb[i];
             // exp(x - i*y) / M
             const double re = x.x + y.y, im = x.y - y.x;
             double sn, cs;
             fa_sincos(im, &sn, &cs);
             const double m = exp(re) / (double)P.n;
-            P.out[i] = cmake(m * cs, m * sn);
+            Pout[i] = cmake(m * cs, m * sn);
         } break;
-        case INV_REV_CONJ: P.out[i] = cconj(P.a[P.i0 - i]); break;
+        case INV_REV_CONJ: Pout[i] = cconj(Pa[P.i0 - i]); break;
         case INV_ITER_FIN: {
-            const cplx q = P.a[i];
+            const cplx q = Pa[i];
             const double d = 1.0 / (sqrt(1.0 + (double)P.kappa * cnorm2(q)) * (double)P.n);
-            P.out[i] = q * d;
+            Pout[i] = q * d;
         } break;
-        case INV_REVERSE: P.out[i] = P.a[P.n - 1 - i]; break;
+        case INV_REVERSE: Pout[i] = Pa[P.n - 1 - i]; break;
         case INV_ITER_PHASE: {
-            const cplx v = P.a[i];
+            const cplx v = Pa[i];
             const double ph = atan2(v.y, v.x);
             mine = fabs(ph);
             const long long h = P.n / 2;
-            const cplx c = P.b[(i <= h) ? i + (h - 1) : i - (h + 1)];
+            const cplx c = Pb[(i <= h) ? i + (h - 1) : i - (h + 1)];
             double sn, cs;
             fa_sincos(ph, &sn, &cs);
-            P.out[i] = c * cmake(cs, sn);
+            Pout[i] = c * cmake(cs, sn);
         } break;
         case INV_BTAU: {
             const double f = (i == 0 || i == P.n - 1) ? P.s0 : 2.0 * P.s0;
-            P.out[i] = P.a[i] * f;
+            Pout[i] = Pa[i] * f;
         } break;
-        case INV_DOUBLE_Q: P.out[i] = P.a[(i + 1) / 2]; break;
+        case INV_DOUBLE_Q: Pout[i] = Pa[(i + 1) / 2]; break;
+        case INV_TM_B: {
+            const long long w = P.n / 4, deg = w - 1, k = i % w;
+            const int e = (int)(i / w);
+            cplx v = cmake(0.0, 0.0);
+            if (e == 1) {
+                if (k >= P.i0) v = cconj(Pa[P.i1 - 1 - deg + k] * P.s0) * (double)(-P.kappa);
+            } else if (e == 2) {
+                if (k >= P.i0) v = Pa[deg - k] * P.s0;
+            } else if (P.s1 != 0.0 && ((e == 0 && k == deg) || (e == 3 && k == 0))) {
+                v = cmake(1.0, 0.0);
+            }
+            Pout[i] = v;
+        } break;
+        case INV_TM_AB: {
+            const long long w = P.n / 4, D = w - 1, k = i % w;
+            const int e = (int)(i / w);
+            cplx v = cmake(0.0, 0.0);
+            if (e == 0) { if (k >= 1) v = Pa[k - 1]; }
+            else if (e == 1) { if (k < D) v = cconj(Pb[D - 1 - k]) * (double)(-P.kappa); }
+            else if (e == 2) { if (k >= 1) v = Pb[k - 1]; }
+            else if (k < D) v = Pa[D - 1 - k];
+            Pout[i] = v;
+        } break;
         default: break;
         }
     }
@@ -2908,23 +2946,27 @@ struct PeelIoParams {
     const cplx *A, *B;        // four entries of d+1 coefficients each, highest power first
     long long As, Bs;         // entry strides
     long long d;
-    cplx *body, *tail;        // import: level 0 of the plan (plane = 2*d)
+    cplx *body, *tail;        // import: level 0 of the plan (2 matrices per signal, plane = n0*d)
     double *scale;
     int *wexp;
+    // batch: signal s's factors at A + s*Ab, B + s*Bb, its two matrices at 2s, 2s+1 of the plan (n0 = 2*batch)
+    long long batch, Ab, Bb, n0;
 };
 FA_DEV void body_peel_import(const PeelIoParams &P)
 {
-    const long long i = (long long)FA_BID * FA_BDIM + FA_TID;
+    const long long gi = (long long)FA_BID * FA_BDIM + FA_TID;
     const long long w = P.d + 1;
-    if (i >= 8 * w) return;
+    if (gi >= 8 * w * P.batch) return;
+    const long long sg = gi / (8 * w), i = gi % (8 * w);
     const int e = (int)(i / (2 * w));
     const long long r = i % (2 * w);
     const int m = (int)(r / w);
     const long long k = r % w;
-    const cplx v = m == 0 ? P.A[(long long)e * P.As + k] : P.B[(long long)e * P.Bs + k];
-    if (k < P.d) P.body[(long long)e * 2 * P.d + (long long)m * P.d + k] = v;
-    else P.tail[e * 2 + m] = v;
-    if (i < 2) { P.scale[i] = 1.0; P.wexp[i] = 0; }
+    const long long j = 2 * sg + m;   // matrix of the plan
+    const cplx v = m == 0 ? P.A[sg * P.Ab + (long long)e * P.As + k] : P.B[sg * P.Bb + (long long)e * P.Bs + k];
+    if (k < P.d) P.body[(long long)e * P.n0 * P.d + j * P.d + k] = v;
+    else P.tail[e * P.n0 + j] = v;
+    if (i < 2) { P.scale[2 * sg + i] = 1.0; P.wexp[2 * sg + i] = 0; }
 }
 // One 2x2 polynomial product of the layer peeling in ONE launch, for the degrees where a product is a single
 // workgroup's work anyway (deg = N/2 = 256, 512, 1024): the four entries of a factor are transformed CONCURRENTLY
@@ -2937,6 +2979,7 @@ struct PeelProdParams {
     cplx *C;                  // four entries of 2 deg + 1 coefficients
     long long Cs;
     const cplx *tw;           // exp(-2 pi i j / N), j < N
+    long long Ab, Bb, Cb;     // batch (grid.y = signal): per-signal strides of A, B, C (0 for one signal)
 };
 template <int N, int R> FA_DEV void body_peel_product(const PeelProdParams &P)
 {
@@ -2946,16 +2989,18 @@ template <int N, int R> FA_DEV void body_peel_product(const PeelProdParams &P)
     const int tid = FA_TID;
     const int g = tid % 4, v = tid / 4; // entry of this lane's group, lane inside the group
     const int r = g >> 1, cc = g & 1;   // row and column of the result entry this group forms
+    const long long sg = FA_BID_Y;
+    const cplx *PA = P.A + sg * P.Ab, *PB = P.B + sg * P.Bb;
     cplx a[R], b[R];
 #pragma unroll
     for (int i = 0; i < R; i++) {
         const int n = v + (N / R) * i;
-        a[i] = (n <= DEG) ? P.A[(long long)g * P.As + n] : cmake(0.0, 0.0);   // deg + 1 coefficients, zero-padded to N
-        b[i] = (n <= DEG) ? P.B[(long long)g * P.Bs + n] : cmake(0.0, 0.0);
+        a[i] = (n <= DEG) ? PA[(long long)g * P.As + n] : cmake(0.0, 0.0);   // deg + 1 coefficients, zero-padded to N
+        b[i] = (n <= DEG) ? PB[(long long)g * P.Bs + n] : cmake(0.0, 0.0);
     }
     // constant terms of the row of A and the column of B this group needs: the aliased coefficient
-    const cplx tp = P.A[(long long)(2 * r) * P.As + DEG] * P.B[(long long)cc * P.Bs + DEG]
-                  + P.A[(long long)(2 * r + 1) * P.As + DEG] * P.B[(long long)(2 + cc) * P.Bs + DEG];
+    const cplx tp = PA[(long long)(2 * r) * P.As + DEG] * PB[(long long)cc * P.Bs + DEG]
+                  + PA[(long long)(2 * r + 1) * P.As + DEG] * PB[(long long)(2 + cc) * P.Bs + DEG];
     int parity = 0;
     fft_wg<N, R, 4, -1, false, true>(a, lds, v, g, P.tw, parity);
     fft_wg<N, R, 4, -1, false, true>(b, lds, v, g, P.tw, parity);
@@ -2982,7 +3027,7 @@ template <int N, int R> FA_DEV void body_peel_product(const PeelProdParams &P)
     FA_SYNC_LDS();
     fft_wg<N, R, 4, +1, false, true>(a, lds, v, g, P.tw, parity);
     const double inv = 1.0 / (double)N;
-    cplx *dst = P.C + (long long)g * P.Cs;
+    cplx *dst = P.C + sg * P.Cb + (long long)g * P.Cs;
 #pragma unroll
     for (int i = 0; i < R; i++) {
         const int n = v + (N / R) * i;
@@ -3014,6 +3059,8 @@ struct PeelLeafParams {
     double eps_t;
     int kappa, modal;
     int *status;              // bit 4: a reconstructed sample violates 1 + kappa |eps q|^2 > 0 (:173-176); bit 5: internal
+    long long Tb, Tib, qb;    // batch (grid.y = signal): per-signal strides of T, Ti, q (0 for one signal)
+    int sb;                   // and of the status word
 };
 FA_DEV cplx fa_shfl_c(cplx v, int src) { return cmake(fa_shfl(v.x, src), fa_shfl(v.y, src)); }
 FA_DEV cplx fa_readlane_c(cplx v, int src) { return cmake(fa_readlane(v.x, src), fa_readlane(v.y, src)); }
@@ -3025,8 +3072,16 @@ FA_DEV cplx fa_shfl_down_cz(cplx v) { return cmake(fa_shfl_down1_z(v.x), fa_shfl
 #ifndef FA_PEEL_DIAG
 #define FA_PEEL_DIAG 0
 #endif
-FA_DEV void body_peel_leaf(const PeelLeafParams &P)
+FA_DEV void body_peel_leaf(const PeelLeafParams &P0)
 {
+    PeelLeafParams P = P0;                       // this workgroup's signal
+    {
+        const long long sg = FA_BID_Y;
+        P.T += sg * P0.Tb;
+        if (P0.Ti) P.Ti += sg * P0.Tib;
+        P.q += sg * P0.qb;
+        P.status += sg * P0.sb;
+    }
     constexpr int R = 4;
     FA_LDS_DECL
     cplx *Qs = (cplx *)FA_LDS_PTR;               // 256 step parameters Q

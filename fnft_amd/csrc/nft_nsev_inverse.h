@@ -33,6 +33,9 @@ inline size_t nft_next_fast_size(size_t n)
 // n = 2 matrices: the tree's general pair kernels), factors and results moved between the caller's strided arrays
 // and the plans' layout by two small kernels.  Work arrays: one set per recursion depth (depth-first order on one
 // stream, so siblings reuse them).
+// batch > 1: that many independent signals peeled together -- every launch covers the whole batch (grid.y = signal for
+// the leaf and the one-launch products, plans created with `batch` signals of two matrices each), every array holds the
+// signals at a fixed distance (the *b arguments), and the status word is one int per signal.
 template <class BE> class NftLayerPeelingDev {
 public:
     static constexpr size_t kLeaf = 256;
@@ -40,13 +43,15 @@ public:
     BE &be;
     double eps_t;
     int kappa, modal;
+    size_t batch = 1;
     int rc = NFT_SUCCESS;
-    int *d_status = nullptr;
+    int *d_status = nullptr;     // max(4, batch) ints: signal s's status at d_status[s]
     std::map<size_t, NftPlan<BE> *> plans;
     struct Work { cplx *T2i = nullptr, *T1 = nullptr, *T1i = nullptr; };
     std::vector<Work> work;
 
     NftLayerPeelingDev(BE &b, double eps, int kap, int is_modal) : be(b), eps_t(eps), kappa(kap), modal(is_modal) {}
+    size_t status_words() const { return std::max<size_t>(4, batch); }
     ~NftLayerPeelingDev() { destroy(); }
     void destroy()
     {
@@ -65,23 +70,23 @@ public:
     {
         rc = NFT_SUCCESS;
         if (!d_status) {
-            d_status = (int *)be.alloc(4 * sizeof(int));
+            d_status = (int *)be.alloc(status_words() * sizeof(int));
             if (!d_status) return NFT_EC_NOMEM;
         }
-        be.memset0(d_status, 4 * sizeof(int));
+        be.memset0(d_status, status_words() * sizeof(int));
         if (deg > work_deg) {
             for (auto &w : work) { be.free(w.T2i); be.free(w.T1); be.free(w.T1i); }
             work.clear();
             work_deg = 0;
             for (size_t d = deg; d > kLeaf; d /= 2) {
                 Work w;
-                w.T2i = (cplx *)be.alloc(4 * (d + 1) * sizeof(cplx));
-                w.T1 = (cplx *)be.alloc(4 * (2 * d + 1) * sizeof(cplx));
-                w.T1i = (cplx *)be.alloc(4 * (d / 2 + 1) * sizeof(cplx));
+                w.T2i = (cplx *)be.alloc(batch * 4 * (d + 1) * sizeof(cplx));
+                w.T1 = (cplx *)be.alloc(batch * 4 * (2 * d + 1) * sizeof(cplx));
+                w.T1i = (cplx *)be.alloc(batch * 4 * (d / 2 + 1) * sizeof(cplx));
                 work.push_back(w);
                 if (!w.T2i || !w.T1 || !w.T1i) return NFT_EC_NOMEM;
                 // the upper half of T2i (coefficients 0 .. d/2 - 1 of every entry) is never written: zero once
-                be.memset0(w.T2i, 4 * (d + 1) * sizeof(cplx));
+                be.memset0(w.T2i, batch * 4 * (d + 1) * sizeof(cplx));
             }
             work_deg = deg;
         }
@@ -91,15 +96,27 @@ public:
     {
         auto it = plans.find(deg);
         if (it != plans.end()) return it->second;
-        NftPlan<BE> *pl = new (std::nothrow) NftPlan<BE>(be, 2, 0, 1, -1, (int)deg);
+        NftPlan<BE> *pl = new (std::nothrow) NftPlan<BE>(be, 2, 0, batch, -1, (int)deg);
         if (!pl) { rc = NFT_EC_NOMEM; return nullptr; }
         const int r = pl->init();
         if (r != NFT_SUCCESS) { rc = r; pl->destroy(); delete pl; return nullptr; }
         plans[deg] = pl;
         return pl;
     }
-    // C (four entries of 2 deg + 1 coefficients at stride Cs) = A * B (four entries of deg + 1 at strides As, Bs)
-    void prod(size_t deg, const cplx *A, size_t As, const cplx *B, size_t Bs, cplx *C, size_t Cs)
+    // every plan and work array a peeling of degree deg will use (the batched call allocates nothing while it runs)
+    int prepare(size_t deg)
+    {
+        const int r = init(deg);
+        if (r != NFT_SUCCESS) return r;
+        if (deg > kLeaf && !plan_for(kLeaf * 2)) return rc;
+        for (size_t d = deg; d > kLeaf; d /= 2)
+            if (d != 256 && d != 512 && d != kOneLaunchMaxDeg && !plan_for(d)) return rc;
+        return NFT_SUCCESS;
+    }
+    // C (four entries of 2 deg + 1 coefficients at stride Cs) = A * B (four entries of deg + 1 at strides As, Bs);
+    // Ab, Bb, Cb: distances between the signals of the batch
+    void prod(size_t deg, const cplx *A, size_t As, size_t Ab, const cplx *B, size_t Bs, size_t Bb, cplx *C, size_t Cs,
+              size_t Cb)
     {
         if (rc != NFT_SUCCESS) return;
         if (deg == 256 || deg == 512 || deg == kOneLaunchMaxDeg) {   // one launch, entries transformed concurrently
@@ -109,9 +126,11 @@ public:
             std::memset(&Q, 0, sizeof(Q));
             Q.A = A; Q.B = B; Q.As = (long long)As; Q.Bs = (long long)Bs; Q.C = C; Q.Cs = (long long)Cs;
             Q.tw = tp->tw_table(2 * deg);
-            if (deg == 256) be.template run<KPeelProduct<512>>(1, 1, Q);
-            else if (deg == 512) be.template run<KPeelProduct<1024>>(1, 1, Q);
-            else be.template run<KPeelProduct<2048>>(1, 1, Q);
+            Q.Ab = (long long)Ab; Q.Bb = (long long)Bb; Q.Cb = (long long)Cb;
+            const int gy = (int)batch;
+            if (deg == 256) be.template run<KPeelProduct<512>>(1, gy, Q);
+            else if (deg == 512) be.template run<KPeelProduct<1024>>(1, gy, Q);
+            else be.template run<KPeelProduct<2048>>(1, gy, Q);
             return;
         }
         NftPlan<BE> *pl = plan_for(deg);
@@ -120,18 +139,20 @@ public:
         std::memset(&P, 0, sizeof(P));
         P.A = A; P.B = B; P.As = (long long)As; P.Bs = (long long)Bs; P.d = (long long)deg;
         P.body = pl->body[0]; P.tail = pl->tail[0]; P.scale = pl->scale[0]; P.wexp = pl->wexp[0];
-        be.template run<KPeelImport>((int)((8 * (deg + 1) + 255) / 256), 1, P);
+        P.batch = (long long)batch; P.Ab = (long long)Ab; P.Bb = (long long)Bb; P.n0 = (long long)pl->n0;
+        be.template run<KPeelImport>((int)((batch * 8 * (deg + 1) + 255) / 256), 1, P);
         pl->cur = 0;
         pl->ne = 4;
         pl->start_n = pl->n0;
         pl->start_d = deg;
         const int r = pl->run_tree();
         if (r != NFT_SUCCESS) { rc = r; return; }
-        pl->export_tm(C, Cs, true);     // result layout, un-normalised, straight into the caller's strided array
+        pl->export_tm(C, Cs, true, Cb); // result layout, un-normalised, straight into the caller's strided array
     }
     // T: four entries of deg+1 coefficients at stride Ts; Ti (may be NULL): the inverse up to a power of z, four
-    // entries of deg+1 at stride Tis; q: deg samples.  All device pointers.
-    void peel(size_t deg, const cplx *T, size_t Ts, cplx *Ti, size_t Tis, cplx *q, size_t depth = 0)
+    // entries of deg+1 at stride Tis; q: deg samples.  All device pointers; Tb, Tib, qb: distances between the signals
+    void peel(size_t deg, const cplx *T, size_t Ts, size_t Tb, cplx *Ti, size_t Tis, size_t Tib, cplx *q, size_t qb,
+              size_t depth = 0)
     {
         if (rc != NFT_SUCCESS) return;
         if (deg <= kLeaf) {
@@ -139,7 +160,8 @@ public:
             std::memset(&L, 0, sizeof(L));
             L.T = T; L.Ts = (long long)Ts; L.d = (int)deg; L.Ti = Ti; L.Tis = (long long)Tis; L.q = q;
             L.eps_t = eps_t; L.kappa = kappa; L.modal = modal; L.status = d_status;
-            be.template run<KPeelLeaf>(1, 1, L);
+            L.Tb = (long long)Tb; L.Tib = (long long)Tib; L.qb = (long long)qb; L.sb = 1;
+            be.template run<KPeelLeaf>(1, (int)batch, L);
             return;
         }
         const size_t h = deg / 2;
@@ -147,11 +169,12 @@ public:
         for (size_t d = work_deg; d > deg; d /= 2) slot++;
         (void)depth;
         Work &w = work[slot];
+        const size_t b2i = 4 * (deg + 1), b1 = 4 * (2 * deg + 1), b1i = 4 * (h + 1);   // per signal
         // w.T2i: the child below fills coefficients h .. deg of every entry; 0 .. h-1 are zero since init()
-        peel(h, T + h, Ts, w.T2i + h, deg + 1, q + h, depth + 1);             // step 1, :107-116
-        prod(deg, w.T2i, deg + 1, T, Ts, w.T1, 2 * deg + 1);                  // step 2, :120-127
-        peel(h, w.T1 + deg, 2 * deg + 1, w.T1i, h + 1, q, depth + 1);         // step 3, :131-140
-        if (Ti) prod(h, w.T1i, h + 1, w.T2i + h, deg + 1, Ti, Tis);           // step 4, :144-156
+        peel(h, T + h, Ts, Tb, w.T2i + h, deg + 1, b2i, q + h, qb, depth + 1);                    // step 1, :107-116
+        prod(deg, w.T2i, deg + 1, b2i, T, Ts, Tb, w.T1, 2 * deg + 1, b1);                        // step 2, :120-127
+        peel(h, w.T1 + deg, 2 * deg + 1, b1, w.T1i, h + 1, b1i, q, qb, depth + 1);               // step 3, :131-140
+        if (Ti) prod(h, w.T1i, h + 1, b1i, w.T2i + h, deg + 1, b2i, Ti, Tis, Tib);              // step 4, :144-156
     }
     // host-pointer driver: tm (4*(deg+1)) -> q[deg]
     int run_host(size_t deg, const std::complex<double> *tm, std::complex<double> *q)
@@ -161,7 +184,7 @@ public:
         if (r == NFT_SUCCESS && (!dT || !dq)) r = NFT_EC_NOMEM;
         if (r == NFT_SUCCESS) {
             be.h2d(dT, tm, 4 * (deg + 1) * sizeof(cplx));
-            peel(deg, dT, deg + 1, nullptr, 0, dq);
+            peel(deg, dT, deg + 1, 0, nullptr, 0, 0, dq, 0);
             r = rc;
         }
         if (r == NFT_SUCCESS) {
@@ -489,5 +512,154 @@ public:
         be.free(dbs); be.free(dnc); be.free(dq); be.free(work); be.free(dq2); be.free(cm); be.free(bnd); be.free(bndp);
         be.free(PHI); be.free(PSI); be.free(dout);
         return rc;
+    }
+};
+
+// Batched, device-resident continuous part of fnft_nsev_inverse (K = 0): `batch` signals of one size and one set of
+// options per call, every launch covering the whole batch, nothing copied to or from the host and no allocation while
+// a call runs.  Per signal the arithmetic is that of the host-pointer driver above (NftInverseDev::transfer_matrix,
+// then NftLayerPeelingDev::run_host): the same kernels, with the transfer matrix formed on the device (INV_TM_B /
+// INV_TM_AB) instead of on the host.  Every array holds the signals back to back.
+template <class BE> class NftInverseBatch {
+public:
+    BE &be;
+    const size_t D, M, B;
+    const int cstype;            // 0 rho, 1 b(xi), 2 B(tau)
+    const size_t os;             // oversampling factor of the spectral factorization
+    NftPlan<BE> pl;              // twiddle tables only
+    NftLayerPeelingDev<BE> lp;
+    size_t Mf = 0, Lcap = 0, bytes = 0;
+    cplx *dY = nullptr, *dV = nullptr, *dc = nullptr, *dr = nullptr, *db = nullptr, *da = nullptr, *dtm = nullptr;
+    cplx *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
+    int *dchirp = nullptr;       // status word of the DFTs (DFT mode sets no bit)
+
+    NftInverseBatch(BE &b, size_t D_, size_t M_, size_t B_, int cstype_, size_t os_, int modal)
+        : be(b), D(D_), M(M_), B(B_), cstype(cstype_), os(os_), pl(b, 2, 0, 1, 0, 1), lp(b, 1.0, 1, modal)
+    {
+        lp.batch = B;
+    }
+    ~NftInverseBatch() { destroy(); }
+    void destroy()
+    {
+        lp.destroy();
+        for (cplx *p : {dY, dV, dc, dr, db, da, dtm, w0, w1, w2}) be.free(p);
+        be.free(dchirp);
+        be.free(pl.twtab); be.free(pl.twlo);
+        dY = dV = dc = dr = db = da = dtm = w0 = w1 = w2 = nullptr;
+        dchirp = nullptr;
+        pl.twtab = nullptr; pl.twlo = nullptr;
+    }
+    int init()
+    {
+        const size_t deg = D;
+        if (cstype != 0) Mf = NftInverseDev<BE>::specfact_len(cstype == 1 ? deg : D - 1, os);
+        const size_t L = NftInverseDev<BE>::dft_L(std::max(cstype == 2 ? D : M, Mf));
+        if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
+        Lcap = L;
+        bool ok = pl.alloc(pl.twtab, (size_t)2 * kMaxTwTable) && pl.alloc(pl.twlo, kTwLoEntries);
+        ok = ok && pl.alloc(dY, B * L) && pl.alloc(dV, L) && pl.alloc(dchirp, 4) && pl.alloc(dtm, B * 4 * (deg + 1));
+        if (cstype != 2) ok = ok && pl.alloc(dc, B * M) && pl.alloc(dr, B * M) && pl.alloc(db, B * M);
+        else ok = ok && pl.alloc(db, B * D) && pl.alloc(da, B * D);
+        if (cstype != 0) ok = ok && pl.alloc(w0, B * Mf) && pl.alloc(w1, B * Mf) && pl.alloc(w2, B * Mf);
+        if (!ok) return NFT_EC_NOMEM;
+        pl.upload_twiddles();
+        be.memset0(dchirp, 4 * sizeof(int));
+        const int r = lp.prepare(deg);
+        if (r != NFT_SUCCESS) return r;
+        bytes = pl.bytes + lp.status_words() * sizeof(int);
+        for (size_t d = deg; d > NftLayerPeelingDev<BE>::kLeaf; d /= 2)
+            bytes += B * 4 * ((d + 1) + (2 * d + 1) + (d / 2 + 1)) * sizeof(cplx);
+        for (auto &kv : lp.plans) bytes += kv.second->bytes;
+        return be.sync();
+    }
+    // out[s*n + k] = sum_j in[s*n + j] exp(sign 2 pi i j k / n) for every signal s (NftInverseDev::dft, batched)
+    int dft(const cplx *d_in, cplx *d_out, size_t n, int sign)
+    {
+        const size_t L = NftInverseDev<BE>::dft_L(n);
+        if (L > Lcap) return NFT_EC_OTHER;
+        ChirpParams C;
+        std::memset(&C, 0, sizeof(C));
+        C.poly = d_in;
+        C.deg = (long long)n - 1;
+        C.batch = (int)B;
+        C.npoly = 1;
+        C.M = (long long)n;
+        C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = d_out;
+        pl.fill_chirp_geometry(C, L);
+        C.status = dchirp;
+        C.cstype = -1;
+        C.dft_len = (long long)n;
+        C.dft_sign = sign;
+        return pl.run_chirp(C);
+    }
+    // body_inv_op over n elements of every signal; sa, sb, so: distances between the signals of a, b, out
+    void op(int code, size_t n, const cplx *a, size_t sa, const cplx *b, size_t sb, cplx *out, size_t so,
+            cplx *out2 = nullptr, size_t so2 = 0, double s0 = 0, double s1 = 0, double s2 = 0, long long i0 = 0,
+            int kappa = 0, long long i1 = 0)
+    {
+        InvOpParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.op = code; P.n = (long long)n; P.a = a; P.b = b; P.out = out; P.out2 = out2;
+        P.s0 = s0; P.s1 = s1; P.s2 = s2; P.i0 = i0; P.i1 = i1; P.kappa = kappa;
+        P.sa = (long long)sa; P.sb = (long long)sb; P.sout = (long long)so; P.sout2 = (long long)so2;
+        P.status = lp.d_status; P.sst = 1;
+        be.template run<KInvOp>((int)((n + 255) / 256), (int)B, P);
+    }
+    // NftInverseDev::specfact for every signal: poly (deg+1 coefficients at distance pb) -> result (distance rb)
+    int specfact(size_t deg, const cplx *poly, size_t pb, cplx *result, size_t rb, int kappa)
+    {
+        op(INV_PAD, Mf, poly, pb, nullptr, 0, w0, Mf, nullptr, 0, 0, 0, 0, (long long)deg);
+        int rc = dft(w0, w1, Mf, -1);
+        if (rc != NFT_SUCCESS) return rc;
+        op(INV_SPEC_X, Mf, w1, Mf, nullptr, 0, w2, Mf, nullptr, 0, 0, 0, 0, 0, kappa);
+        rc = dft(w2, w0, Mf, -1);
+        if (rc != NFT_SUCCESS) return rc;
+        op(INV_HILBERT, Mf, w0, Mf, nullptr, 0, w0, Mf);
+        rc = dft(w0, w1, Mf, +1);
+        if (rc != NFT_SUCCESS) return rc;
+        op(INV_SPEC_RESP, Mf, w2, Mf, w1, Mf, w0, Mf);
+        rc = dft(w0, w1, Mf, +1);
+        if (rc != NFT_SUCCESS) return rc;
+        op(INV_REV_CONJ, deg + 1, w1, Mf, nullptr, 0, result, rb, nullptr, 0, 0, 0, 0, (long long)deg);
+        return NFT_SUCCESS;
+    }
+    // d_cs: B*M values (B(tau): B*D), d_q: B*D samples.  pf, eps_t: formed by the caller as the host driver forms
+    // them.  Enqueued on be.stream; the per-signal status words are read by the caller after the stream is done.
+    int run(const cplx *d_cs, const double *XI, cplx *d_q, double eps_t, int kappa, double pf)
+    {
+        const size_t deg = D, per = 4 * (deg + 1);
+        lp.rc = NFT_SUCCESS;
+        lp.eps_t = eps_t;
+        lp.kappa = kappa;
+        be.memset0(lp.d_status, lp.status_words() * sizeof(int));
+        int rc = NFT_SUCCESS;
+        if (cstype != 2) {
+            const double eps_xi = (XI[1] - XI[0]) / (double)(M - 1);
+            op(INV_PREP, M, d_cs, M, nullptr, 0, dc, M, dr, M, XI[0], eps_xi, pf);
+            rc = dft(dr, db, M, -1);                                                  // B(z), :340 / :594
+            if (rc != NFT_SUCCESS) return rc;
+            const long long i0 = (deg <= M - 1) ? 0 : (long long)(deg - (M - 1));
+            op(INV_TM_B, per, db, M, nullptr, 0, dtm, per, nullptr, 0, 1.0 / (double)M, cstype == 0 ? 1.0 : 0.0, 0, i0,
+               kappa, (long long)M);
+            if (cstype == 1) {                                                        // A, :615-620
+                rc = specfact(deg, dtm + 2 * (deg + 1), per, dtm, per, kappa);
+                if (rc != NFT_SUCCESS) return rc;
+                op(INV_REVERSE, deg + 1, dtm, per, nullptr, 0, dtm + 3 * (deg + 1), per);
+            }
+        } else {                                                                      // :632-676
+            op(INV_BTAU, D, d_cs, D, nullptr, 0, db, D, nullptr, 0, eps_t);
+            rc = specfact(D - 1, db, D, da, D, kappa);
+            if (rc != NFT_SUCCESS) return rc;
+            op(INV_TM_AB, per, da, D, db, D, dtm, per, nullptr, 0, 0, 0, 0, 0, kappa);
+        }
+        lp.peel(deg, dtm, deg + 1, per, nullptr, 0, 0, d_q, D);
+        return lp.rc;
+    }
+    // after the stream is done: status word of every signal (bit 3 ill-posed factorization, bits 4, 5 the leaf's)
+    int read_status(std::vector<int> &st)
+    {
+        st.assign(B, 0);
+        be.d2h(st.data(), lp.d_status, B * sizeof(int));
+        return be.sync();
     }
 };

@@ -457,6 +457,32 @@ FNFT_INT fnft_amd_plan_get_transfer_matrix(fnft_amd_plan_t *plan, FNFT_UINT b,
 FNFT_INT fnft_amd_plan_get_transfer_matrix_device(fnft_amd_plan_t *plan, FNFT_UINT b, void *d_result,
                                                   FNFT_UINT *deg, FNFT_INT *W, void *stream);
 
+/* Batched, device-resident fnft_nsev_inverse (continuous part, K = 0): `batch` independent inverse transforms of M
+ * spectral values to D samples each, one set of options, every signal's arithmetic that of fnft_nsev_inverse on it
+ * alone.  Covered: REFLECTION_COEFFICIENT (methods DEFAULT, TFMATRIX_CONTAINS_REFL_COEFF), B_OF_XI (spectral
+ * factorization at opts->oversampling_factor) and B_OF_TAU; 2SPLIT2A and 2SPLIT2_MODAL; kappa = +-1.  D, M, T, kappa,
+ * XI and the oversampling factor follow fnft_nsev_inverse's rules and return its codes in its order (B_OF_TAU with
+ * M != D or T[0] != -T[1]: -FNFT_EC_INVALID_ARGUMENT, as there); the checks that depend on sizes and options run at
+ * create time, before any HIP call.  TFMATRIX_CONTAINS_AB_FROM_ITER and USE_SEED_POTENTIAL_INSTEAD return
+ * FNFT_EC_NOT_YET_IMPLEMENTED at create time.  Every workspace is allocated at create; a call allocates nothing and
+ * never waits for the device.  Leaves, products and DFTs of all signals run in the same launches (grid.y = signal). */
+typedef struct fnft_amd_inverse_plan fnft_amd_inverse_plan_t;
+FNFT_INT fnft_amd_inverse_plan_create(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
+                                      fnft_nsev_inverse_opts_t const *opts, int device);
+/* Waits for the plan's last stream, then gives its workspace back.  NULL is ignored. */
+void fnft_amd_inverse_plan_destroy(fnft_amd_inverse_plan_t *plan);
+/* Bytes of HBM the plan holds. */
+FNFT_UINT fnft_amd_inverse_plan_workspace_bytes(const fnft_amd_inverse_plan_t *plan);
+/* d_contspec: batch*M complex128 (device; signal b at +b*M; B_OF_TAU: M = D samples of B(tau)), NOT modified;
+ * d_q: batch*D complex128 (device) out.  XI, T: host, shared by the batch.  Asynchronous on `stream` (a hipStream_t,
+ * NULL = default stream). */
+FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void *d_contspec, const FNFT_REAL *XI,
+                                      void *d_q, const FNFT_REAL *T, FNFT_INT kappa, void *stream);
+/* Waits for `stream`.  status[b] (may be NULL): what fnft_nsev_inverse returns for signal b alone (0 or a negative
+ * code); warnings[b] (may be NULL): bit 0 = "Ill-posed spectral factorization problem." for signal b.  Returns 0 if
+ * every signal succeeded, else the status of the lowest-index failing signal. */
+FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *stream, FNFT_INT *status, int *warnings);
+
 /* ======================================================================================== */
 /* 4. Korteweg-de Vries equation, vanishing boundaries (include/fnft_kdvv.h)                  */
 /* ======================================================================================== */
