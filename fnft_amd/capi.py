@@ -104,7 +104,8 @@ EXPORTED = [
     "fnft_amd_kdvv_plan_create", "fnft_amd_kdvv_contspec_device", "fnft_amd_kdvv_plan_set_real_mode",
     "fnft_amd_release_cached", "fnft_nsep", "fnft_nsep_default_opts", "fnft_amd_poly_fmult2x2_device",
     "fnft_amd_inverse_plan_create", "fnft_amd_inverse_plan_destroy", "fnft_amd_inverse_plan_workspace_bytes",
-    "fnft_amd_nsev_inverse_device", "fnft_amd_inverse_plan_finish",
+    "fnft_amd_nsev_inverse_device", "fnft_amd_inverse_plan_finish", "fnft_amd_inverse_plan_create_discrete",
+    "fnft_amd_nsev_inverse_discrete_device",
 ]
 
 _lib = None
@@ -246,6 +247,11 @@ def load(path=None):
     L.fnft_amd_nsev_inverse_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
     L.fnft_amd_inverse_plan_finish.restype = i32
     L.fnft_amd_inverse_plan_finish.argtypes = [vp, vp, vp, vp]
+    L.fnft_amd_inverse_plan_create_discrete.restype = i32
+    L.fnft_amd_inverse_plan_create_discrete.argtypes = [C.POINTER(vp), sz, sz, sz, sz, C.POINTER(NsevInverseOpts),
+                                                        C.c_int]
+    L.fnft_amd_nsev_inverse_discrete_device.restype = i32
+    L.fnft_amd_nsev_inverse_discrete_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
     if path is None:
         _lib = L
     return L
@@ -772,19 +778,26 @@ class Plan:
 
 
 class InversePlan:
-    """fnft_amd_inverse_plan_t: `batch` inverse transforms (continuous part) of M spectral values to D samples each,
-    one set of options (dict as for fnft_nsev_inverse), device-resident.  Raises RuntimeError (attribute rc) if the
+    """fnft_amd_inverse_plan_t: `batch` inverse transforms of M spectral values to D samples each, one set of options
+    (dict as for fnft_nsev_inverse), device-resident.  K = 0: the continuous part (run_device); K > 0: K bound states
+    per signal on top of it, or alone with M = 0 (run_device_discrete).  Raises RuntimeError (attribute rc) if the
     plan cannot be created."""
 
-    def __init__(self, D, M, batch=1, opts=None, device=0):
+    def __init__(self, D, M, batch=1, opts=None, device=0, K=0):
         self.L = load()
-        self.D, self.M, self.batch = int(D), int(M), int(batch)
+        self.D, self.M, self.batch, self.K = int(D), int(M), int(batch), int(K)
         self.opts = inverse_opts(opts)
         self.h = C.c_void_p()
-        rc = self.L.fnft_amd_inverse_plan_create(C.byref(self.h), self.D, self.M, self.batch, C.byref(self.opts),
-                                                 int(device))
+        if self.K > 0:
+            fn = "fnft_amd_inverse_plan_create_discrete"
+            rc = self.L.fnft_amd_inverse_plan_create_discrete(C.byref(self.h), self.D, self.M, self.K, self.batch,
+                                                              C.byref(self.opts), int(device))
+        else:
+            fn = "fnft_amd_inverse_plan_create"
+            rc = self.L.fnft_amd_inverse_plan_create(C.byref(self.h), self.D, self.M, self.batch, C.byref(self.opts),
+                                                     int(device))
         if rc != FNFT_SUCCESS:
-            err = RuntimeError("fnft_amd_inverse_plan_create rc=%d (%s)" % (rc, last_error()))
+            err = RuntimeError("%s rc=%d (%s)" % (fn, rc, last_error()))
             err.rc = int(rc)
             raise err
 
@@ -808,6 +821,15 @@ class InversePlan:
         return int(self.L.fnft_amd_nsev_inverse_device(self.h, C.c_void_p(cs_ptr), None if XI is None else _d2(XI),
                                                        C.c_void_p(q_ptr), None if T is None else _d2(T), int(kappa),
                                                        C.c_void_p(stream)))
+
+    def run_device_discrete(self, cs_ptr, bs_ptr, nc_ptr, q_ptr, XI, T, kappa, stream=0):
+        """Enqueue one call of a K > 0 plan: cs_ptr (batch*M complex128, 0 if M = 0), bs_ptr and nc_ptr (batch*K
+        complex128 bound states and norming constants or residues) -> q_ptr (batch*D complex128; the seed on entry with
+        USE_SEED_POTENTIAL_INSTEAD), raw device addresses.  XI may be None (M = 0, B_OF_TAU)."""
+        return int(self.L.fnft_amd_nsev_inverse_discrete_device(
+            self.h, C.c_void_p(cs_ptr or None), None if XI is None else _d2(XI), C.c_void_p(bs_ptr or None),
+            C.c_void_p(nc_ptr or None), C.c_void_p(q_ptr or None), None if T is None else _d2(T), int(kappa),
+            C.c_void_p(stream)))
 
     def finish(self, stream=0):
         """Waits for `stream`: (rc, status[batch], warnings[batch])."""

@@ -826,6 +826,7 @@ struct fnft_amd_inverse_plan {
     NftInverseBatch<HipBackend> *inv = nullptr;
     int device = 0;
     int cstype = 0;
+    size_t K = 0;                 // fnft_amd_inverse_plan_create_discrete: bound states per signal (>= 1)
     hipStream_t last_stream = nullptr;
     std::vector<int> st;
     std::mutex mtx;
@@ -916,6 +917,7 @@ FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void 
                                       void *d_q, const FNFT_REAL *T, FNFT_INT kappa, void *stream)
 {
     SEAM_CHECK(!plan, plan);
+    if (plan->K) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));   // K > 0 plan
     SEAM_CHECK(!d_contspec, contspec);
     SEAM_CHECK(!d_q, q);
     SEAM_CHECK(T == NULL || !(T[0] < T[1]), T);
@@ -941,6 +943,121 @@ FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void 
     return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
 }
 
+// K > 0: the continuous part as above (M > 0) or none (M = 0), then the discrete part (fnft_nsev_inverse_host.c and
+// src/fnft_nsev_inverse.c:680-903, in their order and with their codes)
+FNFT_INT fnft_amd_inverse_plan_create_discrete(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT K,
+                                               FNFT_UINT batch, fnft_nsev_inverse_opts_t const *opts, int device)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(M > 0 && M % 2 != 0, M);                               // fnft_nsev_inverse_host.c, in its order
+    SEAM_CHECK(M > 0 && M < D, M);
+    SEAM_CHECK(D < 2 || (D & (D - 1)) != 0, D);
+    SEAM_CHECK(batch == 0, batch);
+    const fnft_nsev_inverse_opts_t o = opts ? *opts : fnft_nsev_inverse_default_opts();
+    SEAM_CHECK(o.discretization != fnft_nse_discretization_2SPLIT2A
+               && o.discretization != fnft_nse_discretization_2SPLIT2_MODAL, opts->discretization);
+    if (K == 0) {
+        if (M == 0)
+            return fnft_amd__raise(FNFT_EC_SANITY_CHECK_FAILED, __func__, __LINE__,
+                                   "Sanity check failed (Neither contspec nor discspec provided.).");
+        return seam_invalid(__func__, __LINE__, "K");                 // K = 0: fnft_amd_inverse_plan_create
+    }
+    if (K > NftInverseDiscBatch<HipBackend>::kMaxGridY)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched inverse: more than 65535 bound states per signal).");
+    if (o.contspec_inversion_method == fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_AB_FROM_ITER)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched inverse: iterative method).");
+    const bool seed = o.contspec_inversion_method == fnft_nsev_inverse_csmethod_USE_SEED_POTENTIAL_INSTEAD;
+    int cstype = 0;
+    if (M > 0) {
+        switch (o.contspec_type) {
+        case fnft_nsev_inverse_cstype_REFLECTION_COEFFICIENT:
+            if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT
+                && o.contspec_inversion_method != fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_REFL_COEFF)
+                return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
+            break;
+        case fnft_nsev_inverse_cstype_B_OF_XI:
+            cstype = 1;
+            break;
+        case fnft_nsev_inverse_cstype_B_OF_TAU:
+            cstype = 2;
+            if (M != D) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "M"));
+            if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT)
+                return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
+            break;
+        default:
+            return seam_invalid(__func__, __LINE__, "opts->contspec_type");
+        }
+        if (cstype != 0 && o.oversampling_factor == 0)                // fnft__poly_specfact.c:37-38
+            return inv_subroutine(__func__, __LINE__, FNFT_EC_INVALID_ARGUMENT);
+        // b(xi) with the seed method: the drop-in computes the continuous part and then refuses the combination
+        // (:890-891); here before anything runs
+        if (seed) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
+    }
+    const int ds_mode = (M == 0 && !seed) ? 0 : 1;
+    const int residues = o.discspec_type == fnft_nsev_inverse_dstype_RESIDUES ? 1 : 0;
+    DeviceGuard dg(device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    fnft_amd_inverse_plan *P = new (std::nothrow) fnft_amd_inverse_plan();
+    if (!P) return FNFT_EC_NOMEM;
+    P->device = device;
+    P->cstype = cstype;
+    P->K = K;
+    P->inv = new (std::nothrow) NftInverseBatch<HipBackend>(
+        P->be, (size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
+        o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0, (size_t)K, ds_mode, residues);
+    if (!P->inv) { delete P; return FNFT_EC_NOMEM; }
+    const int rc = P->inv->init();
+    if (rc != NFT_SUCCESS || P->be.failed) {
+        (void)P->be.sync();
+        delete P->inv;
+        delete P;
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = P;
+    return FNFT_SUCCESS;
+}
+
+FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, const void *d_contspec,
+                                               const FNFT_REAL *XI, const void *d_bound_states,
+                                               const void *d_normconsts_or_residues, void *d_q, const FNFT_REAL *T,
+                                               FNFT_INT kappa, void *stream)
+{
+    SEAM_CHECK(!plan, plan);
+    if (!plan->K) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));  // K = 0 plan
+    const size_t M = plan->inv->M;
+    SEAM_CHECK(M > 0 && !d_contspec, contspec);                        // fnft_nsev_inverse_host.c, in its order
+    SEAM_CHECK(M == 0 && d_contspec, M);                               // a contspec with M = 0 fails M < D there
+    SEAM_CHECK(!d_q, q);
+    SEAM_CHECK(T == NULL || !(T[0] < T[1]), T);
+    SEAM_CHECK(kappa != +1 && kappa != -1, kappa);
+    if (kappa != +1)
+        return fnft_amd__raise(FNFT_EC_SANITY_CHECK_FAILED, __func__, __LINE__,
+                               "Sanity check failed (Discrete spectrum is present only in the focussing case(kappa=1).).");
+    SEAM_CHECK(!d_bound_states, bound_states);
+    SEAM_CHECK(!d_normconsts_or_residues, normconsts_or_residues);
+    SEAM_CHECK(M > 0 && XI == NULL && plan->cstype != 2, XI);
+    if (M > 0 && plan->cstype == 2 && T[0] != -T[1])                  // :643-647
+        return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "T"));
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    DeviceGuard dg(plan->device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    NftInverseBatch<HipBackend> &inv = *plan->inv;
+    plan->be.stream = (hipStream_t)stream;
+    plan->last_stream = (hipStream_t)stream;
+    plan->be.failed = false;
+    const size_t D = inv.D;
+    const FNFT_REAL eps_t = (T[1] - T[0]) / (D - 1);
+    const FNFT_REAL pf_rho = -2.0 * (T[1] + eps_t * 0.5) + eps_t;
+    const FNFT_REAL pf_b = -eps_t * D - (T[1] + eps_t * 0.5) - (T[0] - eps_t * 0.5) + eps_t;
+    const int rc = inv.run_discrete((const cplx *)d_contspec, XI, (const cplx *)d_bound_states,
+                                    (const cplx *)d_normconsts_or_residues, (cplx *)d_q, T, eps_t, (int)kappa,
+                                    plan->cstype == 0 ? pf_rho : pf_b);
+    if (plan->be.failed) return FNFT_EC_OTHER;
+    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+}
+
 FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *stream, FNFT_INT *status, int *warnings)
 {
     SEAM_CHECK(!plan, plan);
@@ -953,10 +1070,15 @@ FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *strea
     FNFT_INT first = FNFT_SUCCESS;
     for (size_t b = 0; b < plan->st.size(); b++) {
         const int h = plan->st[b];
-        // the drop-in: fnft__nse_finvscatter fails with FNFT_EC_OTHER (bits 4, 5), returned as a subroutine failure
-        const FNFT_INT s = (h & 48) ? -FNFT_EC_OTHER : FNFT_SUCCESS;
+        // the drop-in, in its order: a bound state with Im <= 0 (bit 6) fails before anything runs; then
+        // fnft__nse_finvscatter with FNFT_EC_OTHER (bits 4, 5) and the discrete part on equal bound states (bit 7),
+        // both returned as subroutine failures
+        FNFT_INT s = FNFT_SUCCESS;
+        if (h & 64) s = FNFT_EC_SANITY_CHECK_FAILED;
+        else if (h & 48) s = -FNFT_EC_OTHER;
+        else if (h & 128) s = -FNFT_EC_SANITY_CHECK_FAILED;
         if (status) status[b] = s;
-        if (warnings) warnings[b] = (h & 8) ? 1 : 0;
+        if (warnings) warnings[b] = ((h & 8) && !(h & 64)) ? 1 : 0;
         if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
     }
     return first;

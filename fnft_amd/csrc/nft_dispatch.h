@@ -153,6 +153,12 @@ struct KInvCdt {
     static constexpr size_t lds_bytes() { return 0; }
     static FA_DEV void body(const Params &p) { body_inv_cdt(p); }
 };
+struct KInvDsPrep {
+    using Params = InvDsPrepParams;
+    static constexpr int THREADS = 64;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_inv_ds_prep(p); }
+};
 struct KAberthNewton {
     using Params = AberthParams;
     static constexpr int THREADS = 256;

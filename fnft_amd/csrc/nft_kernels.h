@@ -2298,6 +2298,10 @@ struct BsParams {
     int with_deriv;
     cplx *best;          // K*nchunk*2: {metric, 0}, b of the best point of the chunk
     cplx *a, *aprime, *b;
+    // batch of signals (the batched inverse transform): chunk, phi and psi kernels grid.y = signal * K + k, combine
+    // kernels grid.x = signal * K + k; per-signal strides (elements) of q, lam, cm, bnd and bndp, PHI and PSI, and
+    // a / aprime.  All 0 for one signal.  The matrix, metric and pick kernels take one signal only.
+    long long sq, slam, scm, sbnd, sphi, sab;
 };
 
 FA_DEV void c_cosh_sinh(cplx w, cplx &ch, cplx &sh)
@@ -2346,9 +2350,12 @@ template <bool WITH_D> FA_DEV void bs_step_r(cplx q, cplx r, cplx l, double e, B
 // chunk matrices.  grid.x = nchunk lanes / THREADS, grid.y = K.  BACKWARD: inverse steps, last sample first
 template <bool BACKWARD> FA_DEV void body_bs_chunk(const BsParams &P)
 {
-    const int c = FA_BID * FA_BDIM + FA_TID, e = FA_BID_Y;
+    const int c = FA_BID * FA_BDIM + FA_TID;
     if (c >= P.nchunk) return;
-    const cplx l = P.lam[e] * P.lscale;
+    const long long sg = FA_BID_Y / P.K;
+    const int e = FA_BID_Y - (int)sg * P.K;
+    const cplx *q = P.q + sg * P.sq;
+    const cplx l = P.lam[sg * P.slam + e] * P.lscale;
     const long long n0 = (long long)c * P.L;
     const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
     cplx m00 = cmake(1.0, 0.0), m01 = cmake(0.0, 0.0), m10 = m01, m11 = m00;
@@ -2356,7 +2363,7 @@ template <bool BACKWARD> FA_DEV void body_bs_chunk(const BsParams &P)
     BsStep U, V;
     if (!BACKWARD) {
         for (long long n = n0; n < n1; n++) {
-            const cplx qn = P.q[n];
+            const cplx qn = q[n];
             const cplx rn = P.r ? P.r[n] : (P.kappa < 0 ? cmake(qn.x, -qn.y) : cmake(-qn.x, qn.y));
             bs_step_r<true>(qn, rn, l, P.eps, U, V);
             // M' <- V M + U M',  M <- U M
@@ -2371,13 +2378,13 @@ template <bool BACKWARD> FA_DEV void body_bs_chunk(const BsParams &P)
         }
     } else {
         for (long long n = n1; n-- > n0;) {
-            bs_step<false>(P.q[n], l, -P.eps, U, V);
+            bs_step<false>(q[n], l, -P.eps, U, V);
             const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
             const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
             m00 = f00; m01 = f01; m10 = f10; m11 = f11;
         }
     }
-    cplx *o = P.cm + ((size_t)e * P.nchunk + c) * 8;
+    cplx *o = P.cm + sg * P.scm + ((size_t)e * P.nchunk + c) * 8;
     o[0] = m00; o[1] = m01; o[2] = m10; o[3] = m11;
     if (!BACKWARD) { o[4] = d00; o[5] = d01; o[6] = d10; o[7] = d11; }
 }
@@ -2393,10 +2400,12 @@ template <bool BACKWARD> FA_DEV void body_bs_combine(const BsParams &P)
     FA_LDS_DECL
     cplx *gm = (cplx *)FA_LDS_PTR;             // lanes x 8: the run's map {M[4], M'[4]}
     cplx *gv = gm + (size_t)FA_BDIM * 8;       // lanes x 4: the run's start vector (p1, p2, d1, d2)
-    const int e = FA_BID, t = FA_TID, nl = FA_BDIM;
-    const cplx lc = P.lam[e];
+    const int t = FA_TID, nl = FA_BDIM;
+    const long long sg = FA_BID / P.K;
+    const int e = FA_BID - (int)sg * P.K;
+    const cplx lc = P.lam[sg * P.slam + e];
     const double bc = 0.5;
-    const cplx *cmv = P.cm + (size_t)e * P.nchunk * 8;
+    const cplx *cmv = P.cm + sg * P.scm + (size_t)e * P.nchunk * 8;
     const int G = (P.nchunk + nl - 1) / nl;
     const int k0 = (t * G < P.nchunk) ? t * G : P.nchunk;
     const int k1 = (k0 + G < P.nchunk) ? k0 + G : P.nchunk;
@@ -2448,11 +2457,11 @@ template <bool BACKWARD> FA_DEV void body_bs_combine(const BsParams &P)
                 const cplx t1 = m[0] * p1 + m[1] * p2, t2 = m[2] * p1 + m[3] * p2;
                 p1 = t1; p2 = t2;
             }
-            cplx *bnd = P.bnd + (size_t)e * (P.nchunk + 1) * 2;
+            cplx *bnd = P.bnd + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
             bnd[2 * P.nchunk] = p1; bnd[2 * P.nchunk + 1] = p2;
             const cplx av = p1 * ph;
-            P.a[e] = av;
-            P.aprime[e] = (d1 * ph + cmake(0.0, tb) * av) * P.lscale;
+            P.a[sg * P.sab + e] = av;
+            P.aprime[sg * P.sab + e] = (d1 * ph + cmake(0.0, tb) * av) * P.lscale;
         } else {
             cplx s1 = zero, s2 = ph;
             for (int g = nl; g-- > 0;) {
@@ -2462,7 +2471,7 @@ template <bool BACKWARD> FA_DEV void body_bs_combine(const BsParams &P)
                 const cplx t1 = m[0] * s1 + m[1] * s2, t2 = m[2] * s1 + m[3] * s2;
                 s1 = t1; s2 = t2;
             }
-            cplx *bnd = P.bndp + (size_t)e * (P.nchunk + 1) * 2;
+            cplx *bnd = P.bndp + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
             bnd[0] = s1; bnd[1] = s2;
         }
     }
@@ -2471,7 +2480,7 @@ template <bool BACKWARD> FA_DEV void body_bs_combine(const BsParams &P)
     const cplx *v = gv + (size_t)t * 4;
     if (!BACKWARD) {
         cplx p1 = v[0], p2 = v[1];
-        cplx *bnd = P.bnd + (size_t)e * (P.nchunk + 1) * 2;
+        cplx *bnd = P.bnd + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
         for (int k = k0; k < k1; k++) {
             bnd[2 * k] = p1; bnd[2 * k + 1] = p2;
             const cplx *m = cmv + (size_t)k * 8;
@@ -2480,7 +2489,7 @@ template <bool BACKWARD> FA_DEV void body_bs_combine(const BsParams &P)
         }
     } else {
         cplx s1 = v[0], s2 = v[1];
-        cplx *bnd = P.bndp + (size_t)e * (P.nchunk + 1) * 2;
+        cplx *bnd = P.bndp + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
         for (int k = k1; k-- > k0;) {
             bnd[2 * (k + 1)] = s1; bnd[2 * (k + 1) + 1] = s2;
             const cplx *m = cmv + (size_t)k * 8;
@@ -2533,19 +2542,22 @@ FA_DEV void body_bs_matrix(const BsParams &P)
 // phi at every grid point of the chunk (grid point g+1 follows sample ups*(g+1)-1)
 FA_DEV void body_bs_phi(const BsParams &P)
 {
-    const int c = FA_BID * FA_BDIM + FA_TID, e = FA_BID_Y;
+    const int c = FA_BID * FA_BDIM + FA_TID;
     if (c >= P.nchunk) return;
-    const cplx l = P.lam[e] * P.lscale;
+    const long long sg = FA_BID_Y / P.K;
+    const int e = FA_BID_Y - (int)sg * P.K;
+    const cplx *q = P.q + sg * P.sq;
+    const cplx l = P.lam[sg * P.slam + e] * P.lscale;
     const long long n0 = (long long)c * P.L;
     const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
     const long long Dg = P.D / P.ups;
-    const cplx *bnd = P.bnd + ((size_t)e * (P.nchunk + 1) + c) * 2;
+    const cplx *bnd = P.bnd + sg * P.sbnd + ((size_t)e * (P.nchunk + 1) + c) * 2;
     cplx p1 = bnd[0], p2 = bnd[1];
-    cplx *PHI = P.PHI + (size_t)e * (Dg + 1) * 2;
+    cplx *PHI = P.PHI + sg * P.sphi + (size_t)e * (Dg + 1) * 2;
     if (c == 0) { PHI[0] = p1; PHI[1] = p2; }
     BsStep U, V;
     for (long long n = n0; n < n1; n++) {
-        bs_step<false>(P.q[n], l, P.eps, U, V);
+        bs_step<false>(q[n], l, P.eps, U, V);
         const cplx t1 = U.u00 * p1 + U.u01 * p2, t2 = U.u10 * p1 + U.u11 * p2;
         p1 = t1; p2 = t2;
         if ((n + 1) % P.ups == 0) {
@@ -2559,19 +2571,22 @@ FA_DEV void body_bs_phi(const BsParams &P)
 // transform's Darboux step, src/fnft_nsev_inverse.c:963-1004); grid point g precedes sample ups*g
 FA_DEV void body_bs_psi(const BsParams &P)
 {
-    const int c = FA_BID * FA_BDIM + FA_TID, e = FA_BID_Y;
+    const int c = FA_BID * FA_BDIM + FA_TID;
     if (c >= P.nchunk) return;
-    const cplx l = P.lam[e] * P.lscale;
+    const long long sg = FA_BID_Y / P.K;
+    const int e = FA_BID_Y - (int)sg * P.K;
+    const cplx *q = P.q + sg * P.sq;
+    const cplx l = P.lam[sg * P.slam + e] * P.lscale;
     const long long n0 = (long long)c * P.L;
     const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
     const long long Dg = P.D / P.ups;
-    const cplx *bnd = P.bndp + ((size_t)e * (P.nchunk + 1) + (c + 1)) * 2;
+    const cplx *bnd = P.bndp + sg * P.sbnd + ((size_t)e * (P.nchunk + 1) + (c + 1)) * 2;
     cplx s1 = bnd[0], s2 = bnd[1];
-    cplx *PSI = P.PSI + (size_t)e * (Dg + 1) * 2;
+    cplx *PSI = P.PSI + sg * P.sphi + (size_t)e * (Dg + 1) * 2;
     if (n1 == P.D) { PSI[2 * Dg] = s1; PSI[2 * Dg + 1] = s2; }
     BsStep U, V;
     for (long long n = n1; n-- > n0;) {
-        bs_step<false>(P.q[n], l, -P.eps, U, V);
+        bs_step<false>(q[n], l, -P.eps, U, V);
         const cplx t1 = U.u00 * s1 + U.u01 * s2, t2 = U.u10 * s1 + U.u11 * s2;
         s1 = t1; s2 = t2;
         if (n % P.ups == 0) {
@@ -2811,10 +2826,11 @@ struct InvOpParams {
     int *status;             // bit 3: ill-posed spectral factorization (a warning)
     double *accum;           // INV_ITER_PHASE: one partial sum per workgroup
     long long i1;            // INV_TM_B: M
-    // batch (grid.y = signal): per-signal strides of a, b, out, out2 (elements) and of the status word (ints); all 0
-    // for one signal.  INV_ITER_PHASE is never batched (its block sums are indexed by FA_BID alone).
+    // batch (grid.y = signal): per-signal strides of a, b, out, out2, bs (elements) and of the status word (ints); all
+    // 0 for one signal.  INV_ITER_PHASE is never batched (its block sums are indexed by FA_BID alone).
     long long sa, sb, sout, sout2;
     int sst;
+    long long sbs;
 };
 FA_DEV void body_inv_op(const InvOpParams &P)
 {
@@ -2826,6 +2842,7 @@ FA_DEV void body_inv_op(const InvOpParams &P)
     const cplx *Pa = P.a + sg * P.sa, *Pb = P.b + sg * P.sb;
     cplx *Pout = P.out + sg * P.sout, *Pout2 = P.out2 + sg * P.sout2;
     int *Pst = P.status + sg * P.sst;
+    const cplx *Pbs = P.bs + sg * P.sbs;
     double mine = 0.0;
     if (act) {
         switch (P.op) {
@@ -2833,7 +2850,7 @@ FA_DEV void body_inv_op(const InvOpParams &P)
             const double xi = P.s0 + (double)i * P.s1;
             cplx c = Pa[i];
             for (int k = 0; k < P.K; k++) {
-                const cplx bk = P.bs[k];
+                const cplx bk = Pbs[k];
                 c = c * c_div(cmake(xi - bk.x, -bk.y), cmake(xi - bk.x, bk.y));
             }
             double sn, cs;
@@ -3285,7 +3302,7 @@ FA_DEV void body_peel_leaf(const PeelLeafParams &P0)
     }
 }
 
-// Discrete part, src/fnft_nsev_inverse.c:680-903.  One lane per sample n.
+// Discrete part, src/fnft_nsev_inverse.c:680-903.  One lane per sample n; grid.y = signal of a batch.
 struct InvDsParams {
     long long D;
     int K;
@@ -3296,6 +3313,8 @@ struct InvDsParams {
     cplx *q;                 // D samples: seed in (CDT), result out
     cplx *work;              // K*D (pure solitons: rho_k) or 2*K*D (CDT: S1, S2)
     const cplx *PHI, *PSI;   // K*D*2 each (CDT)
+    // per-signal strides (elements) of bs and nc, q, work, PHI and PSI; all 0 for one signal
+    long long sbs, sq, swork, sphi;
 };
 // pure multi-soliton, :797-842: q(t) by the recursive Darboux formula in rho_k = b_k exp(2 i lam_k t); samples
 // before the zero crossing use the mirrored recursion (1/b_k, -t) and the conjugate
@@ -3303,13 +3322,15 @@ FA_DEV void body_inv_solitons(const InvDsParams &P)
 {
     const long long n = (long long)FA_BID * FA_BDIM + FA_TID;
     if (n >= P.D) return;
+    const long long s = FA_BID_Y;
+    const cplx *bs = P.bs + s * P.sbs, *nc = P.nc + s * P.sbs;
     const double t = P.T0 + P.eps_t * (double)n;
     const bool right = n >= P.zc;
     const double sg = right ? 1.0 : -1.0;
-    cplx *rho = P.work + n;   // rho_k at work[k*D + n]
+    cplx *rho = P.work + s * P.swork + n;   // rho_k at work[k*D + n]
     for (int k = 0; k < P.K; k++) {
-        const cplx l = P.bs[k];
-        const cplx b = right ? P.nc[k] : c_div(cmake(1.0, 0.0), P.nc[k]);
+        const cplx l = bs[k];
+        const cplx b = right ? nc[k] : c_div(cmake(1.0, 0.0), nc[k]);
         // exp(sg * 2 i l t)
         double sn, cs;
         fa_sincos(sg * 2.0 * l.x * t, &sn, &cs);
@@ -3318,30 +3339,34 @@ FA_DEV void body_inv_solitons(const InvDsParams &P)
     }
     cplx qt = cmake(0.0, 0.0);
     for (int i = 0; i < P.K; i++) {
-        const cplx li = P.bs[i];
+        const cplx li = bs[i];
         const cplx r = rho[(size_t)i * P.D], rc = cconj(r);
         const cplx f = cmake(0.0, 2.0 * li.y) * (1.0 / (1.0 + cnorm2(r)));
         qt = qt + (rc * f) * cmake(0.0, 2.0);
         for (int j = i + 1; j < P.K; j++) {
-            const cplx lj = P.bs[j];
+            const cplx lj = bs[j];
             const cplx rj = rho[(size_t)j * P.D];
             const cplx num = (lj - li) * rj + (rj - r) * f;
             const cplx den = lj - cconj(li) - (cmake(1.0, 0.0) + rc * rj) * f;
             rho[(size_t)j * P.D] = c_div(num, den);
         }
     }
-    P.q[n] = right ? qt : cconj(qt);
+    P.q[s * P.sq + n] = right ? qt : cconj(qt);
 }
 // Darboux steps on top of a seed potential, :864-889, from the eigenfunctions phi, psi of the seed at every sample
 FA_DEV void body_inv_cdt(const InvDsParams &P)
 {
     const long long n = (long long)FA_BID * FA_BDIM + FA_TID;
     if (n >= P.D) return;
-    cplx *S1 = P.work + n, *S2 = P.work + (size_t)P.K * P.D + n;
-    cplx qn = P.q[n];
+    const long long s = FA_BID_Y;
+    const cplx *bs = P.bs + s * P.sbs, *nc = P.nc + s * P.sbs;
+    const cplx *PHI = P.PHI + s * P.sphi, *PSI = P.PSI + s * P.sphi;
+    cplx *S1 = P.work + s * P.swork + n, *S2 = S1 + (size_t)P.K * P.D;
+    cplx *q = P.q + s * P.sq;
+    cplx qn = q[n];
     for (int i = 0; i < P.K; i++) {
-        const cplx li = P.bs[i];
-        const cplx *ph = P.PHI + ((size_t)i * P.D + n) * 2, *ps = P.PSI + ((size_t)i * P.D + n) * 2;
+        const cplx li = bs[i];
+        const cplx *ph = PHI + ((size_t)i * P.D + n) * 2, *ps = PSI + ((size_t)i * P.D + n) * 2;
         cplx p1 = ph[0], p2 = ph[1], s1 = ps[0], s2 = ps[1];
         for (int j = 0; j < i; j++) {
             const cplx a = li - S1[(size_t)j * P.D], b = S2[(size_t)j * P.D], ac = li - cconj(S1[(size_t)j * P.D]);
@@ -3352,7 +3377,7 @@ FA_DEV void body_inv_cdt(const InvDsParams &P)
             s2 = cconj(b) * s1 + ac * s2;
             s1 = t2;
         }
-        const cplx nci = P.nc[i];
+        const cplx nci = nc[i];
         const cplx beta = c_div(p1 - nci * s1, p2 - nci * s2);
         const double ab = cnorm2(beta);
         const double inv = 1.0 / (1.0 + ab);
@@ -3362,7 +3387,81 @@ FA_DEV void body_inv_cdt(const InvDsParams &P)
         S2[(size_t)i * P.D] = s2v;
         qn = qn - cmake(0.0, 2.0) * s2v;
     }
-    P.q[n] = qn;
+    q[n] = qn;
+}
+
+// The host bookkeeping of the discrete part (src/fnft_nsev_inverse.c:680-795) for a batch of signals, one lane per
+// signal.  Stage 0: a bound state with Im <= 0 sets status bit 6 (:150-153 of the driver); copies of the caller's
+// bound states and norming constants / residues are sorted by descending imaginary part with the reference's exchange
+// sort (:742-754); equal neighbours set bit 7 (:756-761); residues become norming constants with a = 1 if `residues`.
+// Stage 1: that conversion with a(lambda_k) of the seed (:771-795).  A slot with bit 6 or 7 set is left alone after.
+struct InvDsPrepParams {
+    long long B;                 // signals
+    int K;
+    int stage;
+    int residues;                // stage 0: convert residues with a = 1
+    const cplx *bs_in, *nc_in;   // stage 0: the caller's arrays (signal s at s*K)
+    cplx *bs, *nc;               // the sorted copies (signal s at s*K)
+    const cplx *acs;             // stage 1: a(lambda_k) of the seed (signal s at s*K)
+    int *status;                 // one word per signal
+};
+// the host's std::complex<double> arithmetic operation for operation (products as (ac - bd, ad + bc); quotients as the
+// compiler runtime's __divdc3 forms them: divisor scaled by 2^-logb(max(|c|, |d|)), numerators over c^2 + d^2, the
+// scaling undone; nothing contracted to an FMA), so that the conversion equals the drop-in's
+FA_DEV cplx c_mul_host(cplx x, cplx y)
+{
+#pragma clang fp contract(off)
+    return cmake(x.x * y.x - x.y * y.y, x.x * y.y + x.y * y.x);
+}
+FA_DEV cplx c_div_host(cplx x, cplx y)
+{
+#pragma clang fp contract(off)
+    const double a = x.x, b = x.y;
+    double c = y.x, d = y.y;
+    int e = 0;
+    const double lw = logb(fmax(fabs(c), fabs(d)));
+    if (__builtin_isfinite(lw)) {
+        e = (int)lw;
+        c = scalbn(c, -e);
+        d = scalbn(d, -e);
+    }
+    const double den = c * c + d * d;
+    return cmake(scalbn((a * c + b * d) / den, -e), scalbn((b * c - a * d) / den, -e));
+}
+FA_DEV void inv_residues_to_normconsts(const cplx *bs, cplx *nc, const cplx *acs, int K)
+{
+    for (int i = 0; i < K; i++) {
+        cplx tmp = acs ? acs[i] : cmake(1.0, 0.0);
+        for (int j = 0; j < K; j++)
+            if (j != i) tmp = c_div_host(c_mul_host(tmp, bs[i] - bs[j]), bs[i] - cconj(bs[j]));
+        nc[i] = c_mul_host(c_div_host(nc[i], cmake(0.0, 2.0 * bs[i].y)), tmp);
+    }
+}
+FA_DEV void body_inv_ds_prep(const InvDsPrepParams &P)
+{
+    const long long s = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (s >= P.B) return;
+    const long long o = s * P.K;
+    cplx *bs = P.bs + o, *nc = P.nc + o;
+    int *st = P.status + s;
+    if (P.stage == 1) {
+        if (!(*st & (64 | 128))) inv_residues_to_normconsts(bs, nc, P.acs + o, P.K);
+        return;
+    }
+    const cplx *bi = P.bs_in + o, *ni = P.nc_in + o;
+    for (int i = 0; i < P.K; i++)
+        if (bi[i].y <= 0.0) { *st |= 64; return; }
+    for (int i = 0; i < P.K; i++) { bs[i] = bi[i]; nc[i] = ni[i]; }
+    for (int i = 0; i < P.K; i++)
+        for (int j = i + 1; j < P.K; j++)
+            if (bs[i].y < bs[j].y) {
+                const cplx tb = bs[i], tn = nc[i];
+                bs[i] = bs[j]; nc[i] = nc[j];
+                bs[j] = tb; nc[j] = tn;
+            }
+    for (int i = 0; i + 1 < P.K; i++)
+        if (bs[i + 1].x == bs[i].x && bs[i + 1].y == bs[i].y) { *st |= 128; return; }
+    if (P.residues) inv_residues_to_normconsts(bs, nc, nullptr, P.K);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -515,32 +515,201 @@ public:
     }
 };
 
+// Batched discrete part of fnft_nsev_inverse (src/fnft_nsev_inverse.c:680-903): K bound states and norming constants
+// (or residues) per signal, for `batch` signals of D samples, one launch per stage for the whole batch.  Per signal the
+// arithmetic is that of the host-pointer driver (fnft_amd__inverse_add_discrete, NftInverseDev::add_discrete): the same
+// kernels, with the host's bookkeeping -- the check Im lambda > 0, the sort, the check for equal neighbours and the
+// conversion of residues -- in KInvDsPrep, one lane per signal.  mode 0: pure solitons (:797-842); 1: Darboux steps on
+// the seed in q (:843-889), which is the plan's continuous part (seed_cs) or the caller's q.  Every array is allocated
+// by init(); signal s of an array of n values per signal starts at s*n.
+template <class BE> class NftInverseDiscBatch {
+public:
+    static constexpr size_t kMaxGridY = 65535;   // grid.y of one launch: larger batches go in slices of whole signals
+    BE &be;
+    const size_t D, B, K;
+    const int mode;
+    const bool residues, seed_cs;
+    size_t L = 0, nchunk = 0, Lr = 0, nchunk_r = 0, ncm = 0, bytes = 0;
+    cplx *bs = nullptr, *nc = nullptr, *work = nullptr;                                  // sorted copies; rho_k or S1, S2
+    cplx *q2 = nullptr, *cm = nullptr, *bnd = nullptr, *bndp = nullptr, *PHI = nullptr, *PSI = nullptr, *aout = nullptr;
+
+    NftInverseDiscBatch(BE &b, size_t D_, size_t B_, size_t K_, int mode_, bool residues_, bool seed_cs_)
+        : be(b), D(D_), B(B_), K(K_), mode(mode_), residues(residues_), seed_cs(seed_cs_) {}
+    ~NftInverseDiscBatch() { destroy(); }
+    void destroy()
+    {
+        for (cplx *p : {bs, nc, work, q2, cm, bnd, bndp, PHI, PSI, aout}) be.free(p);
+        bs = nc = work = q2 = cm = bnd = bndp = PHI = PSI = aout = nullptr;
+    }
+    template <class T> bool alloc(T *&p, size_t count)
+    {
+        const size_t b = count * sizeof(T);
+        p = (T *)be.alloc(b ? b : 16);
+        if (!p) return false;
+        bytes += b;
+        return true;
+    }
+    // chunks of the chunk-parallel scatterer over n samples (NftDiscSpec::scatter, NftInverseDev::add_discrete)
+    static size_t chunk_len(size_t n)
+    {
+        size_t l = (n + 16383) / 16384;
+        if (l < 16) l = 16;
+        if (l % 2) l++;
+        return l;
+    }
+    size_t work_per_signal() const { return (mode ? 2 : 1) * K * D; }
+    int init()
+    {
+        bool ok = alloc(bs, B * K) && alloc(nc, B * K) && alloc(work, B * work_per_signal());
+        if (mode == 1) {
+            const size_t D2 = 2 * (D - 1);
+            L = chunk_len(D2);
+            nchunk = (D2 + L - 1) / L;
+            ncm = nchunk;
+            if (residues && seed_cs) {          // a(lambda_k) of the seed, BO scheme on its D samples
+                Lr = chunk_len(D);
+                nchunk_r = (D + Lr - 1) / Lr;
+                ncm = std::max(ncm, nchunk_r);
+            }
+            ok = ok && alloc(q2, B * D2) && alloc(cm, B * K * ncm * 8) && alloc(bnd, B * K * (ncm + 1) * 2)
+                 && alloc(bndp, B * K * (ncm + 1) * 2) && alloc(PHI, B * K * D * 2) && alloc(PSI, B * K * D * 2)
+                 && alloc(aout, 2 * B * K);
+        }
+        return ok ? NFT_SUCCESS : NFT_EC_NOMEM;
+    }
+    // stage 0 of KInvDsPrep: d_bs, d_nc are the caller's arrays; status: one word per signal
+    void check_and_sort(const cplx *d_bs, const cplx *d_nc, int *status)
+    {
+        InvDsPrepParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.B = (long long)B; P.K = (int)K; P.stage = 0; P.residues = (residues && !seed_cs) ? 1 : 0;
+        P.bs_in = d_bs; P.nc_in = d_nc; P.bs = bs; P.nc = nc; P.status = status;
+        be.template run<KInvDsPrep>((int)((B + 63) / 64), 1, P);
+    }
+    // the scatterer's parameters for signals s0 .. s0 + ns - 1 of the batch (strides: see BsParams)
+    BsParams bs_params(const cplx *q, size_t Dq, size_t s0) const
+    {
+        BsParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.K = (int)K;
+        P.q = q + s0 * Dq; P.lam = bs + s0 * K;
+        P.cm = cm + s0 * K * ncm * 8; P.bnd = bnd + s0 * K * (ncm + 1) * 2; P.bndp = bndp + s0 * K * (ncm + 1) * 2;
+        P.PHI = PHI + s0 * K * D * 2; P.PSI = PSI + s0 * K * D * 2;
+        P.a = aout + s0 * K; P.aprime = aout + B * K + s0 * K;
+        P.sq = (long long)Dq; P.slam = (long long)K; P.scm = (long long)(K * ncm * 8);
+        P.sbnd = (long long)(K * (ncm + 1) * 2); P.sphi = (long long)(K * D * 2); P.sab = (long long)K;
+        return P;
+    }
+    InvDsParams ds_params(cplx *q, double T0, double eps_t, size_t zc, size_t s0) const
+    {
+        InvDsParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.D = (long long)D; P.K = (int)K; P.T0 = T0; P.eps_t = eps_t; P.zc = (long long)zc;
+        P.bs = bs + s0 * K; P.nc = nc + s0 * K; P.q = q + s0 * D; P.work = work + s0 * work_per_signal();
+        if (mode == 1) { P.PHI = PHI + s0 * K * D * 2; P.PSI = PSI + s0 * K * D * 2; }
+        P.sbs = (long long)K; P.sq = (long long)D; P.swork = (long long)work_per_signal();
+        P.sphi = (long long)(K * D * 2);
+        return P;
+    }
+    // d_q: the seed on entry (mode 1), the signals on exit; T: host, shared by the batch.  check_and_sort() has run.
+    void run(cplx *d_q, const double *T, int *status)
+    {
+        const double eps_t = (T[1] - T[0]) / (double)(D - 1);
+        size_t zc = 0;                                    // :726-733: first sample with t >= 0 (0 if none)
+        for (size_t i = 0; i < D; i++)
+            if (T[0] + eps_t * (double)i >= 0.0) { zc = i; break; }
+        const size_t per_y = kMaxGridY / K;               // signals per slice of a launch with grid.y = signal*K + k
+        if (residues && seed_cs) {
+            // :771-795 with a continuous part: a(lambda_k) of the seed by the slow scatterer, BO scheme
+            // (NftDiscSpec::prepare(2SPLIT4B, need_tree = false) and scatter(skip_b = true) on the drop-in's path)
+            const double eps_in = (T[1] - T[0]) / (double)(D - 1);
+            const double T1 = T[0] + (double)(D - 1) * eps_in;
+            for (size_t s0 = 0; s0 < B; s0 += per_y) {
+                const size_t ns = std::min(per_y, B - s0);
+                BsParams P = bs_params(d_q, D, s0);
+                P.D = (long long)D; P.ups = 1; P.lscale = 1.0;
+                P.T0 = T[0]; P.T1 = T1; P.eps = (T1 - T[0]) / (double)(D - 1);
+                P.L = (int)Lr; P.nchunk = (int)nchunk_r;
+                const int gx = (int)((nchunk_r + 63) / 64);
+                be.template run<KBsChunk<false>>(gx, (int)(ns * K), P);
+                be.template run<KBsCombine<false>>((int)(ns * K), 1, P);
+            }
+            InvDsPrepParams R;
+            std::memset(&R, 0, sizeof(R));
+            R.B = (long long)B; R.K = (int)K; R.stage = 1; R.bs = bs; R.nc = nc; R.acs = aout; R.status = status;
+            be.template run<KInvDsPrep>((int)((B + 63) / 64), 1, R);
+        }
+        const int gx = (int)((D + 255) / 256);
+        if (mode == 0) {
+            for (size_t s0 = 0; s0 < B; s0 += kMaxGridY)
+                be.template run<KInvSolitons>(gx, (int)std::min(kMaxGridY, B - s0), ds_params(d_q, T[0], eps_t, zc, s0));
+            return;
+        }
+        // eigenfunctions of the seed, :908-1007 (NftInverseDev::add_discrete): the chunk-parallel scatterer on the
+        // half-step signal q' = (q0, q1, q1, q2, q2, ...) with step eps_t/2
+        const size_t D2 = 2 * (D - 1);
+        for (size_t s0 = 0; s0 < B; s0 += kMaxGridY) {
+            InvOpParams O;
+            std::memset(&O, 0, sizeof(O));
+            O.op = INV_DOUBLE_Q; O.n = (long long)D2; O.a = d_q + s0 * D; O.out = q2 + s0 * D2;
+            O.sa = (long long)D; O.sout = (long long)D2;
+            be.template run<KInvOp>((int)((D2 + 255) / 256), (int)std::min(kMaxGridY, B - s0), O);
+        }
+        for (size_t s0 = 0; s0 < B; s0 += per_y) {
+            const size_t ns = std::min(per_y, B - s0);
+            BsParams P = bs_params(q2, D2, s0);
+            P.D = (long long)D2; P.ups = 2; P.lscale = 1.0;
+            P.eps = 0.5 * eps_t;
+            P.T0 = T[0] + 0.5 * P.eps;                 // the combine kernels start at T0 - eps/2 and end at T1 + eps/2
+            P.T1 = T[1] - 0.5 * P.eps;
+            P.L = (int)L; P.nchunk = (int)nchunk;
+            const int gxc = (int)((nchunk + 63) / 64), gy = (int)(ns * K);
+            be.template run<KBsChunk<false>>(gxc, gy, P);
+            be.template run<KBsCombine<false>>(gy, 1, P);
+            be.template run<KBsPhi>(gxc, gy, P);
+            be.template run<KBsChunk<true>>(gxc, gy, P);
+            be.template run<KBsCombine<true>>(gy, 1, P);
+            be.template run<KBsPsi>(gxc, gy, P);
+        }
+        for (size_t s0 = 0; s0 < B; s0 += kMaxGridY)
+            be.template run<KInvCdt>(gx, (int)std::min(kMaxGridY, B - s0), ds_params(d_q, T[0], eps_t, zc, s0));
+    }
+};
+
 // Batched, device-resident continuous part of fnft_nsev_inverse (K = 0): `batch` signals of one size and one set of
 // options per call, every launch covering the whole batch, nothing copied to or from the host and no allocation while
 // a call runs.  Per signal the arithmetic is that of the host-pointer driver above (NftInverseDev::transfer_matrix,
 // then NftLayerPeelingDev::run_host): the same kernels, with the transfer matrix formed on the device (INV_TM_B /
 // INV_TM_AB) instead of on the host.  Every array holds the signals back to back.
+// K > 0: a discrete stage (NftInverseDiscBatch) follows; M = 0 then means no continuous part at all.
 template <class BE> class NftInverseBatch {
 public:
     BE &be;
     const size_t D, M, B;
     const int cstype;            // 0 rho, 1 b(xi), 2 B(tau)
     const size_t os;             // oversampling factor of the spectral factorization
+    const size_t K;              // bound states per signal
+    const int ds_mode, ds_residues;
     NftPlan<BE> pl;              // twiddle tables only
     NftLayerPeelingDev<BE> lp;
+    NftInverseDiscBatch<BE> *ds = nullptr;
     size_t Mf = 0, Lcap = 0, bytes = 0;
     cplx *dY = nullptr, *dV = nullptr, *dc = nullptr, *dr = nullptr, *db = nullptr, *da = nullptr, *dtm = nullptr;
     cplx *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
     int *dchirp = nullptr;       // status word of the DFTs (DFT mode sets no bit)
 
-    NftInverseBatch(BE &b, size_t D_, size_t M_, size_t B_, int cstype_, size_t os_, int modal)
-        : be(b), D(D_), M(M_), B(B_), cstype(cstype_), os(os_), pl(b, 2, 0, 1, 0, 1), lp(b, 1.0, 1, modal)
+    NftInverseBatch(BE &b, size_t D_, size_t M_, size_t B_, int cstype_, size_t os_, int modal, size_t K_ = 0,
+                    int ds_mode_ = 0, int ds_residues_ = 0)
+        : be(b), D(D_), M(M_), B(B_), cstype(cstype_), os(os_), K(K_), ds_mode(ds_mode_), ds_residues(ds_residues_),
+          pl(b, 2, 0, 1, 0, 1), lp(b, 1.0, 1, modal)
     {
         lp.batch = B;
     }
     ~NftInverseBatch() { destroy(); }
     void destroy()
     {
+        delete ds;
+        ds = nullptr;
         lp.destroy();
         for (cplx *p : {dY, dV, dc, dr, db, da, dtm, w0, w1, w2}) be.free(p);
         be.free(dchirp);
@@ -550,6 +719,25 @@ public:
         pl.twtab = nullptr; pl.twlo = nullptr;
     }
     int init()
+    {
+        if (M > 0) {
+            const int r = init_continuous();
+            if (r != NFT_SUCCESS) return r;
+        } else {
+            const int r = lp.init(0);                 // the status words only
+            if (r != NFT_SUCCESS) return r;
+            bytes = lp.status_words() * sizeof(int);
+        }
+        if (K > 0) {
+            ds = new (std::nothrow) NftInverseDiscBatch<BE>(be, D, B, K, ds_mode, ds_residues != 0, M > 0);
+            if (!ds) return NFT_EC_NOMEM;
+            const int r = ds->init();
+            if (r != NFT_SUCCESS) return r;
+            bytes += ds->bytes;
+        }
+        return be.sync();
+    }
+    int init_continuous()
     {
         const size_t deg = D;
         if (cstype != 0) Mf = NftInverseDev<BE>::specfact_len(cstype == 1 ? deg : D - 1, os);
@@ -570,7 +758,7 @@ public:
         for (size_t d = deg; d > NftLayerPeelingDev<BE>::kLeaf; d /= 2)
             bytes += B * 4 * ((d + 1) + (2 * d + 1) + (d / 2 + 1)) * sizeof(cplx);
         for (auto &kv : lp.plans) bytes += kv.second->bytes;
-        return be.sync();
+        return NFT_SUCCESS;
     }
     // out[s*n + k] = sum_j in[s*n + j] exp(sign 2 pi i j k / n) for every signal s (NftInverseDev::dft, batched)
     int dft(const cplx *d_in, cplx *d_out, size_t n, int sign)
@@ -595,13 +783,14 @@ public:
     // body_inv_op over n elements of every signal; sa, sb, so: distances between the signals of a, b, out
     void op(int code, size_t n, const cplx *a, size_t sa, const cplx *b, size_t sb, cplx *out, size_t so,
             cplx *out2 = nullptr, size_t so2 = 0, double s0 = 0, double s1 = 0, double s2 = 0, long long i0 = 0,
-            int kappa = 0, long long i1 = 0)
+            int kappa = 0, long long i1 = 0, const cplx *bs = nullptr)
     {
         InvOpParams P;
         std::memset(&P, 0, sizeof(P));
         P.op = code; P.n = (long long)n; P.a = a; P.b = b; P.out = out; P.out2 = out2;
         P.s0 = s0; P.s1 = s1; P.s2 = s2; P.i0 = i0; P.i1 = i1; P.kappa = kappa;
         P.sa = (long long)sa; P.sb = (long long)sb; P.sout = (long long)so; P.sout2 = (long long)so2;
+        if (bs) { P.K = (int)K; P.bs = bs; P.sbs = (long long)K; }   // INV_PREP: Blaschke factors
         P.status = lp.d_status; P.sst = 1;
         be.template run<KInvOp>((int)((n + 255) / 256), (int)B, P);
     }
@@ -627,15 +816,39 @@ public:
     // them.  Enqueued on be.stream; the per-signal status words are read by the caller after the stream is done.
     int run(const cplx *d_cs, const double *XI, cplx *d_q, double eps_t, int kappa, double pf)
     {
-        const size_t deg = D, per = 4 * (deg + 1);
+        reset(eps_t, kappa);
+        return continuous(d_cs, XI, d_q, eps_t, kappa, pf, nullptr);
+    }
+    // K > 0: d_bs, d_nc: batch*K bound states and norming constants / residues (the caller's, read only); d_cs and XI
+    // unused if M = 0; d_q: the seed on entry if the plan has no continuous part and mode 1; T: host
+    int run_discrete(const cplx *d_cs, const double *XI, const cplx *d_bs, const cplx *d_nc, cplx *d_q, const double *T,
+                     double eps_t, int kappa, double pf)
+    {
+        reset(eps_t, kappa);
+        ds->check_and_sort(d_bs, d_nc, lp.d_status);
+        if (M > 0) {
+            // the Blaschke factors of the reflection coefficient take the bound states in the caller's order, as the
+            // drop-in uploads them (:1013-1033); the Darboux steps the sorted ones
+            const int rc = continuous(d_cs, XI, d_q, eps_t, kappa, pf, cstype == 0 ? d_bs : nullptr);
+            if (rc != NFT_SUCCESS) return rc;
+        }
+        ds->run(d_q, T, lp.d_status);
+        return NFT_SUCCESS;
+    }
+    void reset(double eps_t, int kappa)
+    {
         lp.rc = NFT_SUCCESS;
         lp.eps_t = eps_t;
         lp.kappa = kappa;
         be.memset0(lp.d_status, lp.status_words() * sizeof(int));
+    }
+    int continuous(const cplx *d_cs, const double *XI, cplx *d_q, double eps_t, int kappa, double pf, const cplx *d_bs)
+    {
+        const size_t deg = D, per = 4 * (deg + 1);
         int rc = NFT_SUCCESS;
         if (cstype != 2) {
             const double eps_xi = (XI[1] - XI[0]) / (double)(M - 1);
-            op(INV_PREP, M, d_cs, M, nullptr, 0, dc, M, dr, M, XI[0], eps_xi, pf);
+            op(INV_PREP, M, d_cs, M, nullptr, 0, dc, M, dr, M, XI[0], eps_xi, pf, 0, 0, 0, d_bs);
             rc = dft(dr, db, M, -1);                                                  // B(z), :340 / :594
             if (rc != NFT_SUCCESS) return rc;
             const long long i0 = (deg <= M - 1) ? 0 : (long long)(deg - (M - 1));
@@ -655,7 +868,8 @@ public:
         lp.peel(deg, dtm, deg + 1, per, nullptr, 0, 0, d_q, D);
         return lp.rc;
     }
-    // after the stream is done: status word of every signal (bit 3 ill-posed factorization, bits 4, 5 the leaf's)
+    // after the stream is done: status word of every signal (bit 3 ill-posed factorization, bits 4, 5 the leaf's;
+    // K > 0: bit 6 a bound state with Im <= 0, bit 7 equal bound states)
     int read_status(std::vector<int> &st)
     {
         st.assign(B, 0);

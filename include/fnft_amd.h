@@ -483,6 +483,30 @@ FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void 
  * every signal succeeded, else the status of the lowest-index failing signal. */
 FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *stream, FNFT_INT *status, int *warnings);
 
+/* Batched fnft_nsev_inverse with a discrete spectrum (K >= 1 bound states and norming constants or residues per
+ * signal, opts->discspec_type): a pure multi-soliton (M = 0), Darboux steps on the caller's seed in d_q (M = 0 and
+ * USE_SEED_POTENTIAL_INSTEAD) or on the continuous part the plan computes first (M > 0, the options of
+ * fnft_amd_inverse_plan_create).  Every signal's arithmetic is that of fnft_nsev_inverse on it alone; residues are
+ * converted to norming constants on the device with the host's operation order.  Size and option errors return
+ * fnft_nsev_inverse's codes in its order at create time, before any HIP call (USE_SEED_POTENTIAL_INSTEAD with M > 0:
+ * -FNFT_EC_INVALID_ARGUMENT; K = 0 with M = 0: FNFT_EC_SANITY_CHECK_FAILED, with M > 0: FNFT_EC_INVALID_ARGUMENT, use
+ * fnft_amd_inverse_plan_create); TFMATRIX_CONTAINS_AB_FROM_ITER returns FNFT_EC_NOT_YET_IMPLEMENTED, and so does
+ * K > 65535.  fnft_amd_inverse_plan_destroy, _workspace_bytes and _finish serve these plans too; status[b] adds the
+ * drop-in's codes of the discrete part (a bound state with Im <= 0: FNFT_EC_SANITY_CHECK_FAILED; equal bound states:
+ * -FNFT_EC_SANITY_CHECK_FAILED), a slot that fails leaves the others unchanged and its own q unspecified.
+ * fnft_amd_nsev_inverse_device on such a plan, and the call below on a plan of fnft_amd_inverse_plan_create, return
+ * -FNFT_EC_INVALID_ARGUMENT. */
+FNFT_INT fnft_amd_inverse_plan_create_discrete(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT K,
+                                               FNFT_UINT batch, fnft_nsev_inverse_opts_t const *opts, int device);
+/* d_contspec: batch*M complex128 (device), NULL exactly when M = 0; d_bound_states, d_normconsts_or_residues:
+ * batch*K complex128 (device; signal b at +b*K), NOT modified -- the bound states need not be sorted; d_q: batch*D
+ * complex128 (device), the seed on entry with USE_SEED_POTENTIAL_INSTEAD, the signals on exit.  XI, T: host.  kappa
+ * must be +1 (FNFT_EC_SANITY_CHECK_FAILED otherwise, before anything is enqueued).  Asynchronous on `stream`. */
+FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, const void *d_contspec,
+                                               const FNFT_REAL *XI, const void *d_bound_states,
+                                               const void *d_normconsts_or_residues, void *d_q, const FNFT_REAL *T,
+                                               FNFT_INT kappa, void *stream);
+
 /* ======================================================================================== */
 /* 4. Korteweg-de Vries equation, vanishing boundaries (include/fnft_kdvv.h)                  */
 /* ======================================================================================== */
