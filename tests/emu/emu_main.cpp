@@ -257,4 +257,77 @@ int emu_tree_schedule(int entry, size_t D, int disc, size_t batch, int real, cha
     return rc;
 }
 
+// Schedule of the chirp z-transform entry points without executing them (schedule-only mode, as emu_tree_schedule):
+// the names of every kernel launched, '\n'-separated, into out[cap].  Returns the entry's rc, or -1 if out is too small.
+//   entry 0: fnft__poly_chirpz, a polynomial of degree n, M outputs (chirpz_host)
+//   entry 1: fnft__misc_resample, n samples (resample_host)
+//   entry 2: fnft_amd_plan / fnft_nsev, n samples per signal, `batch` signals, nse discretization `disc`, M points,
+//            contspec type `cstype` (run_front, run_tree, run_contspec)
+//   entry 3: fnft_amd_nsev_contspec_from_tm_device on a plan of n samples (run_contspec_tm)
+//   entry 4: fnft_amd_kdvv_contspec_device, kdv discretization `disc`; real != 0: the real-coefficient tree
+//            (run_front, run_tree, run_contspec_kdv)
+int emu_chirp_schedule(int entry, size_t n, size_t M, int disc, size_t batch, int cstype, int real, char *out,
+                       size_t cap)
+{
+    EmuBackend be;
+    using P = NftPlan<EmuBackend>;
+    std::vector<std::string> names;
+    emu_schedule = &names;
+    int rc = NFT_EC_INVALID_ARGUMENT;
+    const double T[2] = {-1.0, 1.0}, XI[2] = {-0.5, 0.7};
+    // any non-null address: the kernels that would read or write it are not executed (calloc maps lazily)
+    cplx *dummy = (cplx *)be.alloc(16);
+    if (entry == 0 && M > 0) {
+        std::complex<double> *p = (std::complex<double> *)std::calloc(n + 1, sizeof(cplx));
+        rc = p ? P::chirpz_host(be, n, p, {1.0, 0.0}, {std::cos(1e-3), std::sin(1e-3)}, M, nullptr, dummy)
+               : NFT_EC_NOMEM;
+        std::free(p);
+    } else if (entry == 1 && n > 2) {
+        std::complex<double> *q = (std::complex<double> *)std::calloc(2 * n, sizeof(cplx));
+        rc = q ? P::resample_host(be, n, 0.1, q, 0.03, q + n) : NFT_EC_NOMEM;
+        std::free(q);
+    } else if ((entry == 2 || entry == 3) && n > 1 && M > 0 && batch > 0) {
+        const int akns = nft_nse_to_akns(disc);
+        const int ups = nft_nse_upsampling(disc);
+        if (akns >= 0) {
+            const size_t Dtree = (ups == 1) ? n : 2 * P::sub_count(n, 1);
+            P pl(be, Dtree, M, batch, akns, nft_akns_degree(akns));
+            pl.set_front(n, 1, ups);
+            rc = pl.init();
+            double Tsub[2];
+            P::Contspec cs;
+            cs.XI[0] = XI[0]; cs.XI[1] = XI[1];
+            cs.nse_disc = disc; cs.cstype = cstype; cs.normalization_flag = 1;
+            if (entry == 2) {
+                if (rc == NFT_SUCCESS) rc = pl.run_front(dummy, T, 1, Tsub);
+                if (rc == NFT_SUCCESS) rc = pl.run_tree();
+                cs.T[0] = Tsub[0]; cs.T[1] = Tsub[1];
+                if (rc == NFT_SUCCESS) rc = pl.run_contspec(dummy, cs);
+            } else {
+                cs.T[0] = T[0]; cs.T[1] = T[1];
+                if (rc == NFT_SUCCESS) rc = pl.run_contspec_tm(dummy, cs, dummy, 3);
+            }
+            pl.destroy();
+        }
+    } else if (entry == 4 && n > 1 && M > 0 && batch > 0 && disc >= 0) {
+        const int akns = disc + 1;
+        P pl(be, n, M, batch, akns, nft_akns_degree(akns));
+        pl.kdv = true;
+        pl.want_real = real != 0;
+        rc = pl.init();
+        double Tsub[2];
+        if (rc == NFT_SUCCESS) rc = pl.run_front(dummy, T, 1, Tsub);
+        if (rc == NFT_SUCCESS) rc = pl.run_tree();
+        if (rc == NFT_SUCCESS) rc = pl.run_contspec_kdv(dummy, T, XI, disc == 2);
+        pl.destroy();
+    }
+    be.free(dummy);
+    emu_schedule = nullptr;
+    std::string s;
+    for (const auto &nm : names) s += nm + "\n";
+    if (s.size() + 1 > cap) return -1;
+    std::memcpy(out, s.c_str(), s.size() + 1);
+    return rc;
+}
+
 }  // extern "C"
