@@ -126,6 +126,43 @@ FA_DEV void fa_stagger(int n, bool late)
     if (late)
         for (int k = 0; k < n; k++) __builtin_amdgcn_s_sleep(16);
 }
+// 16-byte elements of a region at a workgroup-uniform base, addressed as a 32-bit per-lane byte offset plus a 32-bit
+// workgroup-uniform one (raw buffer access: the base and its size are a descriptor in scalar registers, the uniform
+// offset goes into soffset, so a whole row of loads or stores shares one VGPR of address); bytes: the region's size
+// (the descriptor's range; every access of the callers lies inside it)
+struct FaRegion {
+    __amdgpu_buffer_rsrc_t r;
+};
+FA_DEV FaRegion fa_region(const void *base, unsigned bytes)
+{
+    return FaRegion{__builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)bytes, 0x00020000)};
+}
+template <class T> FA_DEV T fa_load16(FaRegion g, unsigned lane_bytes, unsigned uniform_bytes)
+{
+    static_assert(sizeof(T) == 16, "fa_load16: 16-byte elements");
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(g.r, lane_bytes, uniform_bytes, 0);
+    T x;
+    __builtin_memcpy(&x, &w, 16);
+    return x;
+}
+template <class T> FA_DEV void fa_store16(FaRegion g, unsigned lane_bytes, unsigned uniform_bytes, const T &x)
+{
+    static_assert(sizeof(T) == 16, "fa_store16: 16-byte elements");
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 w;
+    __builtin_memcpy(&w, &x, 16);
+    __builtin_amdgcn_raw_buffer_store_b128(w, g.r, lane_bytes, uniform_bytes, 0);
+}
+// a copy of x, 0 <= x < BOUND, the compiler cannot see through (no instruction): what is derived from it is computed
+// again after this point instead of being kept in registers from an identical computation before it; the range is
+// restated so that index arithmetic on it keeps its 24-bit multiplies
+template <int BOUND> FA_DEV int fa_opaque(int x)
+{
+    asm volatile("" : "+v"(x));
+    __builtin_assume(x >= 0 && x < BOUND);
+    return x;
+}
 // value known to be the same in every lane of the wave: move it to scalar registers
 FA_DEV double fa_uniform(double x)
 {
@@ -198,6 +235,27 @@ FA_DEV double fa_shfl_down1(double v) { return v; }
 FA_DEV double fa_shfl_down1_z(double v) { return v; }
 FA_DEV float fa_rcp_approx_f32(float x) { return 1.0f / x; }
 FA_DEV void fa_sincos(double x, double *s, double *c) { ::sincos(x, s, c); }
+struct FaRegion {
+    unsigned char *base;
+    unsigned bytes;
+};
+FA_DEV FaRegion fa_region(const void *base, unsigned bytes) { return FaRegion{(unsigned char *)const_cast<void *>(base), bytes}; }
+template <class T> FA_DEV T fa_load16(FaRegion g, unsigned lane_bytes, unsigned uniform_bytes)
+{
+    static_assert(sizeof(T) == 16, "fa_load16: 16-byte elements");
+    T x;
+    const size_t o = (size_t)lane_bytes + uniform_bytes;
+    if (o + 16 <= g.bytes) __builtin_memcpy(&x, g.base + o, 16);
+    else __builtin_memset(&x, 0, 16);
+    return x;
+}
+template <class T> FA_DEV void fa_store16(FaRegion g, unsigned lane_bytes, unsigned uniform_bytes, const T &x)
+{
+    static_assert(sizeof(T) == 16, "fa_store16: 16-byte elements");
+    const size_t o = (size_t)lane_bytes + uniform_bytes;
+    if (o + 16 <= g.bytes) __builtin_memcpy(g.base + o, &x, 16);
+}
+template <int BOUND> FA_DEV int fa_opaque(int x) { return x; }
 FA_DEV double fa_uniform(double x) { return x; }
 FA_DEV void fa_stagger(int, bool) {}
 using std::exp;

@@ -369,8 +369,15 @@ template <int N, int R, int B, int SIGN, int NCUR, int S, bool TWC> struct Fft2P
     }
     static FA_DEV void read(cplx (&x)[R], const cplx *buf, int v, int c)
     {
+        if constexpr ((N / R) % 64 == 0) {
+            // lds_swz only mixes the low six bits: one lane address, the R reads at constant offsets from it
+            const cplx *b0 = buf + (size_t)lds_swz<N>(v) * B + c;
 #pragma unroll
-        for (int i = 0; i < R; i++) x[i] = buf[(size_t)lds_swz<N>(v + (N / R) * i) * B + c];
+            for (int i = 0; i < R; i++) x[i] = b0[(size_t)((N / R) * i) * B];
+        } else {
+#pragma unroll
+            for (int i = 0; i < R; i++) x[i] = buf[(size_t)lds_swz<N>(v + (N / R) * i) * B + c];
+        }
     }
 
     // entered with X's pass-p inputs in registers, Y's pass-p inputs READ ISSUED (or, for the first
@@ -418,6 +425,9 @@ FA_DEV void fft_wg2(cplx (&x)[R], cplx (&y)[R], cplx *lds, int v, int c, const c
 {
     static_assert(N >= R, "fft_wg2: N must be at least R");
     using P0 = Fft2Pass<N, R, B, SIGN, N, 1, TWC>;
+    // the LDS addresses of the passes are formed again in every call: the compiler would otherwise keep the ones
+    // of the first call in registers (two dozen VGPRs) for the calls that follow
+    v = fa_opaque<N / R>(v);
     const TwSet8 t0 = P0::load_tw(v, tw);
     P0::run(x, y, lds, lds + (size_t)N * B, v, c, tw, hook, 0, t0);
 }

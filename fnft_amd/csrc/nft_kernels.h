@@ -1385,6 +1385,12 @@ FA_HD size_t yz_index(int rows, int N2, int row, int n2)
     return (size_t)row * (size_t)N2 + (size_t)n2;
 #endif
 }
+// Row accesses of the row kernels split into a per-lane and a workgroup-uniform part: for n2 = v + u with u a
+// multiple of the tile,  yz_index(rows, N2, row, v + u) = yz_index(rows, N2, 0, v) + yz_index(rows, N2, row, u).
+// Both parts as byte offsets (fa_load16 / fa_store16: the lane part in one VGPR, the uniform part in an SGPR); a
+// block of a split level holds N1*N2 <= kMaxSplitTree = 2^24 elements, so its byte offsets fit in 32 bits.
+FA_HD unsigned yz_lane_bytes(int rows, int N2, int v) { return 16u * (unsigned)yz_index(rows, N2, 0, v); }
+FA_HD unsigned yz_row_bytes(int rows, int N2, int row, int u) { return 16u * (unsigned)yz_index(rows, N2, row, u); }
 
 // column step of the forward transform of every input polynomial of the level
 //   grid.x = N2/BC tiles, grid.y = 4*n_in polynomials
@@ -1442,8 +1448,9 @@ FA_DEV unsigned row_tw_index(const BigLevel &G, int k1, int x)
 #define FA_MID_BSTEP 2
 #endif
 template <int N2, int R> struct MidBLoader {
-    const cplx *p0, *p1;
-    int rows, row, v;
+    FaRegion p0, p1;
+    int rows, row;
+    unsigned lane;   // yz_lane_bytes(rows, N2, v)
     cplx (&b11)[R];
     cplx (&b21)[R];
     FA_DEV void operator()(int k) const
@@ -1451,9 +1458,9 @@ template <int N2, int R> struct MidBLoader {
 #pragma unroll
         for (int i = 0; i < R; i++)
             if (i / FA_MID_BSTEP == k) {
-                const size_t o = yz_index(rows, N2, row, v + (N2 / R) * i);
-                b11[i] = p0[o];
-                b21[i] = p1[o];
+                const unsigned u = yz_row_bytes(rows, N2, row, (N2 / R) * i);
+                b11[i] = fa_load16<cplx>(p0, lane, u);
+                b21[i] = fa_load16<cplx>(p1, lane, u);
             }
     }
 };
@@ -1486,8 +1493,17 @@ template <int N2, int R, bool DIRECT> FA_DEV void body_mid_sym(const BigLevel &G
         k1 = FA_BID % G.N1;
     }
     const long long mA = 2 * P, mB = 2 * P + 1;
+    static_assert(FA_YZ_TILE == 0 || (N2 / R) % FA_YZ_TILE == 0, "row accesses: N2/R must be a multiple of the tile");
     cplx a11[R], a21[R], b11[R], b21[R];
-    MidBLoader<N2, R> bld{nullptr, nullptr, 0, 0, 0, b11, b21};
+    // rows of the four input polynomials in the Y / Z scratch (not DIRECT)
+    const bool split = G.y_split != 0;
+    const int rows = split ? G.N1 / 2 : G.N1;
+    const int row = split ? (k1 >> 1) : k1;
+    const cplx *base = split ? ((k1 & 1) ? G.Y : G.Zprev) : G.Y;
+    const size_t blk = (size_t)rows * N2;
+    const unsigned lane = yz_lane_bytes(rows, N2, v);
+    MidBLoader<N2, R> bld{fa_region(base + (size_t)mB * blk, 16u * (unsigned)blk),
+                          fa_region(base + ((size_t)n_in + mB) * blk, 16u * (unsigned)blk), rows, row, lane, b11, b21};
     // One level is one round of resident workgroups (two per CU), which all start together and then
     // sit in the same phase -- everybody loading (HBM saturated, vector units idle), then everybody
     // transforming (vector units saturated, HBM idle).  Holding back the second half of the grid -- the
@@ -1497,49 +1513,49 @@ template <int N2, int R, bool DIRECT> FA_DEV void body_mid_sym(const BigLevel &G
     // ---- loads ------------------------------------------------------------------------------------
     if constexpr (DIRECT) {
         const size_t d = (size_t)L.d;
-        const cplx *pA0 = L.body_in + (size_t)mA * d, *pA1 = L.body_in + L.plane + (size_t)mA * d;
-        const cplx *pB0 = L.body_in + (size_t)mB * d, *pB1 = L.body_in + L.plane + (size_t)mB * d;
+        const unsigned db = 16u * (unsigned)d;
+        const FaRegion pA0 = fa_region(L.body_in + (size_t)mA * d, db), pA1 = fa_region(L.body_in + L.plane + (size_t)mA * d, db);
+        const FaRegion pB0 = fa_region(L.body_in + (size_t)mB * d, db), pB1 = fa_region(L.body_in + L.plane + (size_t)mB * d, db);
         cplx h0[R], h1[R];
+        const unsigned lv = 16u * (unsigned)v;
+        constexpr unsigned kI = 16u * (N2 / R), kH = 16u * N2;   // bytes: element i of the lane, second half of the row
 #pragma unroll
-        for (int i = 0; i < R; i++) { a11[i] = pA0[v + (N2 / R) * i]; a21[i] = pA1[v + (N2 / R) * i]; }
+        for (int i = 0; i < R; i++) { a11[i] = fa_load16<cplx>(pA0, lv, kI * i); a21[i] = fa_load16<cplx>(pA1, lv, kI * i); }
 #pragma unroll
-        for (int i = 0; i < R; i++) { h0[i] = pA0[N2 + v + (N2 / R) * i]; h1[i] = pA1[N2 + v + (N2 / R) * i]; }
+        for (int i = 0; i < R; i++) { h0[i] = fa_load16<cplx>(pA0, lv, kH + kI * i); h1[i] = fa_load16<cplx>(pA1, lv, kH + kI * i); }
 #pragma unroll
-        for (int i = 0; i < R; i++) { b11[i] = pB0[v + (N2 / R) * i]; b21[i] = pB1[v + (N2 / R) * i]; }
+        for (int i = 0; i < R; i++) { b11[i] = fa_load16<cplx>(pB0, lv, kI * i); b21[i] = fa_load16<cplx>(pB1, lv, kI * i); }
         const cplx tA0 = L.tail_in[mA], tA1 = L.tail_in[(size_t)n_in + mA];
-        const cplx tB0 = L.tail_in[mB], tB1 = L.tail_in[(size_t)n_in + mB];
         const int kq = k1 & 3;
-        auto rot = [kq](cplx z) -> cplx {   // z * (-i)^k1
-            return kq == 0 ? z : (kq == 1 ? cmake(z.y, -z.x) : (kq == 2 ? cmake(-z.x, -z.y) : cmake(-z.y, z.x)));
+        // z * (-i)^k1: parts swapped for odd k1, then negated (selects on workgroup-uniform flags, no branches)
+        const bool swp = (kq & 1) != 0, negx = kq >= 2, negy = kq == 1 || kq == 2;
+        auto rot = [swp, negx, negy](cplx z) -> cplx {
+            const double x = swp ? z.y : z.x, y = swp ? z.x : z.y;
+            return cmake(negx ? -x : x, negy ? -y : y);
         };
         const double sg = (k1 & 1) ? -1.0 : 1.0;
+        // each half is folded as soon as its loads have landed (n2 = 0 is element 0 of lane 0), so that the
+        // second halves of B and B's constant terms are requested only into registers that A has given up
 #pragma unroll
         for (int i = 0; i < R; i++) { a11[i] = a11[i] + rot(h0[i]); a21[i] = a21[i] + rot(h1[i]); }
+        if (v == 0) { a11[0] = a11[0] + tA0 * sg; a21[0] = a21[0] + tA1 * sg; }
 #pragma unroll
-        for (int i = 0; i < R; i++) { h0[i] = pB0[N2 + v + (N2 / R) * i]; h1[i] = pB1[N2 + v + (N2 / R) * i]; }
+        for (int i = 0; i < R; i++) { h0[i] = fa_load16<cplx>(pB0, lv, kH + kI * i); h1[i] = fa_load16<cplx>(pB1, lv, kH + kI * i); }
+        const cplx tB0 = L.tail_in[mB], tB1 = L.tail_in[(size_t)n_in + mB];
 #pragma unroll
         for (int i = 0; i < R; i++) { b11[i] = b11[i] + rot(h0[i]); b21[i] = b21[i] + rot(h1[i]); }
-        if (v == 0) {   // n2 = 0 is element 0 of lane 0
-            a11[0] = a11[0] + tA0 * sg; a21[0] = a21[0] + tA1 * sg;
-            b11[0] = b11[0] + tB0 * sg; b21[0] = b21[0] + tB1 * sg;
-        }
+        if (v == 0) { b11[0] = b11[0] + tB0 * sg; b21[0] = b21[0] + tB1 * sg; }
     } else {
-        const bool split = G.y_split != 0;
-        const int rows = split ? G.N1 / 2 : G.N1;
-        const int row = split ? (k1 >> 1) : k1;
-        const cplx *base = split ? ((k1 & 1) ? G.Y : G.Zprev) : G.Y;
-        const size_t blk = (size_t)rows * N2;
-        const cplx *pA0 = base + (size_t)mA * blk, *pA1 = base + ((size_t)n_in + mA) * blk;
-        const cplx *pB0 = base + (size_t)mB * blk, *pB1 = base + ((size_t)n_in + mB) * blk;
+        const FaRegion pA0 = fa_region(base + (size_t)mA * blk, 16u * (unsigned)blk);
+        const FaRegion pA1 = fa_region(base + ((size_t)n_in + mA) * blk, 16u * (unsigned)blk);
 #pragma unroll
         for (int i = 0; i < R; i++) {
-            const size_t o = yz_index(rows, N2, row, v + (N2 / R) * i);
-            a11[i] = pA0[o]; a21[i] = pA1[o];
+            const unsigned u = yz_row_bytes(rows, N2, row, (N2 / R) * i);
+            a11[i] = fa_load16<cplx>(pA0, lane, u); a21[i] = fa_load16<cplx>(pA1, lane, u);
         }
-        // the right factor's rows are requested from inside the left factor's transforms (MidBLoader):
+        // the right factor's rows are requested from inside the left factor's transforms (bld, MidBLoader):
         // a wave cannot run ahead of a load it has not been able to issue yet, and with all 4*R requests of
         // every wave queued at once the first transform starts only when the whole level has been fetched
-        bld.p0 = pB0; bld.p1 = pB1; bld.rows = rows; bld.row = row; bld.v = v;
     }
     FA_STAMP(G.stamps, 1);
     // ---- bookkeeping of the level (once per pair) and the factors every polynomial shares ------------
@@ -1607,14 +1623,16 @@ template <int N2, int R, bool DIRECT> FA_DEV void body_mid_sym(const BigLevel &G
     fft_wg2<N2, R, 1, +1, true>(b11, b21, lds, v, 0, tw);
     FA_STAMP(G.stamps, 6);
     // ---- stores: conj twiddle and 1/N2 -------------------------------------------------------------------
-    cplx *d0 = G.Z + (size_t)P * G.N1 * N2, *d1 = G.Z + ((size_t)n_out + P) * G.N1 * N2;
+    const unsigned zb = 16u * (unsigned)(G.N1 * N2);
+    const FaRegion d0 = fa_region(G.Z + (size_t)P * G.N1 * N2, zb), d1 = fa_region(G.Z + ((size_t)n_out + P) * G.N1 * N2, zb);
     const cplx wb = wbase * (1.0 / (double)N2);
+    const unsigned lz = yz_lane_bytes(G.N1, N2, v);
 #pragma unroll
     for (int i = 0; i < R; i++) {
         const cplx w = cconj((i == 0) ? wb : wb * wu[i]);
-        const size_t o = yz_index(G.N1, N2, k1, v + (N2 / R) * i);
-        d0[o] = b11[i] * w;
-        d1[o] = b21[i] * w;
+        const unsigned u = yz_row_bytes(G.N1, N2, k1, (N2 / R) * i);
+        fa_store16(d0, lz, u, b11[i] * w);
+        fa_store16(d1, lz, u, b21[i] * w);
     }
     FA_STAMP(G.stamps, 7);
 }
