@@ -106,6 +106,8 @@ EXPORTED = [
     "fnft_amd_inverse_plan_create", "fnft_amd_inverse_plan_destroy", "fnft_amd_inverse_plan_workspace_bytes",
     "fnft_amd_nsev_inverse_device", "fnft_amd_inverse_plan_finish", "fnft_amd_inverse_plan_create_discrete",
     "fnft_amd_nsev_inverse_discrete_device",
+    "fnft_amd_discspec_plan_create", "fnft_amd_discspec_plan_destroy", "fnft_amd_discspec_plan_workspace_bytes",
+    "fnft_amd_nsev_discspec_device", "fnft_amd_discspec_plan_finish",
 ]
 
 _lib = None
@@ -252,6 +254,16 @@ def load(path=None):
                                                         C.c_int]
     L.fnft_amd_nsev_inverse_discrete_device.restype = i32
     L.fnft_amd_nsev_inverse_discrete_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.fnft_amd_discspec_plan_create.restype = i32
+    L.fnft_amd_discspec_plan_create.argtypes = [C.POINTER(vp), sz, sz, sz, C.POINTER(NsevOpts), C.c_int]
+    L.fnft_amd_discspec_plan_destroy.restype = None
+    L.fnft_amd_discspec_plan_destroy.argtypes = [vp]
+    L.fnft_amd_discspec_plan_workspace_bytes.restype = sz
+    L.fnft_amd_discspec_plan_workspace_bytes.argtypes = [vp]
+    L.fnft_amd_nsev_discspec_device.restype = i32
+    L.fnft_amd_nsev_discspec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fnft_amd_discspec_plan_finish.restype = i32
+    L.fnft_amd_discspec_plan_finish.argtypes = [vp, vp, vp, vp]
     if path is None:
         _lib = L
     return L
@@ -837,6 +849,76 @@ class InversePlan:
         wn = np.zeros(self.batch, np.int32)
         rc = self.L.fnft_amd_inverse_plan_finish(self.h, C.c_void_p(stream), _ptr(st), _ptr(wn))
         return int(rc), st, wn
+
+
+def nsev_opts(opts=None):
+    """fnft_nsev_opts_t: the defaults, with the fields of the dict `opts` (reference names; strings for the enums)
+    replaced."""
+    o = load().fnft_nsev_default_opts()
+    for k, v in (opts or {}).items():
+        if k == "discretization":
+            v = NSE_DISC[v] if isinstance(v, str) else int(v)
+        elif k == "bound_state_localization":
+            v = BSLOC[v] if isinstance(v, str) else int(v)
+        elif k == "bound_state_filtering":
+            v = BSFILT[v] if isinstance(v, str) else int(v)
+        elif k == "discspec_type":
+            v = DSTYPE[v] if isinstance(v, str) else int(v)
+        elif k == "contspec_type":
+            v = CSTYPE[v] if isinstance(v, str) else int(v)
+        setattr(o, k, v)
+    return o
+
+
+class DiscSpecPlan:
+    """fnft_amd_discspec_plan_t: the discrete spectrum (NEWTON) of `batch` signals of D samples with K guesses each,
+    one set of options (dict as for nsev_opts; None: the defaults with NEWTON), device-resident.  Raises RuntimeError
+    (attribute rc) if the plan cannot be created."""
+
+    def __init__(self, D, K, batch=1, opts=None, device=0):
+        self.L = load()
+        self.D, self.K, self.batch = int(D), int(K), int(batch)
+        self.opts = None if opts is None else (opts if isinstance(opts, NsevOpts) else nsev_opts(opts))
+        self.h = C.c_void_p()
+        rc = self.L.fnft_amd_discspec_plan_create(C.byref(self.h), self.D, self.K, self.batch,
+                                                  None if self.opts is None else C.byref(self.opts), int(device))
+        if rc != FNFT_SUCCESS:
+            err = RuntimeError("fnft_amd_discspec_plan_create rc=%d (%s)" % (rc, last_error()))
+            err.rc = int(rc)
+            raise err
+
+    def close(self):
+        if self.h:
+            self.L.fnft_amd_discspec_plan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self):
+        return int(self.L.fnft_amd_discspec_plan_workspace_bytes(self.h))
+
+    def nc_len(self):
+        """complex128 values per signal of the norming-constant / residue output (2K for BOTH)."""
+        d = DSTYPE["NORMING_CONSTANTS"] if self.opts is None else int(self.opts.discspec_type)
+        return 2 * self.K if d == DSTYPE["BOTH"] else self.K
+
+    def run_device(self, q_ptr, T, guesses_ptr, bs_ptr, nc_ptr, k_ptr, stream=0):
+        """Enqueue one call: q_ptr (batch*D complex128), guesses_ptr (batch*K) -> bs_ptr (batch*K), nc_ptr (batch *
+        nc_len(), or 0 to skip that stage), k_ptr (batch uint64); raw device addresses (e.g. tensor.data_ptr())."""
+        return int(self.L.fnft_amd_nsev_discspec_device(
+            self.h, C.c_void_p(q_ptr or None), None if T is None else _d2(T), C.c_void_p(guesses_ptr or None),
+            C.c_void_p(bs_ptr or None), C.c_void_p(nc_ptr or None), C.c_void_p(k_ptr or None), C.c_void_p(stream)))
+
+    def finish(self, stream=0):
+        """Waits for `stream`: (rc, status[batch], K_out[batch])."""
+        st = np.zeros(self.batch, np.int32)
+        ko = np.zeros(self.batch, np.uint64)
+        rc = self.L.fnft_amd_discspec_plan_finish(self.h, C.c_void_p(stream), _ptr(st), _ptr(ko))
+        return int(rc), st, ko
 
 
 def poly_fmult2x2_device(deg, n, p_ptr, out_ptr, stream=0):

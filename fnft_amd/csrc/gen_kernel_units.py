@@ -26,6 +26,7 @@ groups["pair2"] = ["KPairFft<%d, 2>" % n for n in PF if n >= 16]
 groups["multi3"] = ["KMulti<%d, 3>" % n for n in (128, 1024)]
 groups["multi2"] = ["KMulti<%d, 2>" % n for n in (128, 1024)]
 groups["leafmulti"] = ["KLeafMulti<%d, %d>" % (d, s) for s in (3, 2) for d in (1, 2, 4)]
+groups["discbatch"] = ["KDsBox", "KDsNewton<false>", "KDsNewton<true>", "KDsFilter", "KDsNorm<false>", "KDsNorm<true>"]
 groups["mid"] = ["KMidSym<true>", "KMidSym<false>"]
 groups["col"] = ["KColFwd<%d>" % n for n in N1_ALL] + ["KColInv<%d>" % n for n in N1_ALL]
 groups["bridge"] = ["KColBridge2<%d>" % n for n in N1_BR + [1024, 2048, 4096]]

@@ -1084,6 +1084,141 @@ FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *strea
     return first;
 }
 
+// ---- batched, device-resident discrete spectrum of fnft_nsev (NEWTON) ----------------------------------------------
+// Size and option checks follow fnft_nsev (fnft_nsev_host.c) in its order, with its codes and message texts, and run
+// before any HIP call.
+struct fnft_amd_discspec_plan {
+    HipBackend be;
+    NftDiscSpecBatch<HipBackend> *ds = nullptr;
+    int device = 0;
+    hipStream_t last_stream = nullptr;
+    const unsigned long long *last_K = nullptr;   // d_K_out of the last call
+    std::vector<int> st;
+    std::vector<unsigned long long> kout;
+    std::mutex mtx;
+};
+
+FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UINT D, FNFT_UINT K, FNFT_UINT batch,
+                                       fnft_nsev_opts_t const *opts, int device)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(D < 2, D);
+    SEAM_CHECK(K == 0, K);
+    SEAM_CHECK(batch == 0, batch);
+    fnft_nsev_opts_t o = opts ? *opts : fnft_nsev_default_opts();
+    if (!opts) o.bound_state_localization = fnft_nsev_bsloc_NEWTON;
+    const int disc = (int)o.discretization, loc = (int)o.bound_state_localization;
+    const bool slow = disc == (int)fnft_nse_discretization_BO
+                      || (disc >= (int)fnft_nse_discretization_CF4_2 && disc <= (int)fnft_nse_discretization_TES4);
+    SEAM_CHECK(slow && loc != (int)fnft_nsev_bsloc_NEWTON, opts->bound_state_localization);   // fnft_nsev.c:183-220
+    SEAM_CHECK(!slow && nft_nse_to_akns(disc) < 0, opts->discretization);
+    if (slow)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (discretization). GPU path covers the fast (polynomial) discretizations.");
+    SEAM_CHECK(loc < 0 || loc > 2, opts->bound_state_localization);
+    SEAM_CHECK((int)o.bound_state_filtering < 0 || (int)o.bound_state_filtering > 2, opts->bound_state_filtering);
+    SEAM_CHECK((int)o.discspec_type < 0 || (int)o.discspec_type > 2, opts->discspec_type);
+    if (loc != (int)fnft_nsev_bsloc_NEWTON)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched discrete spectrum: FAST_EIGENVALUE and SUBSAMPLE_AND_REFINE).");
+    if (o.richardson_extrapolation_flag != 0)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched discrete spectrum: Richardson extrapolation).");
+    if (K > NftDiscSpecBatch<HipBackend>::kMaxK || batch > NftDiscSpecBatch<HipBackend>::kMaxGroups / K)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched discrete spectrum: K > 65535 or batch*K > 2^31 - 1).");
+    DeviceGuard dg(device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    fnft_amd_discspec_plan *P = new (std::nothrow) fnft_amd_discspec_plan();
+    if (!P) return FNFT_EC_NOMEM;
+    P->device = device;
+    NftDsOpts d;
+    d.bsfilt = (int)o.bound_state_filtering; d.bsloc = 1; d.niter = o.niter; d.Dsub = 0;
+    d.dstype = (int)o.discspec_type; d.nse_disc = disc; d.richardson = 0;
+    P->ds = new (std::nothrow) NftDiscSpecBatch<HipBackend>(P->be, (size_t)D, (size_t)K, (size_t)batch, d);
+    if (!P->ds) { delete P; return FNFT_EC_NOMEM; }
+    const int rc = P->ds->init();
+    if (rc != NFT_SUCCESS || P->be.failed) {
+        (void)P->be.sync();
+        P->ds->destroy();
+        delete P->ds;
+        delete P;
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = P;
+    return FNFT_SUCCESS;
+}
+
+void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
+{
+    if (!plan) return;
+    {
+        DeviceGuard dg(plan->device);
+        // the pool hands these blocks to the next allocation: nothing the plan enqueued may still be writing them
+        if (plan->last_stream) (void)hipStreamSynchronize(plan->last_stream);
+        (void)hipDeviceSynchronize();
+        plan->ds->destroy();
+        delete plan->ds;
+        plan->be.destroy_events();
+    }
+    delete plan;
+}
+
+FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan)
+{
+    return plan ? plan->ds->workspace_bytes() : 0;
+}
+
+FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
+                                       const void *d_guesses, void *d_bound_states, void *d_normconsts_or_residues,
+                                       void *d_K_out, void *stream)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(!d_q, q);
+    SEAM_CHECK(T == NULL || T[0] >= T[1], T);
+    SEAM_CHECK(!d_guesses, guesses);
+    SEAM_CHECK(!d_bound_states, bound_states);
+    SEAM_CHECK(!d_K_out, K_out);
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    DeviceGuard dg(plan->device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    plan->be.stream = (hipStream_t)stream;
+    plan->last_stream = (hipStream_t)stream;
+    plan->last_K = (const unsigned long long *)d_K_out;
+    plan->be.failed = false;
+    const int rc = plan->ds->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
+                                 (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
+    if (plan->be.failed) return FNFT_EC_OTHER;
+    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+}
+
+FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *stream, FNFT_INT *status,
+                                       FNFT_UINT *K_out)
+{
+    SEAM_CHECK(!plan, plan);
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    DeviceGuard dg(plan->device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    plan->be.stream = (hipStream_t)stream;
+    const int rc = plan->ds->read(plan->st, plan->kout, plan->last_K);
+    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
+    FNFT_INT first = FNFT_SUCCESS;
+    for (size_t b = 0; b < plan->st.size(); b++) {
+        const int h = plan->st[b];
+        // the drop-in on this signal alone, in its order: the MODAL step-size check of the transform it runs first
+        // (fnft__akns_fscatter.c:122-126), an empty bounding box, a' = 0 in the refinement or the residues -- each
+        // passed on as a subroutine failure (negative)
+        FNFT_INT s = FNFT_SUCCESS;
+        if (h & 1) s = -FNFT_EC_OTHER;
+        else if (h & 4) s = -FNFT_EC_INVALID_ARGUMENT;
+        else if (h & 2) s = -FNFT_EC_DIV_BY_ZERO;
+        if (status) status[b] = s;
+        if (K_out) K_out[b] = (FNFT_UINT)plan->kout[b];
+        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
+    }
+    return first;
+}
+
 FNFT_INT fnft_amd_poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const double *A,
                               const double *W, const FNFT_UINT M, FNFT_COMPLEX *const result)
 {

@@ -14,6 +14,7 @@
 
 #include "nft_api.h"
 #include "nft_discspec.h"
+#include "nft_discspec_batch.h"
 
 extern thread_local std::string g_last_error;   // defined in hip_backend.hip
 

@@ -1,0 +1,151 @@
+// nft_discspec_batch.h -- batched, device-resident discrete spectrum of fnft_nsev (NEWTON localization, kappa = +1):
+// `batch` signals of D samples with K eigenvalue guesses each, every array on the device, nothing read back between
+// the stages.  Per signal it computes what NftDiscSpec::base() with bsloc == 1 computes (nft_discspec.h; reference:
+// src/fnft_nsev.c:971-1038 Newton refinement, misc_filter / misc_merge, :895-968 norming constants / residues), with
+// one workgroup per (signal, eigenvalue) instead of a host loop over chunk kernels (nft_kernels.h: body_ds_*).
+//   box kernel -> Newton kernel (all iterations on chip) -> filter + merge kernel -> norming kernel
+// 4SPLIT4A/B refine on the resampled signal of the batched front end of NftPlan (set_front / run_front, qpre).
+// Back-end independent like NftDiscSpec: hip_backend.hip instantiates it with the HIP back end, tests/emu with the
+// lane emulator.
+#pragma once
+#include "nft_discspec.h"
+
+template <class BE> class NftDiscSpecBatch {
+public:
+    BE &be;
+    const size_t D, K, batch;
+    const NftDsOpts o;
+    int ups = 1, deg0 = 0, akns = -1;
+    size_t Dq = 0;                    // preprocessed samples per signal
+    int G = 1;                        // samples per lane
+    std::unique_ptr<NftPlan<BE>> front;   // 4SPLIT4A/B: resampling workspace
+    cplx *lam = nullptr;              // batch*K refined eigenvalues
+    double *box = nullptr;            // batch*4
+    int *status = nullptr;            // batch
+    cplx *phi = nullptr;              // slab * K * sphi
+    size_t slab = 0, sphi = 0;        // signals per launch of the norming kernel; phi values per (signal, eigenvalue)
+    size_t bytes = 0;
+    static constexpr size_t kMaxK = 65535;                      // the merge is one lane's O(K^2) loop per signal
+    static constexpr size_t kMaxGroups = 0x7fffffff;            // batch*K workgroups on grid.x
+    static constexpr size_t kPhiBytes = (size_t)256 << 20;      // phi workspace of one norming launch
+
+    NftDiscSpecBatch(BE &be_, size_t D_, size_t K_, size_t batch_, const NftDsOpts &o_)
+        : be(be_), D(D_), K(K_), batch(batch_), o(o_)
+    {
+        akns = nft_nse_to_akns(o.nse_disc);
+        ups = nft_nse_upsampling(o.nse_disc);
+        deg0 = akns >= 0 ? nft_akns_degree(akns) : 0;
+        Dq = D * (size_t)ups;
+        size_t g = (Dq + kDsLanes - 1) / kDsLanes;
+        g = (g + (size_t)ups - 1) / (size_t)ups * (size_t)ups;
+        G = (int)g;
+        sphi = ((size_t)G / (size_t)ups + 1) * (size_t)kDsLanes * 2;
+    }
+
+    template <class T> bool alloc(T *&p, size_t count)
+    {
+        const size_t b = count * sizeof(T);
+        p = (T *)be.alloc(b ? b : 16);
+        if (!p) return false;
+        bytes += b;
+        return true;
+    }
+
+    int init()
+    {
+        if (akns < 0 || deg0 == 0 || D < 2 || K == 0 || batch == 0) return NFT_EC_INVALID_ARGUMENT;
+        if (K > kMaxK || batch > kMaxGroups / K || Dq > (size_t)0x7fffffff * (size_t)kDsLanes)
+            return NFT_EC_NOT_YET_IMPLEMENTED;
+        if (ups == 2) {
+            front.reset(new NftPlan<BE>(be, Dq, 0, batch, akns, deg0));
+            front->set_front(D, 1, ups);
+            const int rc = front->init();
+            if (rc != NFT_SUCCESS) return rc;
+        }
+        const size_t per_signal = K * sphi * sizeof(cplx);
+        slab = kPhiBytes / per_signal;
+        if (slab < 1) slab = 1;
+        if (slab > batch) slab = batch;
+        bool ok = alloc(lam, batch * K) && alloc(box, batch * 4) && alloc(status, batch) && alloc(phi, slab * K * sphi);
+        return ok ? NFT_SUCCESS : NFT_EC_NOMEM;
+    }
+
+    void destroy()
+    {
+        if (front) front->destroy();
+        front.reset();
+        be.free(lam); be.free(box); be.free(status); be.free(phi);
+        lam = nullptr; box = nullptr; status = nullptr; phi = nullptr;
+    }
+
+    size_t workspace_bytes() const { return bytes + (front ? front->bytes : 0); }
+
+    // enqueues everything; waits for nothing.  d_nc may be NULL (no norming constants / residues)
+    int run(const cplx *d_q, const double T[2], const cplx *d_guess, cplx *d_bs, cplx *d_nc,
+            unsigned long long *d_K)
+    {
+        // grid and step as NftDiscSpec::prepare forms them for the full signal (Dsub = D, nskip = 1)
+        const double eps_in = (T[1] - T[0]) / (double)(D - 1);
+        const double T1 = T[0] + (double)(D - 1) * eps_in;
+        const double eps_t = (T1 - T[0]) / (double)(D - 1);
+        be.memset0(status, batch * sizeof(int));
+        const cplx *qpre = d_q;
+        if (ups == 2) {
+            double Tsub[2];
+            const int rc = front->run_front(d_q, T, +1, Tsub);   // resampling (and level 0 of the tree, unused here)
+            if (rc != NFT_SUCCESS) return rc;
+            qpre = front->qpre;
+        }
+        DsBatchParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.q = qpre;
+        P.D = (long long)Dq;
+        P.ups = ups;
+        P.G = G;
+        P.lscale = (ups == 2) ? 0.5 : 1.0;
+        P.T0 = T[0]; P.T1 = T1; P.eps = eps_t;
+        P.K = (int)K;
+        P.batch = (long long)batch;
+        P.guess = d_guess;
+        P.lam = lam;
+        P.src = (o.niter > 0) ? lam : d_guess;
+        P.box = box;
+        P.re_bound = 0.9 * 3.14159265358979323846 / std::fabs(2.0 / (double)deg0 * eps_t);
+        P.bsfilt = o.bsfilt;
+        P.niter = (int)std::min<size_t>(o.niter, 0x7fffffff);
+        P.dstype = o.dstype;
+        P.modal = (o.nse_disc == 0) ? 1 : 0;
+        P.status = status;
+        P.bs = d_bs;
+        P.nc = d_nc;
+        P.K_out = d_K;
+        P.phi = phi;
+        P.sphi = (long long)sphi;
+        const bool ldsq = Dq <= (size_t)kDsLdsSamples;
+        be.template run<KDsBox>((int)batch, 1, P);
+        if (o.niter > 0) {
+            if (ldsq) be.template run<KDsNewton<true>>((int)(batch * K), 1, P);
+            else be.template run<KDsNewton<false>>((int)(batch * K), 1, P);
+        }
+        be.template run<KDsFilter>((int)((batch + 255) / 256), 1, P);
+        if (d_nc) {
+            for (size_t b0 = 0; b0 < batch; b0 += slab) {
+                const size_t nb = std::min(slab, batch - b0);
+                P.b0 = (long long)b0;
+                if (ldsq) be.template run<KDsNorm<true>>((int)(nb * K), 1, P);
+                else be.template run<KDsNorm<false>>((int)(nb * K), 1, P);
+            }
+        }
+        return NFT_SUCCESS;
+    }
+
+    // waits for the stream; st: the status words, kout: the counts (d_K of the last call)
+    int read(std::vector<int> &st, std::vector<unsigned long long> &kout, const unsigned long long *d_K)
+    {
+        st.assign(batch, 0);
+        kout.assign(batch, 0);
+        be.d2h(st.data(), status, batch * sizeof(int));
+        if (d_K) be.d2h(kout.data(), d_K, batch * sizeof(unsigned long long));
+        return be.sync();
+    }
+};

@@ -91,6 +91,31 @@ struct KBsPsi {
     static constexpr size_t lds_bytes() { return 0; }
     static FA_DEV void body(const Params &p) { body_bs_psi(p); }
 };
+// batched discrete spectrum (nft_discspec_batch.h); LDSQ adds the staged signal to the workgroup's LDS
+struct KDsBox {
+    using Params = DsBatchParams;
+    static constexpr int THREADS = kDsLanes;
+    static constexpr size_t lds_bytes() { return kDsLanes * sizeof(double); }
+    static FA_DEV void body(const Params &p) { body_ds_box(p); }
+};
+template <bool LDSQ> struct KDsNewton {
+    using Params = DsBatchParams;
+    static constexpr int THREADS = kDsLanes;
+    static constexpr size_t lds_bytes() { return ((size_t)kDsLanes * 8 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx); }
+    static FA_DEV void body(const Params &p) { body_ds_newton<LDSQ>(p); }
+};
+struct KDsFilter {
+    using Params = DsBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_ds_filter(p); }
+};
+template <bool LDSQ> struct KDsNorm {
+    using Params = DsBatchParams;
+    static constexpr int THREADS = kDsLanes;
+    static constexpr size_t lds_bytes() { return ((size_t)kDsLanes * 10 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx); }
+    static FA_DEV void body(const Params &p) { body_ds_norm<LDSQ>(p); }
+};
 struct KGridMark {
     using Params = GridSearchParams;
     static constexpr int THREADS = 256;

@@ -2685,6 +2685,374 @@ FA_DEV void body_bs_pick(const BsParams &P)
 }
 
 // ---------------------------------------------------------------------------------------------
+// Batched discrete spectrum (fnft_amd_discspec_plan_*, nft_discspec_batch.h): many short signals with a handful of
+// eigenvalues each.  The chunk kernels above spread ONE signal over a grid and return to the host after every Newton
+// step; here one workgroup owns one (signal, eigenvalue) pair from the first guess to the result:
+//   body_ds_box     per signal: the bounding box of the filter (trapezoid rule of l2norm2) and the MODAL step check
+//   body_ds_newton  per (signal, eigenvalue): every Newton iteration on chip -- lane t composes the map {M, M'} of its
+//                   run of samples (the step arithmetic of body_bs_chunk), the 256 maps are combined pairwise through
+//                   LDS in 8 rounds, lane 0 forms a, a', applies the reference's update and stopping rule
+//                   (src/fnft_nsev.c:971-1038) and broadcasts the new lambda or the stop
+//   body_ds_filter  per signal: box test and in-order merge (NftDiscSpec::filter_merge), K_out, NaN tails
+//   body_ds_norm    per (signal, surviving eigenvalue): a', phi forward and psi backward over the runs, the grid point
+//                   with the smallest bs_metric (first on ties), b = phi1/psi1 there, residue b/a'
+// LDSQ: the signal's samples are staged in LDS once per workgroup (up to kDsLdsSamples of them); longer signals are
+// read from global memory / L2 by the same body.
+// ---------------------------------------------------------------------------------------------
+constexpr int kDsLanes = 256;
+constexpr int kDsLdsSamples = 2048;   // 32 KiB of samples next to 32-40 KiB of maps: two workgroups per CU (160 KiB)
+struct DsBatchParams {
+    const cplx *q;            // batch * D preprocessed samples, signal b at b*D
+    long long D;              // preprocessed samples per signal (a multiple of ups)
+    int ups;                  // samples per grid point: 1 BO, 2 CF4_2
+    int G;                    // samples per lane (a multiple of ups), kDsLanes*G >= D
+    double lscale;            // 1/2 for CF4_2, 1 otherwise (BsParams::lscale)
+    double T0, T1, eps;
+    int K;                    // eigenvalue slots per signal
+    long long batch;
+    long long b0;             // body_ds_norm: first signal of this launch
+    const cplx *guess;        // batch*K initial values (never written)
+    cplx *lam;                // batch*K refined values (body_ds_newton out)
+    const cplx *src;          // body_ds_filter in: lam, or guess when nothing was refined
+    double *box;              // batch*4: re_lo, re_hi, im_lo, im_hi
+    double re_bound;          // FULL filter: 0.9 pi / |2 eps_t / deg|
+    int bsfilt, niter, dstype, modal;
+    int *status;              // per signal; bit 0: MODAL step-size check, bit 1: a' = 0, bit 2: empty bounding box
+    cplx *bs, *nc;            // caller's outputs (nc may be NULL)
+    unsigned long long *K_out;
+    cplx *phi;                // body_ds_norm: phi at the grid points of every lane's run, sphi values per workgroup,
+    long long sphi;           //   point j of lane t at (j*kDsLanes + t)*2
+};
+
+FA_DEV double ds_inf() { return 1.0e308 * 10.0; }
+
+// {M, M'} of samples n0 .. n1-1 at l (forward steps; body_bs_chunk's loop for r = -conj(q))
+FA_DEV void ds_run_map(const cplx *q, long long n0, long long n1, cplx l, double eps, cplx *o)
+{
+    cplx m00 = cmake(1.0, 0.0), m01 = cmake(0.0, 0.0), m10 = m01, m11 = m00;
+    cplx d00 = m01, d01 = m01, d10 = m01, d11 = m01;
+    BsStep U, V;
+    for (long long n = n0; n < n1; n++) {
+        bs_step<true>(q[n], l, eps, U, V);
+        const cplx e00 = V.u00 * m00 + V.u01 * m10 + U.u00 * d00 + U.u01 * d10;
+        const cplx e01 = V.u00 * m01 + V.u01 * m11 + U.u00 * d01 + U.u01 * d11;
+        const cplx e10 = V.u10 * m00 + V.u11 * m10 + U.u10 * d00 + U.u11 * d10;
+        const cplx e11 = V.u10 * m01 + V.u11 * m11 + U.u10 * d01 + U.u11 * d11;
+        d00 = e00; d01 = e01; d10 = e10; d11 = e11;
+        const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
+        const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
+        m00 = f00; m01 = f01; m10 = f10; m11 = f11;
+    }
+    o[0] = m00; o[1] = m01; o[2] = m10; o[3] = m11; o[4] = d00; o[5] = d01; o[6] = d10; o[7] = d11;
+}
+
+// a and a' from the map of the whole signal (stage 2 of body_bs_combine: start vector, end phase)
+FA_DEV void ds_a_aprime(const DsBatchParams &P, const cplx *m, cplx lc, cplx &av, cplx &apv)
+{
+    double s, c;
+    const double ta = P.T0 - P.eps * 0.5, tb = P.T1 + P.eps * 0.5;
+    fa_sincos(-lc.x * ta, &s, &c);
+    const cplx p1 = cmake(c, s) * exp(lc.y * ta);      // e^{-i lam ta}
+    const cplx d1 = p1 * cmake(0.0, -ta);
+    fa_sincos(lc.x * tb, &s, &c);
+    const cplx ph = cmake(c, s) * exp(-lc.y * tb);     // e^{i lam tb}
+    const cplx pe = m[0] * p1;
+    const cplx de = m[4] * p1 + m[0] * d1;
+    av = pe * ph;
+    apv = (de * ph + cmake(0.0, tb) * av) * P.lscale;
+}
+
+// one workgroup per signal
+FA_DEV void body_ds_box(const DsBatchParams &P)
+{
+    FA_LDS_DECL
+    double *red = (double *)FA_LDS_PTR;
+    const long long b = FA_BID;
+    const int t = FA_TID, nl = FA_BDIM;
+    const cplx *q = P.q + b * P.D;
+    const long long N = P.D / P.ups;
+    double acc = 0.0;
+    bool bad = false;
+    for (long long i = t; i < N; i += nl) {
+        // 4SPLIT4A/B: the middle sample of every pair, times the upsampling factor (NftDiscSpec::base)
+        const cplx z = (P.ups == 1) ? q[i] : q[i * P.ups + 1] * (double)P.ups;
+        const double n2 = cnorm2(z);
+        acc += ((i == 0 || i == N - 1) ? 0.5 : 1.0) * n2;
+        if (P.modal && z.x == 0.0 && P.eps * sqrt(n2) >= 1.0) bad = true;   // sample_coeffs, 2SPLIT2_MODAL, r = -conj(q)
+    }
+    if (bad) fa_atomic_or_i32(P.status + b, 1);
+    red[t] = acc;
+    FA_SYNC();
+    for (int h = nl / 2; h >= 1; h >>= 1) {
+        if (t < h) red[t] += red[t + h];
+        FA_SYNC();
+    }
+    if (t != 0) return;
+    double *box = P.box + 4 * b;
+    const double inf = ds_inf();
+    box[0] = -inf; box[1] = inf; box[2] = -inf; box[3] = inf;
+    if (P.bsfilt == 1) box[2] = 0.0;
+    else if (P.bsfilt == 2) {
+        box[1] = P.re_bound;
+        box[0] = -P.re_bound;
+        box[2] = 0.0;
+        box[3] = 1.5 * 0.25 * (((P.T1 - P.T0) / (double)N) * red[0]);
+    }
+    if (P.niter > 0 && (!(box[0] <= box[1]) || !(box[2] <= box[3]))) fa_atomic_or_i32(P.status + b, 4);
+}
+
+template <bool LDSQ> FA_DEV void body_ds_newton(const DsBatchParams &P)
+{
+    FA_LDS_DECL
+    cplx *gm = (cplx *)FA_LDS_PTR;            // lanes x 8: {M[4], M'[4]} of the lane's run, then of growing spans
+    cplx *ctl = gm + (size_t)kDsLanes * 8;    // [0]: lambda of this iteration, [1].x: 1 = go on
+    cplx *ql = ctl + 2;                       // LDSQ: the signal
+    const int t = FA_TID;
+    const long long w = FA_BID;               // signal * K + eigenvalue
+    const long long b = w / P.K;
+    const cplx *q = P.q + b * P.D;
+    if (LDSQ) {
+        for (long long i = t; i < P.D; i += kDsLanes) ql[i] = q[i];
+        q = ql;
+    }
+    const long long n0 = ((long long)t * P.G < P.D) ? (long long)t * P.G : P.D;
+    const long long n1 = (n0 + P.G < P.D) ? n0 + P.G : P.D;
+    const double *box = P.box + 4 * b;
+    if (t == 0) {
+        ctl[0] = P.guess[w];
+        const bool ok = P.niter > 0 && (box[0] <= box[1]) && (box[2] <= box[3]);
+        ctl[1] = cmake(ok ? 1.0 : 0.0, 0.0);
+    }
+    FA_SYNC();
+    int it = 0;
+    while (ctl[1].x != 0.0) {
+        const cplx lc = ctl[0];
+        ds_run_map(q, n0, n1, lc * P.lscale, P.eps, gm + (size_t)t * 8);
+        FA_SYNC();
+        for (int s = 1; s < kDsLanes; s <<= 1) {
+            if ((t & (2 * s - 1)) == 0) {   // (M, D) <- (m M, m' M + m D), m the later span
+                cplx *M = gm + (size_t)t * 8;
+                const cplx *m = gm + (size_t)(t + s) * 8;
+                const cplx e0 = m[4] * M[0] + m[5] * M[2] + m[0] * M[4] + m[1] * M[6];
+                const cplx e1 = m[4] * M[1] + m[5] * M[3] + m[0] * M[5] + m[1] * M[7];
+                const cplx e2 = m[6] * M[0] + m[7] * M[2] + m[2] * M[4] + m[3] * M[6];
+                const cplx e3 = m[6] * M[1] + m[7] * M[3] + m[2] * M[5] + m[3] * M[7];
+                const cplx f0 = m[0] * M[0] + m[1] * M[2], f1 = m[0] * M[1] + m[1] * M[3];
+                const cplx f2 = m[2] * M[0] + m[3] * M[2], f3 = m[2] * M[1] + m[3] * M[3];
+                M[0] = f0; M[1] = f1; M[2] = f2; M[3] = f3; M[4] = e0; M[5] = e1; M[6] = e2; M[7] = e3;
+            }
+            FA_SYNC();
+        }
+        if (t == 0) {
+            cplx av, apv, ln = lc;
+            ds_a_aprime(P, gm, lc, av, apv);
+            bool go = true;
+            if (av.x == 0.0 && av.y == 0.0) go = false;
+            else if (apv.x == 0.0 && apv.y == 0.0) {
+                fa_atomic_or_i32(P.status + b, 2);
+                go = false;
+            } else {
+                const cplx err = c_div(av, apv);
+                ln = lc - err;
+                it++;
+                if (ln.y > box[3] || ln.x > box[1] || ln.x < box[0] || ln.y < box[2]) go = false;
+                else if (!(sqrt(cnorm2(err)) > 100.0 * 2.220446049250313e-16 && it < P.niter)) go = false;
+            }
+            ctl[0] = ln;
+            ctl[1] = cmake(go ? 1.0 : 0.0, 0.0);
+        }
+        FA_SYNC();
+    }
+    if (t == 0) P.lam[w] = ctl[0];
+}
+
+// one lane per signal
+FA_DEV void body_ds_filter(const DsBatchParams &P)
+{
+    const long long b = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (b >= P.batch) return;
+    const int K = P.K;
+    const cplx *src = P.src + b * K;
+    cplx *v = P.bs + b * K;
+    int n = 0;
+    if (P.bsfilt == 0) {
+        for (int i = 0; i < K; i++) v[i] = src[i];
+        n = K;
+    } else {
+        const double *box = P.box + 4 * b;
+        for (int i = 0; i < K; i++) {
+            const cplx x = src[i];
+            if (!(x.x >= box[0]) || !(x.x <= box[1])) continue;
+            if (!(x.y >= box[2]) || !(x.y <= box[3])) continue;
+            v[n++] = x;
+        }
+        if (n > 0) {
+            const double tol = sqrt(2.220446049250313e-16);
+            int kept = 1;
+            for (int i = 1; i < n; i++) {
+                double dist = -1.0;
+                const cplx vi = v[i];
+                for (int j = 0; j < i; j++) {
+                    dist = sqrt(cnorm2(v[j] - vi));
+                    if (dist < tol) break;
+                }
+                if (dist < tol) continue;
+                v[kept++] = vi;
+            }
+            n = kept;
+        }
+    }
+    const double qn = __builtin_nan("");
+    for (int i = n; i < K; i++) v[i] = cmake(qn, qn);
+    if (P.nc) {
+        const int W = (P.dstype == 2) ? 2 * K : K;
+        cplx *nc = P.nc + b * W;
+        for (int i = 0; i < W; i++) nc[i] = cmake(qn, qn);
+    }
+    P.K_out[b] = (unsigned long long)n;
+}
+
+template <bool LDSQ> FA_DEV void body_ds_norm(const DsBatchParams &P)
+{
+    FA_LDS_DECL
+    cplx *gm = (cplx *)FA_LDS_PTR;            // lanes x 8: forward {M, M'}; then lanes x 4 backward maps; then the reduction
+    cplx *gv = gm + (size_t)kDsLanes * 8;     // lanes x 2: phi at the start of the run; then psi at its end
+    cplx *ctl = gv + (size_t)kDsLanes * 2;    // [0]: a'
+    cplx *ql = ctl + 2;
+    const int t = FA_TID;
+    const long long w = FA_BID;
+    const long long b = P.b0 + w / P.K;
+    const int e = (int)(w % P.K);
+    if ((unsigned long long)e >= P.K_out[b]) return;   // the whole workgroup: nothing survived in this slot
+    const cplx *q = P.q + b * P.D;
+    if (LDSQ) {
+        for (long long i = t; i < P.D; i += kDsLanes) ql[i] = q[i];
+        q = ql;
+        FA_SYNC();
+    }
+    const long long n0 = ((long long)t * P.G < P.D) ? (long long)t * P.G : P.D;
+    const long long n1 = (n0 + P.G < P.D) ? n0 + P.G : P.D;
+    const cplx lc = P.bs[b * P.K + e];
+    const cplx l = lc * P.lscale;
+    const cplx zero = cmake(0.0, 0.0);
+    double s, c;
+    ds_run_map(q, n0, n1, l, P.eps, gm + (size_t)t * 8);
+    FA_SYNC();
+    if (t == 0) {   // phi at the start of every run; a' from the end
+        const double ta = P.T0 - P.eps * 0.5, tb = P.T1 + P.eps * 0.5;
+        fa_sincos(-lc.x * ta, &s, &c);
+        cplx p1 = cmake(c, s) * exp(lc.y * ta), p2 = zero;
+        cplx d1 = p1 * cmake(0.0, -ta), d2 = zero;
+        for (int g = 0; g < kDsLanes; g++) {
+            gv[2 * g] = p1; gv[2 * g + 1] = p2;
+            const cplx *m = gm + (size_t)g * 8;
+            const cplx n1v = m[4] * p1 + m[5] * p2 + m[0] * d1 + m[1] * d2;
+            const cplx n2v = m[6] * p1 + m[7] * p2 + m[2] * d1 + m[3] * d2;
+            d1 = n1v; d2 = n2v;
+            const cplx t1 = m[0] * p1 + m[1] * p2, t2 = m[2] * p1 + m[3] * p2;
+            p1 = t1; p2 = t2;
+        }
+        fa_sincos(lc.x * tb, &s, &c);
+        const cplx ph = cmake(c, s) * exp(-lc.y * tb);
+        const cplx av = p1 * ph;
+        ctl[0] = (d1 * ph + cmake(0.0, tb) * av) * P.lscale;
+    }
+    FA_SYNC();
+    cplx *PHI = P.phi + w * P.sphi + (size_t)t * 2;   // point j of this lane at PHI[j * kDsLanes * 2]
+    BsStep U, V;
+    {   // phi at the grid points of the run (point j follows sample n0 + ups*j - 1); the run's backward map
+        cplx p1 = gv[2 * t], p2 = gv[2 * t + 1];
+        long long j = 0;
+        PHI[0] = p1; PHI[1] = p2;
+        for (long long n = n0; n < n1; n++) {
+            bs_step<false>(q[n], l, P.eps, U, V);
+            const cplx t1 = U.u00 * p1 + U.u01 * p2, t2 = U.u10 * p1 + U.u11 * p2;
+            p1 = t1; p2 = t2;
+            if ((n + 1) % P.ups == 0) {
+                j++;
+                PHI[j * kDsLanes * 2] = p1; PHI[j * kDsLanes * 2 + 1] = p2;
+            }
+        }
+        cplx m00 = cmake(1.0, 0.0), m01 = zero, m10 = zero, m11 = m00;
+        for (long long n = n1; n-- > n0;) {
+            bs_step<false>(q[n], l, -P.eps, U, V);
+            const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
+            const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
+            m00 = f00; m01 = f01; m10 = f10; m11 = f11;
+        }
+        cplx *o = gm + (size_t)t * 4;
+        o[0] = m00; o[1] = m01; o[2] = m10; o[3] = m11;
+    }
+    FA_SYNC();
+    if (t == 0) {   // psi at the end of every run, from (0, e^{i lam tb}) at the end of the grid
+        const double tb = P.T1 + P.eps * 0.5;
+        fa_sincos(lc.x * tb, &s, &c);
+        cplx s1 = zero, s2 = cmake(c, s) * exp(-lc.y * tb);
+        for (int g = kDsLanes; g-- > 0;) {
+            gv[2 * g] = s1; gv[2 * g + 1] = s2;
+            const cplx *m = gm + (size_t)g * 4;
+            const cplx t1 = m[0] * s1 + m[1] * s2, t2 = m[2] * s1 + m[3] * s2;
+            s1 = t1; s2 = t2;
+        }
+    }
+    FA_SYNC();
+    // psi backwards through the run; the run owns its grid points except its first one (run 0 owns point 0 too);
+    // its best point by the metric, the first one on ties
+    double best = ds_inf();
+    cplx bval = zero;
+    if (n1 > n0) {
+        cplx s1 = gv[2 * t], s2 = gv[2 * t + 1];
+        long long j = (n1 - n0) / P.ups;
+        {
+            const cplx f1 = PHI[j * kDsLanes * 2], f2 = PHI[j * kDsLanes * 2 + 1];
+            const double m = bs_metric(f1, f2, s1, s2);
+            if (m <= best) { best = m; bval = c_div(f1, s1); }
+        }
+        for (long long n = n1; n-- > n0;) {
+            bs_step<false>(q[n], l, -P.eps, U, V);
+            const cplx t1 = U.u00 * s1 + U.u01 * s2, t2 = U.u10 * s1 + U.u11 * s2;
+            s1 = t1; s2 = t2;
+            if (n % P.ups == 0) {
+                j--;
+                if (n > n0 || t == 0) {
+                    const cplx f1 = PHI[j * kDsLanes * 2], f2 = PHI[j * kDsLanes * 2 + 1];
+                    const double m = bs_metric(f1, f2, s1, s2);
+                    if (m <= best) { best = m; bval = c_div(f1, s1); }
+                }
+            }
+        }
+    }
+    double *lm = (double *)gm;                // lanes: best metric
+    int *li = (int *)(lm + kDsLanes);         // lanes: its lane (grid order)
+    lm[t] = best;
+    li[t] = (best < ds_inf()) ? t : 0x7fffffff;
+    FA_SYNC();
+    for (int h = kDsLanes / 2; h >= 1; h >>= 1) {
+        if (t < h) {
+            const double mo = lm[t + h];
+            const int io = li[t + h];
+            if (mo < lm[t] || (mo == lm[t] && io < li[t])) { lm[t] = mo; li[t] = io; }
+        }
+        FA_SYNC();
+    }
+    const int win = li[0];
+    if (t != ((win != 0x7fffffff) ? win : 0)) return;
+    if (win == 0x7fffffff) bval = zero;
+    const cplx apv = ctl[0];
+    cplx res = zero;
+    if (P.dstype != 0) {
+        if (apv.x == 0.0 && apv.y == 0.0) fa_atomic_or_i32(P.status + b, 2);
+        res = c_div(bval, apv);
+    }
+    if (P.dstype == 0) P.nc[b * P.K + e] = bval;
+    else if (P.dstype == 1) P.nc[b * P.K + e] = res;
+    else {
+        P.nc[b * 2 * P.K + e] = bval;
+        P.nc[b * 2 * P.K + P.K + e] = res;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Roots of a polynomial on an arc of the unit circle by grid search (src/private/fnft__poly_roots_fftgridsearch.c):
 // the polynomial is evaluated by chirp z-transforms (three rings, or one for the para-Hermitian form); these
 // kernels mark the grid points that hold a root estimate and then compact the estimates IN GRID ORDER (block counts,

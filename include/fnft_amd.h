@@ -507,8 +507,51 @@ FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, co
                                                const void *d_normconsts_or_residues, void *d_q, const FNFT_REAL *T,
                                                FNFT_INT kappa, void *stream);
 
+/* Batched, device-resident discrete spectrum of fnft_nsev (focusing case, kappa = +1): for each of `batch` signals of
+ * D samples what fnft_nsev computes on it alone with bound_state_localization = NEWTON, that signal's K guesses as
+ * the initial bound_states, *K_ptr = K and contspec = NULL -- the Newton refinement, the filter and merge
+ * (opts->bound_state_filtering) and the norming constants, residues or both (opts->discspec_type).  niter,
+ * bound_state_filtering, discspec_type and discretization are taken from opts at create time; niter = 0 is valid
+ * (norming constants at the caller's eigenvalues, no refinement).  opts == NULL: fnft_nsev_default_opts() with the
+ * localization taken as NEWTON.  All 21 fast discretizations: the 19 with upsampling factor 1 refine with the BO steps
+ * on the raw samples, 4SPLIT4A/B with CF4_2 on the samples the plan resamples into its own workspace (the resampler's
+ * "not band-limited" warning is not reported here).
+ * Create-time codes, before any HIP call: FNFT_EC_INVALID_ARGUMENT for plan == NULL, D < 2, K == 0, batch == 0, an
+ * unknown discretization, bound_state_localization, bound_state_filtering or discspec_type;
+ * FNFT_EC_NOT_YET_IMPLEMENTED for the slow discretizations (BO, CF*, ES4, TES4), a localization other than NEWTON,
+ * richardson_extrapolation_flag != 0, and K > 65535 or batch*K > 2^31 - 1 (one workgroup per (signal, eigenvalue) on
+ * one grid axis; one lane merges a signal's K values).  Every workspace is allocated at create; a call allocates
+ * nothing, never waits for the device and copies nothing to the host.  One workgroup refines one (signal, eigenvalue)
+ * pair through all its iterations on chip; signals of up to 2048 preprocessed samples are staged in LDS. */
+typedef struct fnft_amd_discspec_plan fnft_amd_discspec_plan_t;
+FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UINT D, FNFT_UINT K, FNFT_UINT batch,
+                                       fnft_nsev_opts_t const *opts, int device);
+/* Waits for the plan's last stream, then gives its workspace back.  NULL is ignored. */
+void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan);
+/* Bytes of HBM the plan holds. */
+FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan);
+/* d_q: batch*D complex128 (device; signal b at +b*D) and d_guesses: batch*K complex128, both NOT modified.
+ * d_bound_states: batch*K complex128 out: the first K_out[b] entries of signal b are its bound states in the order
+ * fnft_nsev returns them, the rest NaN + NaN i.  d_normconsts_or_residues: NULL (that stage is skipped), or batch*K
+ * complex128 (NORMING_CONSTANTS, RESIDUES), or batch*2K (BOTH): signal b's norming constants at b*2K + [0, K_out[b])
+ * and its residues at b*2K + K + [0, K_out[b]) -- the residues start at the capacity K, not at the count, so that a
+ * device consumer addresses them without reading the count back; unused entries are NaN.  d_K_out: batch FNFT_UINT
+ * (64-bit) on the device.  T: host, shared by the batch.  FNFT_EC_INVALID_ARGUMENT, before anything is enqueued, for a
+ * NULL plan, d_q, d_guesses, d_bound_states, d_K_out or T, or T[0] >= T[1].  Asynchronous on `stream` (a hipStream_t,
+ * NULL = default stream). */
+FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
+                                       const void *d_guesses, void *d_bound_states, void *d_normconsts_or_residues,
+                                       void *d_K_out, void *stream);
+/* Waits for `stream`.  status[b] (may be NULL): what fnft_nsev returns for signal b alone -- 0, or the drop-in's
+ * subroutine-failure form of the code: -FNFT_EC_DIV_BY_ZERO where a' = 0 exactly, -FNFT_EC_OTHER for the step-size
+ * check of 2SPLIT2_MODAL, -FNFT_EC_INVALID_ARGUMENT for an empty bounding box (a signal with NaN samples).  K_out[b]
+ * (may be NULL): the count of the last call's d_K_out.  Returns 0, or the status of the lowest-index failing signal; a
+ * failing signal leaves the others unchanged and its own outputs unspecified. */
+FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *stream, FNFT_INT *status,
+                                       FNFT_UINT *K_out);
+
 /* ======================================================================================== */
-/* 4. Korteweg-de Vries equation, vanishing boundaries (include/fnft_kdvv.h)                  */
+/* 4.Korteweg-de Vries equation, vanishing boundaries (include/fnft_kdvv.h)                  */
 /* ======================================================================================== */
 
 /* include/fnft_kdv_discretization_t.h:96-122 (same ordinals) */
