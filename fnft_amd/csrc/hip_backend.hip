@@ -837,6 +837,97 @@ static FNFT_INT inv_subroutine(const char *func, int line, FNFT_INT ec)
     return fnft_amd__raise(-std::abs((int)ec), func, line, "Subroutine failure.");
 }
 
+// continuous-spectrum options of a plan with a continuous part: *cstype (0 rho, 1 b(xi), 2 B(tau)), or the error,
+// raised in the name of the public entry `func`
+static FNFT_INT inv_cstype(const char *func, const fnft_nsev_inverse_opts_t &o, FNFT_UINT D, FNFT_UINT M, int *cstype)
+{
+    *cstype = 0;
+    switch (o.contspec_type) {
+    case fnft_nsev_inverse_cstype_REFLECTION_COEFFICIENT:
+        if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT
+            && o.contspec_inversion_method != fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_REFL_COEFF)
+            return inv_subroutine(func, __LINE__, seam_invalid(func, __LINE__, "opts->contspec_inversion_method"));
+        break;
+    case fnft_nsev_inverse_cstype_B_OF_XI:
+        *cstype = 1;
+        break;
+    case fnft_nsev_inverse_cstype_B_OF_TAU:
+        *cstype = 2;
+        if (M != D) return inv_subroutine(func, __LINE__, seam_invalid(func, __LINE__, "M"));
+        if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT)
+            return inv_subroutine(func, __LINE__, seam_invalid(func, __LINE__, "opts->contspec_inversion_method"));
+        break;
+    default:
+        return seam_invalid(func, __LINE__, "opts->contspec_type");
+    }
+    if (*cstype != 0 && o.oversampling_factor == 0)                   // fnft__poly_specfact.c:37-38
+        return inv_subroutine(func, __LINE__, FNFT_EC_INVALID_ARGUMENT);
+    return FNFT_SUCCESS;
+}
+
+// the plan and its workspace, once the options are accepted.  K = 0: no discrete part
+static FNFT_INT inv_plan_new(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
+                             const fnft_nsev_inverse_opts_t &o, int device, int cstype, FNFT_UINT K, int ds_mode,
+                             int residues)
+{
+    DeviceGuard dg(device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    fnft_amd_inverse_plan *P = new (std::nothrow) fnft_amd_inverse_plan();
+    if (!P) return FNFT_EC_NOMEM;
+    P->device = device;
+    P->cstype = cstype;
+    P->K = K;
+    P->inv = new (std::nothrow) NftInverseBatch<HipBackend>(
+        P->be, (size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
+        o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0, (size_t)K, ds_mode, residues);
+    if (!P->inv) { delete P; return FNFT_EC_NOMEM; }
+    const int rc = P->inv->init();
+    if (rc != NFT_SUCCESS || P->be.failed) {
+        (void)P->be.sync();
+        delete P->inv;
+        delete P;
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = P;
+    return FNFT_SUCCESS;
+}
+
+// one call on a plan: its lock, its device, its stream.  last_stream != NULL (the *_device entries): the stream is also
+// the one destroy waits for, and the failure flag starts clear
+struct PlanCall {
+    std::lock_guard<std::mutex> lk;
+    DeviceGuard dg;
+    const bool ok;
+    PlanCall(std::mutex &m, int device, HipBackend &be, hipStream_t *last_stream, void *stream)
+        : lk(m), dg(device), ok(dg.ok)
+    {
+        if (!ok) return;
+        be.stream = (hipStream_t)stream;
+        if (last_stream) {
+            *last_stream = (hipStream_t)stream;
+            be.failed = false;
+        }
+    }
+};
+
+// destroy: the pool hands the plan's blocks to the next allocation, so nothing it enqueued may still be writing them
+static void plan_quiesce(hipStream_t last_stream)
+{
+    if (last_stream) (void)hipStreamSynchronize(last_stream);
+    (void)hipDeviceSynchronize();
+}
+
+// step size and phase factor exactly as the host driver forms them (fnft_nsev_inverse_host.c)
+static FNFT_REAL inv_phase_factor(const fnft_amd_inverse_plan &plan, const FNFT_REAL *T, FNFT_REAL *eps_t_out)
+{
+    const size_t D = plan.inv->D;
+    const FNFT_REAL eps_t = (T[1] - T[0]) / (D - 1);
+    const FNFT_REAL pf_rho = -2.0 * (T[1] + eps_t * 0.5) + eps_t;
+    const FNFT_REAL pf_b = -eps_t * D - (T[1] + eps_t * 0.5) - (T[0] - eps_t * 0.5) + eps_t;
+    *eps_t_out = eps_t;
+    return plan.cstype == 0 ? pf_rho : pf_b;
+}
+
 FNFT_INT fnft_amd_inverse_plan_create(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
                                       fnft_nsev_inverse_opts_t const *opts, int device)
 {
@@ -853,45 +944,9 @@ FNFT_INT fnft_amd_inverse_plan_create(fnft_amd_inverse_plan_t **plan, FNFT_UINT 
         return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
                                "Not yet implemented (batched inverse: iterative or seed-potential method).");
     int cstype = 0;
-    switch (o.contspec_type) {
-    case fnft_nsev_inverse_cstype_REFLECTION_COEFFICIENT:
-        if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT
-            && o.contspec_inversion_method != fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_REFL_COEFF)
-            return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
-        break;
-    case fnft_nsev_inverse_cstype_B_OF_XI:
-        cstype = 1;
-        break;
-    case fnft_nsev_inverse_cstype_B_OF_TAU:
-        cstype = 2;
-        if (M != D) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "M"));
-        if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT)
-            return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
-        break;
-    default:
-        return seam_invalid(__func__, __LINE__, "opts->contspec_type");
-    }
-    if (cstype != 0 && o.oversampling_factor == 0)                    // fnft__poly_specfact.c:37-38
-        return inv_subroutine(__func__, __LINE__, FNFT_EC_INVALID_ARGUMENT);
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    fnft_amd_inverse_plan *P = new (std::nothrow) fnft_amd_inverse_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->device = device;
-    P->cstype = cstype;
-    P->inv = new (std::nothrow) NftInverseBatch<HipBackend>(
-        P->be, (size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
-        o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0);
-    if (!P->inv) { delete P; return FNFT_EC_NOMEM; }
-    const int rc = P->inv->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        (void)P->be.sync();
-        delete P->inv;
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
-    }
-    *plan = P;
-    return FNFT_SUCCESS;
+    const FNFT_INT rc = inv_cstype(__func__, o, D, M, &cstype);
+    if (rc != FNFT_SUCCESS) return rc;
+    return inv_plan_new(plan, D, M, batch, o, device, cstype, 0, 0, 0);
 }
 
 void fnft_amd_inverse_plan_destroy(fnft_amd_inverse_plan_t *plan)
@@ -899,9 +954,7 @@ void fnft_amd_inverse_plan_destroy(fnft_amd_inverse_plan_t *plan)
     if (!plan) return;
     {
         DeviceGuard dg(plan->device);
-        // the pool hands these blocks to the next allocation: nothing the plan enqueued may still be writing them
-        if (plan->last_stream) (void)hipStreamSynchronize(plan->last_stream);
-        (void)hipDeviceSynchronize();
+        plan_quiesce(plan->last_stream);
         delete plan->inv;
         plan->be.destroy_events();
     }
@@ -925,20 +978,11 @@ FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void 
     SEAM_CHECK(XI == NULL && plan->cstype != 2, XI);
     if (plan->cstype == 2 && T[0] != -T[1])                           // :643-647
         return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "T"));
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    NftInverseBatch<HipBackend> &inv = *plan->inv;
-    plan->be.stream = (hipStream_t)stream;
-    plan->last_stream = (hipStream_t)stream;
-    plan->be.failed = false;
-    // step size and phase factors exactly as the host driver forms them (fnft_nsev_inverse_host.c)
-    const size_t D = inv.D;
-    const FNFT_REAL eps_t = (T[1] - T[0]) / (D - 1);
-    const FNFT_REAL pf_rho = -2.0 * (T[1] + eps_t * 0.5) + eps_t;
-    const FNFT_REAL pf_b = -eps_t * D - (T[1] + eps_t * 0.5) - (T[0] - eps_t * 0.5) + eps_t;
-    const int rc = inv.run((const cplx *)d_contspec, XI, (cplx *)d_q, eps_t, (int)kappa,
-                           plan->cstype == 0 ? pf_rho : pf_b);
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    FNFT_REAL eps_t;
+    const FNFT_REAL pf = inv_phase_factor(*plan, T, &eps_t);
+    const int rc = plan->inv->run((const cplx *)d_contspec, XI, (cplx *)d_q, eps_t, (int)kappa, pf);
     if (plan->be.failed) return FNFT_EC_OTHER;
     return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
 }
@@ -971,52 +1015,15 @@ FNFT_INT fnft_amd_inverse_plan_create_discrete(fnft_amd_inverse_plan_t **plan, F
     const bool seed = o.contspec_inversion_method == fnft_nsev_inverse_csmethod_USE_SEED_POTENTIAL_INSTEAD;
     int cstype = 0;
     if (M > 0) {
-        switch (o.contspec_type) {
-        case fnft_nsev_inverse_cstype_REFLECTION_COEFFICIENT:
-            if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT
-                && o.contspec_inversion_method != fnft_nsev_inverse_csmethod_TFMATRIX_CONTAINS_REFL_COEFF)
-                return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
-            break;
-        case fnft_nsev_inverse_cstype_B_OF_XI:
-            cstype = 1;
-            break;
-        case fnft_nsev_inverse_cstype_B_OF_TAU:
-            cstype = 2;
-            if (M != D) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "M"));
-            if (o.contspec_inversion_method != fnft_nsev_inverse_csmethod_DEFAULT)
-                return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
-            break;
-        default:
-            return seam_invalid(__func__, __LINE__, "opts->contspec_type");
-        }
-        if (cstype != 0 && o.oversampling_factor == 0)                // fnft__poly_specfact.c:37-38
-            return inv_subroutine(__func__, __LINE__, FNFT_EC_INVALID_ARGUMENT);
+        const FNFT_INT rc = inv_cstype(__func__, o, D, M, &cstype);
+        if (rc != FNFT_SUCCESS) return rc;
         // b(xi) with the seed method: the drop-in computes the continuous part and then refuses the combination
         // (:890-891); here before anything runs
         if (seed) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_inversion_method"));
     }
     const int ds_mode = (M == 0 && !seed) ? 0 : 1;
     const int residues = o.discspec_type == fnft_nsev_inverse_dstype_RESIDUES ? 1 : 0;
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    fnft_amd_inverse_plan *P = new (std::nothrow) fnft_amd_inverse_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->device = device;
-    P->cstype = cstype;
-    P->K = K;
-    P->inv = new (std::nothrow) NftInverseBatch<HipBackend>(
-        P->be, (size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
-        o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0, (size_t)K, ds_mode, residues);
-    if (!P->inv) { delete P; return FNFT_EC_NOMEM; }
-    const int rc = P->inv->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        (void)P->be.sync();
-        delete P->inv;
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
-    }
-    *plan = P;
-    return FNFT_SUCCESS;
+    return inv_plan_new(plan, D, M, batch, o, device, cstype, K, ds_mode, residues);
 }
 
 FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, const void *d_contspec,
@@ -1040,20 +1047,12 @@ FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, co
     SEAM_CHECK(M > 0 && XI == NULL && plan->cstype != 2, XI);
     if (M > 0 && plan->cstype == 2 && T[0] != -T[1])                  // :643-647
         return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "T"));
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    NftInverseBatch<HipBackend> &inv = *plan->inv;
-    plan->be.stream = (hipStream_t)stream;
-    plan->last_stream = (hipStream_t)stream;
-    plan->be.failed = false;
-    const size_t D = inv.D;
-    const FNFT_REAL eps_t = (T[1] - T[0]) / (D - 1);
-    const FNFT_REAL pf_rho = -2.0 * (T[1] + eps_t * 0.5) + eps_t;
-    const FNFT_REAL pf_b = -eps_t * D - (T[1] + eps_t * 0.5) - (T[0] - eps_t * 0.5) + eps_t;
-    const int rc = inv.run_discrete((const cplx *)d_contspec, XI, (const cplx *)d_bound_states,
-                                    (const cplx *)d_normconsts_or_residues, (cplx *)d_q, T, eps_t, (int)kappa,
-                                    plan->cstype == 0 ? pf_rho : pf_b);
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    FNFT_REAL eps_t;
+    const FNFT_REAL pf = inv_phase_factor(*plan, T, &eps_t);
+    const int rc = plan->inv->run_discrete((const cplx *)d_contspec, XI, (const cplx *)d_bound_states,
+                                           (const cplx *)d_normconsts_or_residues, (cplx *)d_q, T, eps_t, (int)kappa, pf);
     if (plan->be.failed) return FNFT_EC_OTHER;
     return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
 }
@@ -1061,10 +1060,8 @@ FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, co
 FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *stream, FNFT_INT *status, int *warnings)
 {
     SEAM_CHECK(!plan, plan);
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    plan->be.stream = (hipStream_t)stream;
+    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
     const int rc = plan->inv->read_status(plan->st);
     if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
     FNFT_INT first = FNFT_SUCCESS;
@@ -1154,9 +1151,7 @@ void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
     if (!plan) return;
     {
         DeviceGuard dg(plan->device);
-        // the pool hands these blocks to the next allocation: nothing the plan enqueued may still be writing them
-        if (plan->last_stream) (void)hipStreamSynchronize(plan->last_stream);
-        (void)hipDeviceSynchronize();
+        plan_quiesce(plan->last_stream);
         plan->ds->destroy();
         delete plan->ds;
         plan->be.destroy_events();
@@ -1179,13 +1174,9 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
     SEAM_CHECK(!d_guesses, guesses);
     SEAM_CHECK(!d_bound_states, bound_states);
     SEAM_CHECK(!d_K_out, K_out);
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    plan->be.stream = (hipStream_t)stream;
-    plan->last_stream = (hipStream_t)stream;
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
     plan->last_K = (const unsigned long long *)d_K_out;
-    plan->be.failed = false;
     const int rc = plan->ds->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
                                  (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
     if (plan->be.failed) return FNFT_EC_OTHER;
@@ -1196,10 +1187,8 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
                                        FNFT_UINT *K_out)
 {
     SEAM_CHECK(!plan, plan);
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    plan->be.stream = (hipStream_t)stream;
+    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
     const int rc = plan->ds->read(plan->st, plan->kout, plan->last_K);
     if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
     FNFT_INT first = FNFT_SUCCESS;
@@ -1444,9 +1433,7 @@ FNFT_INT fnft__nse_scatter_matrix(const FNFT_UINT D, FNFT_COMPLEX const *const q
     HipBackend be;
     BsParams B;
     std::memset(&B, 0, sizeof(B));
-    size_t L = (D + 16383) / 16384;
-    if (L < 16) L = 16;
-    if (L % 2) L++;
+    const size_t L = nft_bs_chunk_len(D);
     const size_t nchunk = (D + L - 1) / L;
     const size_t w = derivative_flag ? 8 : 4;
     cplx *dq = (cplx *)be.alloc(D * sizeof(cplx)), *dr = r ? (cplx *)be.alloc(D * sizeof(cplx)) : nullptr;

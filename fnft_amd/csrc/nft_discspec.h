@@ -52,6 +52,38 @@ struct NftDsOpts {
     int richardson;
 };
 
+// ---- launches of the chunk-parallel scatterer (body_bs_*), shared with the inverse transform ---------------------
+// samples per chunk: at least 16 and even (a multiple of ups), about 16384 chunks on a long signal (one lane each in
+// the chunk kernels; the combine kernels take them in runs of nchunk/256 per lane)
+inline size_t nft_bs_chunk_len(size_t n)
+{
+    size_t l = (n + 16383) / 16384;
+    if (l < 16) l = 16;
+    if (l % 2) l++;
+    return l;
+}
+// chunk maps {M, M'}, then a, a' and phi at the chunk starts.  gx = ceil(nchunk/64), gy = eigenvalues (x signals)
+template <class BE> void nft_bs_forward(BE &be, int gx, int gy, const BsParams &B)
+{
+    be.template run<KBsChunk<false>>(gx, gy, B);
+    be.template run<KBsCombine<false>>(gy, 1, B);
+}
+// phi and psi at every grid point of a signal with D samples over T, step eps_t (src/fnft_nsev_inverse.c:908-1007): two
+// half steps per sample interval = the scatterer on the half-step signal B.q = (q0, q1, q1, q2, q2, ...) of 2 (D - 1)
+// samples with step eps_t/2.  Sets the step and time fields of B; the caller has set the rest.
+template <class BE> void nft_bs_eigenfunctions(BE &be, int gx, int gy, BsParams B, const double *T, double eps_t)
+{
+    B.ups = 2; B.lscale = 1.0;
+    B.eps = 0.5 * eps_t;
+    B.T0 = T[0] + 0.5 * B.eps;                 // the combine kernels start at T0 - eps/2 and end at T1 + eps/2
+    B.T1 = T[1] - 0.5 * B.eps;
+    nft_bs_forward(be, gx, gy, B);
+    be.template run<KBsPhi>(gx, gy, B);
+    be.template run<KBsChunk<true>>(gx, gy, B);
+    be.template run<KBsCombine<true>>(gy, 1, B);
+    be.template run<KBsPsi>(gx, gy, B);
+}
+
 template <class BE> class NftDiscSpec {
 public:
     typedef std::complex<double> cd;
@@ -158,11 +190,7 @@ public:
         B.lscale = (P.ups == 2) ? 0.5 : 1.0;
         B.T0 = P.T[0]; B.T1 = P.T[1]; B.eps = P.eps_t;
         B.K = (int)K;
-        // chunks of >= 16 samples, about 16384 of them on a long signal (one lane each in the chunk kernels;
-        // the combine kernels take them in runs of nchunk/256 per lane)
-        size_t L = (P.Deff + 16383) / 16384;
-        if (L < 16) L = 16;
-        if (L % 2) L++;
+        const size_t L = nft_bs_chunk_len(P.Deff);
         B.L = (int)L;
         B.nchunk = (int)((P.Deff + L - 1) / L);
         const size_t Dg = P.Deff / (size_t)P.ups;
@@ -184,8 +212,7 @@ public:
             B.lam = d_lam; B.cm = cm; B.bnd = bnd; B.bndp = bndp; B.PHI = PHI; B.best = best;
             B.a = d_out; B.aprime = d_out + K; B.b = d_out + 2 * K;
             const int gx = (B.nchunk + 63) / 64;
-            be.template run<KBsChunk<false>>(gx, (int)K, B);
-            be.template run<KBsCombine<false>>((int)K, 1, B);
+            nft_bs_forward(be, gx, (int)K, B);
             if (!skip_b) {
                 be.template run<KBsPhi>(gx, (int)K, B);
                 be.template run<KBsChunk<true>>(gx, (int)K, B);

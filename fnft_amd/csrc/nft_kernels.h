@@ -2331,7 +2331,7 @@ FA_DEV void c_cosh_sinh(cplx w, cplx &ch, cplx &sh)
     sh = cmake(shr * c, chr * s);
 }
 
-struct BsStep { cplx u00, u01, u10, u11; };
+struct BsStep { cplx u[4]; };   // row-major 2x2, the layout of every stored map
 // step matrix for step size e (e < 0: inverse step); V (derivative) only when WITH_D
 template <bool WITH_D> FA_DEV void bs_step_r(cplx q, cplx r, cplx l, double e, BsStep &U, BsStep &V);
 template <bool WITH_D> FA_DEV void bs_step(cplx q, cplx l, double e, BsStep &U, BsStep &V)
@@ -2348,21 +2348,133 @@ template <bool WITH_D> FA_DEV void bs_step_r(cplx q, cplx r, cplx l, double e, B
     const cplx sh = nz ? c_div(shk, k) : cmake(e, 0.0);
     const cplx il = cmake(-l.y, l.x);   // i*l
     const cplx ilsh = il * sh;
-    U.u00 = ch - ilsh;
-    U.u01 = q * sh;
-    U.u10 = r * sh;
-    U.u11 = ch + ilsh;
+    U.u[0] = ch - ilsh;
+    U.u[1] = q * sh;
+    U.u[2] = r * sh;
+    U.u[3] = ch + ilsh;
     if (WITH_D) {
         const cplx g = c_div(ch * e - sh, ks);           // -(d sh/dl)/l
         const cplx ish = cmake(-sh.y, sh.x);
         const cplx t = (l * sh) * e;                     // e l sh
         const cplx ill_g = (il * l) * g;                 // i l^2 g
-        V.u00 = cmake(0.0, 0.0) - t - ish + ill_g;
-        V.u11 = cmake(0.0, 0.0) - t + ish - ill_g;
+        V.u[0] = cmake(0.0, 0.0) - t - ish + ill_g;
+        V.u[3] = cmake(0.0, 0.0) - t + ish - ill_g;
         const cplx lg = l * g;
-        V.u01 = cmake(0.0, 0.0) - q * lg;
-        V.u10 = cmake(0.0, 0.0) - r * lg;
+        V.u[1] = cmake(0.0, 0.0) - q * lg;
+        V.u[2] = cmake(0.0, 0.0) - r * lg;
     }
+}
+
+// ---- the 2x2 map arithmetic of every scatterer kernel -------------------------------------------------------------
+// A map is cplx[4] (row-major), a map with its lambda-derivative ("jet") cplx[8] = {M[4], M'[4]}, a vector cplx[2] and
+// a vector with its derivative cplx[4] = {p1, p2, d1, d2}.  The helpers take pointers, so the same spelling serves a
+// register array, an LDS slot and a global slot; each formula is written out here and nowhere else.
+FA_DEV double bs_inf() { return 1.0e308 * 10.0; }
+
+FA_DEV void bs_map_identity(cplx *M)
+{
+    M[0] = cmake(1.0, 0.0); M[1] = cmake(0.0, 0.0); M[2] = M[1]; M[3] = M[0];
+}
+FA_DEV void bs_jet_identity(cplx *M)
+{
+    bs_map_identity(M);
+    M[4] = M[1]; M[5] = M[1]; M[6] = M[1]; M[7] = M[1];
+}
+// M <- m M
+FA_DEV void bs_map_mul(const cplx *m, cplx *M)
+{
+    const cplx f0 = m[0] * M[0] + m[1] * M[2], f1 = m[0] * M[1] + m[1] * M[3];
+    const cplx f2 = m[2] * M[0] + m[3] * M[2], f3 = m[2] * M[1] + m[3] * M[3];
+    M[0] = f0; M[1] = f1; M[2] = f2; M[3] = f3;
+}
+// M' <- md M + m M',  M <- m M
+FA_DEV void bs_jet_mul(const cplx *m, const cplx *md, cplx *M)
+{
+    const cplx e0 = md[0] * M[0] + md[1] * M[2] + m[0] * M[4] + m[1] * M[6];
+    const cplx e1 = md[0] * M[1] + md[1] * M[3] + m[0] * M[5] + m[1] * M[7];
+    const cplx e2 = md[2] * M[0] + md[3] * M[2] + m[2] * M[4] + m[3] * M[6];
+    const cplx e3 = md[2] * M[1] + md[3] * M[3] + m[2] * M[5] + m[3] * M[7];
+    bs_map_mul(m, M);
+    M[4] = e0; M[5] = e1; M[6] = e2; M[7] = e3;
+}
+// jet push: one more step (U, V = dU/dlambda) on the left of {M, M'}
+FA_DEV void bs_jet_push(const BsStep &U, const BsStep &V, cplx *M) { bs_jet_mul(U.u, V.u, M); }
+// jet compose: (M, M') <- (m M, m' M + m M'), m = {m[4], m'[4]} the later span
+FA_DEV void bs_jet_compose(const cplx *m, cplx *M) { bs_jet_mul(m, m + 4, M); }
+// p <- m p
+FA_DEV void bs_map_apply(const cplx *m, cplx *p)
+{
+    const cplx t1 = m[0] * p[0] + m[1] * p[1], t2 = m[2] * p[0] + m[3] * p[1];
+    p[0] = t1; p[1] = t2;
+}
+// (p, d) <- (m p, m' p + m d) on v = {p1, p2, d1, d2}
+FA_DEV void bs_jet_apply(const cplx *m, cplx *v)
+{
+    const cplx n1 = m[4] * v[0] + m[5] * v[1] + m[0] * v[2] + m[1] * v[3];
+    const cplx n2 = m[6] * v[0] + m[7] * v[1] + m[2] * v[2] + m[3] * v[3];
+    bs_map_apply(m, v);
+    v[2] = n1; v[3] = n2;
+}
+
+// boundary data of the grid T0 .. T1 with step eps: phi = (e^{-i lam ta}, 0) and its lambda-derivative at
+// ta = T0 - eps/2, the phase e^{i lam tb} at tb = T1 + eps/2 (psi = (0, e^{i lam tb}) there), and a, a' from phi1 and
+// phi1' at tb (fnft__nse_scatter_bound_states.c:627-628)
+FA_DEV void bs_start(cplx lc, double T0, double eps, cplx *v)
+{
+    double s, c;
+    const double ta = T0 - eps * 0.5;
+    fa_sincos(-lc.x * ta, &s, &c);
+    v[0] = cmake(c, s) * exp(lc.y * ta);
+    v[1] = cmake(0.0, 0.0);
+    v[2] = v[0] * cmake(0.0, -ta);
+    v[3] = cmake(0.0, 0.0);
+}
+FA_DEV cplx bs_end_phase(cplx lc, double T1, double eps)
+{
+    double s, c;
+    const double tb = T1 + eps * 0.5;
+    fa_sincos(lc.x * tb, &s, &c);
+    return cmake(c, s) * exp(-lc.y * tb);
+}
+FA_DEV void bs_a_aprime(cplx p1, cplx d1, cplx ph, double T1, double eps, double lscale, cplx &av, cplx &apv)
+{
+    const double tb = T1 + eps * 0.5;
+    av = p1 * ph;
+    apv = (d1 * ph + cmake(0.0, tb) * av) * lscale;
+}
+
+// run i of `len` items out of N: [a, b), empty past the end
+template <class I> FA_DEV void bs_run_bounds(I i, I len, I N, I &a, I &b)
+{
+    a = (i * len < N) ? i * len : N;
+    b = (a + len < N) ? a + len : N;
+}
+
+// {M, M'} of samples n0 .. n1-1 at l, forward steps.  r = NULL: r = -kappa conj(q)
+FA_DEV void bs_run_jet(const cplx *q, const cplx *r, int kappa, long long n0, long long n1, cplx l, double eps, cplx *o)
+{
+    cplx M[8];
+    bs_jet_identity(M);
+    BsStep U, V;
+    for (long long n = n0; n < n1; n++) {
+        const cplx qn = q[n];
+        const cplx rn = r ? r[n] : (kappa < 0 ? cmake(qn.x, -qn.y) : cmake(-qn.x, qn.y));   // else: bs_step's r
+        bs_step_r<true>(qn, rn, l, eps, U, V);
+        bs_jet_push(U, V, M);
+    }
+    for (int i = 0; i < 8; i++) o[i] = M[i];
+}
+// the map of samples n1-1 .. n0 at l, inverse steps, last sample first
+FA_DEV void bs_run_map_back(const cplx *q, long long n0, long long n1, cplx l, double eps, cplx *o)
+{
+    cplx M[4];
+    bs_map_identity(M);
+    BsStep U, V;
+    for (long long n = n1; n-- > n0;) {
+        bs_step<false>(q[n], l, -eps, U, V);
+        bs_map_mul(U.u, M);
+    }
+    for (int i = 0; i < 4; i++) o[i] = M[i];
 }
 
 // chunk matrices.  grid.x = nchunk lanes / THREADS, grid.y = K.  BACKWARD: inverse steps, last sample first
@@ -2374,37 +2486,11 @@ template <bool BACKWARD> FA_DEV void body_bs_chunk(const BsParams &P)
     const int e = FA_BID_Y - (int)sg * P.K;
     const cplx *q = P.q + sg * P.sq;
     const cplx l = P.lam[sg * P.slam + e] * P.lscale;
-    const long long n0 = (long long)c * P.L;
-    const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
-    cplx m00 = cmake(1.0, 0.0), m01 = cmake(0.0, 0.0), m10 = m01, m11 = m00;
-    cplx d00 = m01, d01 = m01, d10 = m01, d11 = m01;
-    BsStep U, V;
-    if (!BACKWARD) {
-        for (long long n = n0; n < n1; n++) {
-            const cplx qn = q[n];
-            const cplx rn = P.r ? P.r[n] : (P.kappa < 0 ? cmake(qn.x, -qn.y) : cmake(-qn.x, qn.y));
-            bs_step_r<true>(qn, rn, l, P.eps, U, V);
-            // M' <- V M + U M',  M <- U M
-            const cplx e00 = V.u00 * m00 + V.u01 * m10 + U.u00 * d00 + U.u01 * d10;
-            const cplx e01 = V.u00 * m01 + V.u01 * m11 + U.u00 * d01 + U.u01 * d11;
-            const cplx e10 = V.u10 * m00 + V.u11 * m10 + U.u10 * d00 + U.u11 * d10;
-            const cplx e11 = V.u10 * m01 + V.u11 * m11 + U.u10 * d01 + U.u11 * d11;
-            d00 = e00; d01 = e01; d10 = e10; d11 = e11;
-            const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
-            const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
-            m00 = f00; m01 = f01; m10 = f10; m11 = f11;
-        }
-    } else {
-        for (long long n = n1; n-- > n0;) {
-            bs_step<false>(q[n], l, -P.eps, U, V);
-            const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
-            const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
-            m00 = f00; m01 = f01; m10 = f10; m11 = f11;
-        }
-    }
+    long long n0, n1;
+    bs_run_bounds<long long>(c, P.L, P.D, n0, n1);
     cplx *o = P.cm + sg * P.scm + ((size_t)e * P.nchunk + c) * 8;
-    o[0] = m00; o[1] = m01; o[2] = m10; o[3] = m11;
-    if (!BACKWARD) { o[4] = d00; o[5] = d01; o[6] = d10; o[7] = d11; }
+    if (!BACKWARD) bs_run_jet(q, P.r, P.kappa, n0, n1, l, P.eps, o);
+    else bs_run_map_back(q, n0, n1, l, P.eps, o);
 }
 
 // one workgroup per eigenvalue: string the chunks together.  Forward: a, a' (:627-628) and phi at the
@@ -2422,97 +2508,56 @@ template <bool BACKWARD> FA_DEV void body_bs_combine(const BsParams &P)
     const long long sg = FA_BID / P.K;
     const int e = FA_BID - (int)sg * P.K;
     const cplx lc = P.lam[sg * P.slam + e];
-    const double bc = 0.5;
     const cplx *cmv = P.cm + sg * P.scm + (size_t)e * P.nchunk * 8;
-    const int G = (P.nchunk + nl - 1) / nl;
-    const int k0 = (t * G < P.nchunk) ? t * G : P.nchunk;
-    const int k1 = (k0 + G < P.nchunk) ? k0 + G : P.nchunk;
-    const cplx one = cmake(1.0, 0.0), zero = cmake(0.0, 0.0);
+    cplx *bnd = (BACKWARD ? P.bndp : P.bnd) + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
+    int k0, k1;
+    bs_run_bounds<int>(t, (P.nchunk + nl - 1) / nl, P.nchunk, k0, k1);
     {   // stage 1
-        cplx m0 = one, m1 = zero, m2 = zero, m3 = one, d0 = zero, d1 = zero, d2 = zero, d3 = zero;
-        if (!BACKWARD) {
-            for (int k = k0; k < k1; k++) {
-                const cplx *m = cmv + (size_t)k * 8;
-                // D <- m' M + m D,  M <- m M
-                const cplx e0 = m[4] * m0 + m[5] * m2 + m[0] * d0 + m[1] * d2;
-                const cplx e1 = m[4] * m1 + m[5] * m3 + m[0] * d1 + m[1] * d3;
-                const cplx e2 = m[6] * m0 + m[7] * m2 + m[2] * d0 + m[3] * d2;
-                const cplx e3 = m[6] * m1 + m[7] * m3 + m[2] * d1 + m[3] * d3;
-                d0 = e0; d1 = e1; d2 = e2; d3 = e3;
-                const cplx f0 = m[0] * m0 + m[1] * m2, f1 = m[0] * m1 + m[1] * m3;
-                const cplx f2 = m[2] * m0 + m[3] * m2, f3 = m[2] * m1 + m[3] * m3;
-                m0 = f0; m1 = f1; m2 = f2; m3 = f3;
-            }
-        } else {
-            for (int k = k1; k-- > k0;) {
-                const cplx *m = cmv + (size_t)k * 8;
-                const cplx f0 = m[0] * m0 + m[1] * m2, f1 = m[0] * m1 + m[1] * m3;
-                const cplx f2 = m[2] * m0 + m[3] * m2, f3 = m[2] * m1 + m[3] * m3;
-                m0 = f0; m1 = f1; m2 = f2; m3 = f3;
-            }
-        }
+        cplx M[8];
+        bs_jet_identity(M);
+        if (!BACKWARD) for (int k = k0; k < k1; k++) bs_jet_compose(cmv + (size_t)k * 8, M);
+        else for (int k = k1; k-- > k0;) bs_map_mul(cmv + (size_t)k * 8, M);
         cplx *o = gm + (size_t)t * 8;
-        o[0] = m0; o[1] = m1; o[2] = m2; o[3] = m3; o[4] = d0; o[5] = d1; o[6] = d2; o[7] = d3;
+        for (int i = 0; i < 8; i++) o[i] = M[i];
     }
     FA_SYNC();
-    double s, c;
-    const double tb = P.T1 + P.eps * bc;            // e^{i lam tb}
-    fa_sincos(lc.x * tb, &s, &c);
-    const cplx ph = cmake(c, s) * exp(-lc.y * tb);
+    const cplx ph = bs_end_phase(lc, P.T1, P.eps);
     if (t == 0) {   // stage 2
         if (!BACKWARD) {
-            const double ta = P.T0 - P.eps * bc;        // e^{-i lam ta}
-            fa_sincos(-lc.x * ta, &s, &c);
-            cplx p1 = cmake(c, s) * exp(lc.y * ta), p2 = zero;
-            cplx d1 = p1 * cmake(0.0, -ta), d2 = zero;
+            cplx v[4];
+            bs_start(lc, P.T0, P.eps, v);
             for (int g = 0; g < nl; g++) {
-                cplx *v = gv + (size_t)g * 4;
-                v[0] = p1; v[1] = p2; v[2] = d1; v[3] = d2;
-                const cplx *m = gm + (size_t)g * 8;
-                const cplx n1 = m[4] * p1 + m[5] * p2 + m[0] * d1 + m[1] * d2;
-                const cplx n2 = m[6] * p1 + m[7] * p2 + m[2] * d1 + m[3] * d2;
-                d1 = n1; d2 = n2;
-                const cplx t1 = m[0] * p1 + m[1] * p2, t2 = m[2] * p1 + m[3] * p2;
-                p1 = t1; p2 = t2;
+                cplx *o = gv + (size_t)g * 4;
+                o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+                bs_jet_apply(gm + (size_t)g * 8, v);
             }
-            cplx *bnd = P.bnd + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
-            bnd[2 * P.nchunk] = p1; bnd[2 * P.nchunk + 1] = p2;
-            const cplx av = p1 * ph;
+            bnd[2 * P.nchunk] = v[0]; bnd[2 * P.nchunk + 1] = v[1];
+            cplx av, apv;
+            bs_a_aprime(v[0], v[2], ph, P.T1, P.eps, P.lscale, av, apv);
             P.a[sg * P.sab + e] = av;
-            P.aprime[sg * P.sab + e] = (d1 * ph + cmake(0.0, tb) * av) * P.lscale;
+            P.aprime[sg * P.sab + e] = apv;
         } else {
-            cplx s1 = zero, s2 = ph;
+            cplx s[2] = {cmake(0.0, 0.0), ph};
             for (int g = nl; g-- > 0;) {
-                cplx *v = gv + (size_t)g * 4;
-                v[0] = s1; v[1] = s2;
-                const cplx *m = gm + (size_t)g * 8;
-                const cplx t1 = m[0] * s1 + m[1] * s2, t2 = m[2] * s1 + m[3] * s2;
-                s1 = t1; s2 = t2;
+                cplx *o = gv + (size_t)g * 4;
+                o[0] = s[0]; o[1] = s[1];
+                bs_map_apply(gm + (size_t)g * 8, s);
             }
-            cplx *bnd = P.bndp + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
-            bnd[0] = s1; bnd[1] = s2;
+            bnd[0] = s[0]; bnd[1] = s[1];
         }
     }
     FA_SYNC();
     // stage 3
-    const cplx *v = gv + (size_t)t * 4;
+    cplx p[2] = {gv[(size_t)t * 4], gv[(size_t)t * 4 + 1]};
     if (!BACKWARD) {
-        cplx p1 = v[0], p2 = v[1];
-        cplx *bnd = P.bnd + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
         for (int k = k0; k < k1; k++) {
-            bnd[2 * k] = p1; bnd[2 * k + 1] = p2;
-            const cplx *m = cmv + (size_t)k * 8;
-            const cplx t1 = m[0] * p1 + m[1] * p2, t2 = m[2] * p1 + m[3] * p2;
-            p1 = t1; p2 = t2;
+            bnd[2 * k] = p[0]; bnd[2 * k + 1] = p[1];
+            bs_map_apply(cmv + (size_t)k * 8, p);
         }
     } else {
-        cplx s1 = v[0], s2 = v[1];
-        cplx *bnd = P.bndp + sg * P.sbnd + (size_t)e * (P.nchunk + 1) * 2;
         for (int k = k1; k-- > k0;) {
-            bnd[2 * (k + 1)] = s1; bnd[2 * (k + 1) + 1] = s2;
-            const cplx *m = cmv + (size_t)k * 8;
-            const cplx t1 = m[0] * s1 + m[1] * s2, t2 = m[2] * s1 + m[3] * s2;
-            s1 = t1; s2 = t2;
+            bnd[2 * (k + 1)] = p[0]; bnd[2 * (k + 1) + 1] = p[1];
+            bs_map_apply(cmv + (size_t)k * 8, p);
         }
     }
 }
@@ -2526,34 +2571,23 @@ FA_DEV void body_bs_matrix(const BsParams &P)
     cplx *gm = (cplx *)FA_LDS_PTR;             // lanes x 8
     const int e = FA_BID, t = FA_TID, nl = FA_BDIM;
     const cplx *cmv = P.cm + (size_t)e * P.nchunk * 8;
-    const int G = (P.nchunk + nl - 1) / nl;
-    const int k0 = (t * G < P.nchunk) ? t * G : P.nchunk;
-    const int k1 = (k0 + G < P.nchunk) ? k0 + G : P.nchunk;
-    const cplx one = cmake(1.0, 0.0), zero = cmake(0.0, 0.0);
-    cplx m0 = one, m1 = zero, m2 = zero, m3 = one, d0 = zero, d1 = zero, d2 = zero, d3 = zero;
-    auto apply = [&](const cplx *m) {   // (M, D) <- (m M, m' M + m D)
-        const cplx e0 = m[4] * m0 + m[5] * m2 + m[0] * d0 + m[1] * d2;
-        const cplx e1 = m[4] * m1 + m[5] * m3 + m[0] * d1 + m[1] * d3;
-        const cplx e2 = m[6] * m0 + m[7] * m2 + m[2] * d0 + m[3] * d2;
-        const cplx e3 = m[6] * m1 + m[7] * m3 + m[2] * d1 + m[3] * d3;
-        d0 = e0; d1 = e1; d2 = e2; d3 = e3;
-        const cplx f0 = m[0] * m0 + m[1] * m2, f1 = m[0] * m1 + m[1] * m3;
-        const cplx f2 = m[2] * m0 + m[3] * m2, f3 = m[2] * m1 + m[3] * m3;
-        m0 = f0; m1 = f1; m2 = f2; m3 = f3;
-    };
-    for (int k = k0; k < k1; k++) apply(cmv + (size_t)k * 8);
+    int k0, k1;
+    bs_run_bounds<int>(t, (P.nchunk + nl - 1) / nl, P.nchunk, k0, k1);
+    cplx M[8];
+    bs_jet_identity(M);
+    for (int k = k0; k < k1; k++) bs_jet_compose(cmv + (size_t)k * 8, M);
     cplx *o = gm + (size_t)t * 8;
-    o[0] = m0; o[1] = m1; o[2] = m2; o[3] = m3; o[4] = d0; o[5] = d1; o[6] = d2; o[7] = d3;
+    for (int i = 0; i < 8; i++) o[i] = M[i];
     FA_SYNC();
     if (t != 0) return;
-    m0 = one; m1 = zero; m2 = zero; m3 = one; d0 = zero; d1 = zero; d2 = zero; d3 = zero;
-    for (int g = 0; g < nl; g++) apply(gm + (size_t)g * 8);
+    bs_jet_identity(M);
+    for (int g = 0; g < nl; g++) bs_jet_compose(gm + (size_t)g * 8, M);
     const int w = P.with_deriv ? 8 : 4;
     cplx *res = P.smat + (size_t)e * w;
-    res[0] = m0; res[1] = m1; res[2] = m2; res[3] = m3;
+    res[0] = M[0]; res[1] = M[1]; res[2] = M[2]; res[3] = M[3];
     if (P.with_deriv) {
         const double s = P.lscale;       // chain rule of the scaled spectral parameter (1 for BO)
-        res[4] = d0 * s; res[5] = d1 * s; res[6] = d2 * s; res[7] = d3 * s;
+        res[4] = M[4] * s; res[5] = M[5] * s; res[6] = M[6] * s; res[7] = M[7] * s;
     }
 }
 
@@ -2566,21 +2600,20 @@ FA_DEV void body_bs_phi(const BsParams &P)
     const int e = FA_BID_Y - (int)sg * P.K;
     const cplx *q = P.q + sg * P.sq;
     const cplx l = P.lam[sg * P.slam + e] * P.lscale;
-    const long long n0 = (long long)c * P.L;
-    const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
+    long long n0, n1;
+    bs_run_bounds<long long>(c, P.L, P.D, n0, n1);
     const long long Dg = P.D / P.ups;
     const cplx *bnd = P.bnd + sg * P.sbnd + ((size_t)e * (P.nchunk + 1) + c) * 2;
-    cplx p1 = bnd[0], p2 = bnd[1];
+    cplx p[2] = {bnd[0], bnd[1]};
     cplx *PHI = P.PHI + sg * P.sphi + (size_t)e * (Dg + 1) * 2;
-    if (c == 0) { PHI[0] = p1; PHI[1] = p2; }
+    if (c == 0) { PHI[0] = p[0]; PHI[1] = p[1]; }
     BsStep U, V;
     for (long long n = n0; n < n1; n++) {
         bs_step<false>(q[n], l, P.eps, U, V);
-        const cplx t1 = U.u00 * p1 + U.u01 * p2, t2 = U.u10 * p1 + U.u11 * p2;
-        p1 = t1; p2 = t2;
+        bs_map_apply(U.u, p);
         if ((n + 1) % P.ups == 0) {
             const long long g = (n + 1) / P.ups;
-            PHI[2 * g] = p1; PHI[2 * g + 1] = p2;
+            PHI[2 * g] = p[0]; PHI[2 * g + 1] = p[1];
         }
     }
 }
@@ -2595,21 +2628,20 @@ FA_DEV void body_bs_psi(const BsParams &P)
     const int e = FA_BID_Y - (int)sg * P.K;
     const cplx *q = P.q + sg * P.sq;
     const cplx l = P.lam[sg * P.slam + e] * P.lscale;
-    const long long n0 = (long long)c * P.L;
-    const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
+    long long n0, n1;
+    bs_run_bounds<long long>(c, P.L, P.D, n0, n1);
     const long long Dg = P.D / P.ups;
     const cplx *bnd = P.bndp + sg * P.sbnd + ((size_t)e * (P.nchunk + 1) + (c + 1)) * 2;
-    cplx s1 = bnd[0], s2 = bnd[1];
+    cplx s[2] = {bnd[0], bnd[1]};
     cplx *PSI = P.PSI + sg * P.sphi + (size_t)e * (Dg + 1) * 2;
-    if (n1 == P.D) { PSI[2 * Dg] = s1; PSI[2 * Dg + 1] = s2; }
+    if (n1 == P.D) { PSI[2 * Dg] = s[0]; PSI[2 * Dg + 1] = s[1]; }
     BsStep U, V;
     for (long long n = n1; n-- > n0;) {
         bs_step<false>(q[n], l, -P.eps, U, V);
-        const cplx t1 = U.u00 * s1 + U.u01 * s2, t2 = U.u10 * s1 + U.u11 * s2;
-        s1 = t1; s2 = t2;
+        bs_map_apply(U.u, s);
         if (n % P.ups == 0) {
             const long long g = n / P.ups;
-            PSI[2 * g] = s1; PSI[2 * g + 1] = s2;
+            PSI[2 * g] = s[0]; PSI[2 * g + 1] = s[1];
         }
     }
 }
@@ -2620,39 +2652,64 @@ FA_DEV double bs_metric(cplx p1, cplx p2, cplx s1, cplx s2)
     return fabs(0.5 * log(sqrt(cnorm2(r))));
 }
 
-// psi backwards through the chunk; the chunk owns its grid points except its first one (chunk 0
-// owns point 0 too); best point of the chunk by the metric, first one on ties in ascending order
+// psi backwards through the run of samples n0 .. n1-1 from s = psi at its end.  The run owns its grid points except
+// its first one (own_first: that one too); best point of the run by the metric, first one on ties in ascending
+// order, and b = phi1/psi1 there.  phi of the run's grid point j (the one before sample n0 + ups*j) is at PHI[j * stride].
+FA_DEV void bs_best_point(const cplx *q, long long n0, long long n1, int ups, cplx l, double eps, cplx *s,
+                          const cplx *PHI, long long stride, bool own_first, double &best, cplx &bval)
+{
+    best = bs_inf();
+    bval = cmake(0.0, 0.0);
+    long long j = (n1 - n0) / ups;
+    auto look = [&]() {
+        const cplx f1 = PHI[j * stride], f2 = PHI[j * stride + 1];
+        const double m = bs_metric(f1, f2, s[0], s[1]);
+        if (m <= best) { best = m; bval = c_div(f1, s[0]); }
+    };
+    look();
+    BsStep U, V;
+    for (long long n = n1; n-- > n0;) {
+        bs_step<false>(q[n], l, -eps, U, V);
+        bs_map_apply(U.u, s);
+        if (n % ups == 0) {
+            j--;
+            if (n > n0 || own_first) look();
+        }
+    }
+}
+
+// (metric, index) of every lane through LDS: lm[0], li[0] = the smallest metric and its index, the lower index on
+// ties.  Every lane of the workgroup calls it; nl lanes, a power of two
+FA_DEV void bs_argmin(double *lm, int *li, int t, int nl, double best, int bi)
+{
+    lm[t] = best;
+    li[t] = bi;
+    FA_SYNC();
+    for (int h = nl / 2; h >= 1; h >>= 1) {
+        if (t < h) {
+            const double mo = lm[t + h];
+            const int io = li[t + h];
+            if (mo < lm[t] || (mo == lm[t] && io < li[t])) { lm[t] = mo; li[t] = io; }
+        }
+        FA_SYNC();
+    }
+}
+
+// the chunk's best point (bs_best_point; chunk 0 owns point 0 too)
 FA_DEV void body_bs_metric(const BsParams &P)
 {
     const int c = FA_BID * FA_BDIM + FA_TID, e = FA_BID_Y;
     if (c >= P.nchunk) return;
     const cplx l = P.lam[e] * P.lscale;
-    const long long n0 = (long long)c * P.L;
-    const long long n1 = (n0 + P.L < P.D) ? n0 + P.L : P.D;
+    long long n0, n1;
+    bs_run_bounds<long long>(c, P.L, P.D, n0, n1);
     const long long Dg = P.D / P.ups;
     const cplx *bnd = P.bndp + ((size_t)e * (P.nchunk + 1) + (c + 1)) * 2;
-    cplx s1 = bnd[0], s2 = bnd[1];
-    const cplx *PHI = P.PHI + (size_t)e * (Dg + 1) * 2;
-    double best = 1.0e308 * 10.0;   // +inf
-    cplx bval = cmake(0.0, 0.0);
-    {
-        const long long g = n1 / P.ups;
-        const double m = bs_metric(PHI[2 * g], PHI[2 * g + 1], s1, s2);
-        if (m <= best) { best = m; bval = c_div(PHI[2 * g], s1); }
-    }
-    BsStep U, V;
-    for (long long n = n1; n-- > n0;) {
-        bs_step<false>(P.q[n], l, -P.eps, U, V);
-        const cplx t1 = U.u00 * s1 + U.u01 * s2, t2 = U.u10 * s1 + U.u11 * s2;
-        s1 = t1; s2 = t2;
-        if (n % P.ups == 0) {
-            const long long g = n / P.ups;
-            if (n > n0 || c == 0) {
-                const double m = bs_metric(PHI[2 * g], PHI[2 * g + 1], s1, s2);
-                if (m <= best) { best = m; bval = c_div(PHI[2 * g], s1); }
-            }
-        }
-    }
+    cplx s[2] = {bnd[0], bnd[1]};
+    const cplx *PHI = P.PHI + ((size_t)e * (Dg + 1) + (size_t)c * (P.L / P.ups)) * 2;   // the chunk's first grid point
+    double best;
+    cplx bval;
+    bs_best_point(P.q, n0, n1, P.ups, l, P.eps, s, PHI, 2, c == 0, best, bval);
     cplx *o = P.best + ((size_t)e * P.nchunk + c) * 2;
     o[0] = cmake(best, 0.0);
     o[1] = bval;
@@ -2666,21 +2723,11 @@ FA_DEV void body_bs_pick(const BsParams &P)
     int *li = (int *)(lm + FA_BDIM);            // lanes: its chunk
     const int e = FA_BID, t = FA_TID, nl = FA_BDIM;
     const cplx *bv = P.best + (size_t)e * P.nchunk * 2;
-    double best = 1.0e308 * 10.0;
+    double best = bs_inf();
     int bi = 0x7fffffff;
     for (int c = t; c < P.nchunk; c += nl)
         if (bv[2 * c].x < best) { best = bv[2 * c].x; bi = c; }
-    lm[t] = best;
-    li[t] = bi;
-    FA_SYNC();
-    for (int h = nl / 2; h >= 1; h >>= 1) {
-        if (t < h) {
-            const double mo = lm[t + h];
-            const int io = li[t + h];
-            if (mo < lm[t] || (mo == lm[t] && io < li[t])) { lm[t] = mo; li[t] = io; }
-        }
-        FA_SYNC();
-    }
+    bs_argmin(lm, li, t, nl, best, bi);
     if (t == 0) P.b[e] = (li[0] != 0x7fffffff) ? bv[2 * li[0] + 1] : cmake(0.0, 0.0);
 }
 
@@ -2690,12 +2737,13 @@ FA_DEV void body_bs_pick(const BsParams &P)
 // step; here one workgroup owns one (signal, eigenvalue) pair from the first guess to the result:
 //   body_ds_box     per signal: the bounding box of the filter (trapezoid rule of l2norm2) and the MODAL step check
 //   body_ds_newton  per (signal, eigenvalue): every Newton iteration on chip -- lane t composes the map {M, M'} of its
-//                   run of samples (the step arithmetic of body_bs_chunk), the 256 maps are combined pairwise through
-//                   LDS in 8 rounds, lane 0 forms a, a', applies the reference's update and stopping rule
+//                   run of samples (bs_run_jet, as the chunk kernel does), the 256 maps are combined pairwise through
+//                   LDS in 8 rounds (bs_jet_compose), lane 0 forms a, a', applies the reference's update and stopping rule
 //                   (src/fnft_nsev.c:971-1038) and broadcasts the new lambda or the stop
 //   body_ds_filter  per signal: box test and in-order merge (NftDiscSpec::filter_merge), K_out, NaN tails
 //   body_ds_norm    per (signal, surviving eigenvalue): a', phi forward and psi backward over the runs, the grid point
-//                   with the smallest bs_metric (first on ties), b = phi1/psi1 there, residue b/a'
+//                   with the smallest bs_metric (bs_best_point per run, bs_argmin over the runs), b = phi1/psi1 there,
+//                   residue b/a'
 // LDSQ: the signal's samples are staged in LDS once per workgroup (up to kDsLdsSamples of them); longer signals are
 // read from global memory / L2 by the same body.
 // ---------------------------------------------------------------------------------------------
@@ -2724,42 +2772,16 @@ struct DsBatchParams {
     long long sphi;           //   point j of lane t at (j*kDsLanes + t)*2
 };
 
-FA_DEV double ds_inf() { return 1.0e308 * 10.0; }
-
-// {M, M'} of samples n0 .. n1-1 at l (forward steps; body_bs_chunk's loop for r = -conj(q))
-FA_DEV void ds_run_map(const cplx *q, long long n0, long long n1, cplx l, double eps, cplx *o)
-{
-    cplx m00 = cmake(1.0, 0.0), m01 = cmake(0.0, 0.0), m10 = m01, m11 = m00;
-    cplx d00 = m01, d01 = m01, d10 = m01, d11 = m01;
-    BsStep U, V;
-    for (long long n = n0; n < n1; n++) {
-        bs_step<true>(q[n], l, eps, U, V);
-        const cplx e00 = V.u00 * m00 + V.u01 * m10 + U.u00 * d00 + U.u01 * d10;
-        const cplx e01 = V.u00 * m01 + V.u01 * m11 + U.u00 * d01 + U.u01 * d11;
-        const cplx e10 = V.u10 * m00 + V.u11 * m10 + U.u10 * d00 + U.u11 * d10;
-        const cplx e11 = V.u10 * m01 + V.u11 * m11 + U.u10 * d01 + U.u11 * d11;
-        d00 = e00; d01 = e01; d10 = e10; d11 = e11;
-        const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
-        const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
-        m00 = f00; m01 = f01; m10 = f10; m11 = f11;
-    }
-    o[0] = m00; o[1] = m01; o[2] = m10; o[3] = m11; o[4] = d00; o[5] = d01; o[6] = d10; o[7] = d11;
-}
-
-// a and a' from the map of the whole signal (stage 2 of body_bs_combine: start vector, end phase)
+// a and a' from the map {M, M'} of the whole signal.  Not bs_jet_apply: phi2 = phi2' = 0 at the start and only phi1, phi1'
+// are needed at the end, so the products with m[1], m[5] and the second row are left out
 FA_DEV void ds_a_aprime(const DsBatchParams &P, const cplx *m, cplx lc, cplx &av, cplx &apv)
 {
-    double s, c;
-    const double ta = P.T0 - P.eps * 0.5, tb = P.T1 + P.eps * 0.5;
-    fa_sincos(-lc.x * ta, &s, &c);
-    const cplx p1 = cmake(c, s) * exp(lc.y * ta);      // e^{-i lam ta}
-    const cplx d1 = p1 * cmake(0.0, -ta);
-    fa_sincos(lc.x * tb, &s, &c);
-    const cplx ph = cmake(c, s) * exp(-lc.y * tb);     // e^{i lam tb}
-    const cplx pe = m[0] * p1;
-    const cplx de = m[4] * p1 + m[0] * d1;
-    av = pe * ph;
-    apv = (de * ph + cmake(0.0, tb) * av) * P.lscale;
+    cplx v[4];
+    bs_start(lc, P.T0, P.eps, v);
+    const cplx ph = bs_end_phase(lc, P.T1, P.eps);
+    const cplx pe = m[0] * v[0];
+    const cplx de = m[4] * v[0] + m[0] * v[2];
+    bs_a_aprime(pe, de, ph, P.T1, P.eps, P.lscale, av, apv);
 }
 
 // one workgroup per signal
@@ -2789,7 +2811,7 @@ FA_DEV void body_ds_box(const DsBatchParams &P)
     }
     if (t != 0) return;
     double *box = P.box + 4 * b;
-    const double inf = ds_inf();
+    const double inf = bs_inf();
     box[0] = -inf; box[1] = inf; box[2] = -inf; box[3] = inf;
     if (P.bsfilt == 1) box[2] = 0.0;
     else if (P.bsfilt == 2) {
@@ -2815,8 +2837,8 @@ template <bool LDSQ> FA_DEV void body_ds_newton(const DsBatchParams &P)
         for (long long i = t; i < P.D; i += kDsLanes) ql[i] = q[i];
         q = ql;
     }
-    const long long n0 = ((long long)t * P.G < P.D) ? (long long)t * P.G : P.D;
-    const long long n1 = (n0 + P.G < P.D) ? n0 + P.G : P.D;
+    long long n0, n1;
+    bs_run_bounds<long long>(t, P.G, P.D, n0, n1);
     const double *box = P.box + 4 * b;
     if (t == 0) {
         ctl[0] = P.guess[w];
@@ -2827,20 +2849,10 @@ template <bool LDSQ> FA_DEV void body_ds_newton(const DsBatchParams &P)
     int it = 0;
     while (ctl[1].x != 0.0) {
         const cplx lc = ctl[0];
-        ds_run_map(q, n0, n1, lc * P.lscale, P.eps, gm + (size_t)t * 8);
+        bs_run_jet(q, nullptr, 1, n0, n1, lc * P.lscale, P.eps, gm + (size_t)t * 8);
         FA_SYNC();
         for (int s = 1; s < kDsLanes; s <<= 1) {
-            if ((t & (2 * s - 1)) == 0) {   // (M, D) <- (m M, m' M + m D), m the later span
-                cplx *M = gm + (size_t)t * 8;
-                const cplx *m = gm + (size_t)(t + s) * 8;
-                const cplx e0 = m[4] * M[0] + m[5] * M[2] + m[0] * M[4] + m[1] * M[6];
-                const cplx e1 = m[4] * M[1] + m[5] * M[3] + m[0] * M[5] + m[1] * M[7];
-                const cplx e2 = m[6] * M[0] + m[7] * M[2] + m[2] * M[4] + m[3] * M[6];
-                const cplx e3 = m[6] * M[1] + m[7] * M[3] + m[2] * M[5] + m[3] * M[7];
-                const cplx f0 = m[0] * M[0] + m[1] * M[2], f1 = m[0] * M[1] + m[1] * M[3];
-                const cplx f2 = m[2] * M[0] + m[3] * M[2], f3 = m[2] * M[1] + m[3] * M[3];
-                M[0] = f0; M[1] = f1; M[2] = f2; M[3] = f3; M[4] = e0; M[5] = e1; M[6] = e2; M[7] = e3;
-            }
+            if ((t & (2 * s - 1)) == 0) bs_jet_compose(gm + (size_t)(t + s) * 8, gm + (size_t)t * 8);   // the later span
             FA_SYNC();
         }
         if (t == 0) {
@@ -2930,111 +2942,58 @@ template <bool LDSQ> FA_DEV void body_ds_norm(const DsBatchParams &P)
         q = ql;
         FA_SYNC();
     }
-    const long long n0 = ((long long)t * P.G < P.D) ? (long long)t * P.G : P.D;
-    const long long n1 = (n0 + P.G < P.D) ? n0 + P.G : P.D;
+    long long n0, n1;
+    bs_run_bounds<long long>(t, P.G, P.D, n0, n1);
     const cplx lc = P.bs[b * P.K + e];
     const cplx l = lc * P.lscale;
     const cplx zero = cmake(0.0, 0.0);
-    double s, c;
-    ds_run_map(q, n0, n1, l, P.eps, gm + (size_t)t * 8);
+    bs_run_jet(q, nullptr, 1, n0, n1, l, P.eps, gm + (size_t)t * 8);
     FA_SYNC();
     if (t == 0) {   // phi at the start of every run; a' from the end
-        const double ta = P.T0 - P.eps * 0.5, tb = P.T1 + P.eps * 0.5;
-        fa_sincos(-lc.x * ta, &s, &c);
-        cplx p1 = cmake(c, s) * exp(lc.y * ta), p2 = zero;
-        cplx d1 = p1 * cmake(0.0, -ta), d2 = zero;
+        cplx v[4], av;
+        bs_start(lc, P.T0, P.eps, v);
         for (int g = 0; g < kDsLanes; g++) {
-            gv[2 * g] = p1; gv[2 * g + 1] = p2;
-            const cplx *m = gm + (size_t)g * 8;
-            const cplx n1v = m[4] * p1 + m[5] * p2 + m[0] * d1 + m[1] * d2;
-            const cplx n2v = m[6] * p1 + m[7] * p2 + m[2] * d1 + m[3] * d2;
-            d1 = n1v; d2 = n2v;
-            const cplx t1 = m[0] * p1 + m[1] * p2, t2 = m[2] * p1 + m[3] * p2;
-            p1 = t1; p2 = t2;
+            gv[2 * g] = v[0]; gv[2 * g + 1] = v[1];
+            bs_jet_apply(gm + (size_t)g * 8, v);
         }
-        fa_sincos(lc.x * tb, &s, &c);
-        const cplx ph = cmake(c, s) * exp(-lc.y * tb);
-        const cplx av = p1 * ph;
-        ctl[0] = (d1 * ph + cmake(0.0, tb) * av) * P.lscale;
+        bs_a_aprime(v[0], v[2], bs_end_phase(lc, P.T1, P.eps), P.T1, P.eps, P.lscale, av, ctl[0]);
     }
     FA_SYNC();
     cplx *PHI = P.phi + w * P.sphi + (size_t)t * 2;   // point j of this lane at PHI[j * kDsLanes * 2]
-    BsStep U, V;
     {   // phi at the grid points of the run (point j follows sample n0 + ups*j - 1); the run's backward map
-        cplx p1 = gv[2 * t], p2 = gv[2 * t + 1];
+        cplx p[2] = {gv[2 * t], gv[2 * t + 1]};
         long long j = 0;
-        PHI[0] = p1; PHI[1] = p2;
+        PHI[0] = p[0]; PHI[1] = p[1];
+        BsStep U, V;
         for (long long n = n0; n < n1; n++) {
             bs_step<false>(q[n], l, P.eps, U, V);
-            const cplx t1 = U.u00 * p1 + U.u01 * p2, t2 = U.u10 * p1 + U.u11 * p2;
-            p1 = t1; p2 = t2;
+            bs_map_apply(U.u, p);
             if ((n + 1) % P.ups == 0) {
                 j++;
-                PHI[j * kDsLanes * 2] = p1; PHI[j * kDsLanes * 2 + 1] = p2;
+                PHI[j * kDsLanes * 2] = p[0]; PHI[j * kDsLanes * 2 + 1] = p[1];
             }
         }
-        cplx m00 = cmake(1.0, 0.0), m01 = zero, m10 = zero, m11 = m00;
-        for (long long n = n1; n-- > n0;) {
-            bs_step<false>(q[n], l, -P.eps, U, V);
-            const cplx f00 = U.u00 * m00 + U.u01 * m10, f01 = U.u00 * m01 + U.u01 * m11;
-            const cplx f10 = U.u10 * m00 + U.u11 * m10, f11 = U.u10 * m01 + U.u11 * m11;
-            m00 = f00; m01 = f01; m10 = f10; m11 = f11;
-        }
-        cplx *o = gm + (size_t)t * 4;
-        o[0] = m00; o[1] = m01; o[2] = m10; o[3] = m11;
+        bs_run_map_back(q, n0, n1, l, P.eps, gm + (size_t)t * 4);
     }
     FA_SYNC();
     if (t == 0) {   // psi at the end of every run, from (0, e^{i lam tb}) at the end of the grid
-        const double tb = P.T1 + P.eps * 0.5;
-        fa_sincos(lc.x * tb, &s, &c);
-        cplx s1 = zero, s2 = cmake(c, s) * exp(-lc.y * tb);
+        cplx s[2] = {zero, bs_end_phase(lc, P.T1, P.eps)};
         for (int g = kDsLanes; g-- > 0;) {
-            gv[2 * g] = s1; gv[2 * g + 1] = s2;
-            const cplx *m = gm + (size_t)g * 4;
-            const cplx t1 = m[0] * s1 + m[1] * s2, t2 = m[2] * s1 + m[3] * s2;
-            s1 = t1; s2 = t2;
+            gv[2 * g] = s[0]; gv[2 * g + 1] = s[1];
+            bs_map_apply(gm + (size_t)g * 4, s);
         }
     }
     FA_SYNC();
-    // psi backwards through the run; the run owns its grid points except its first one (run 0 owns point 0 too);
-    // its best point by the metric, the first one on ties
-    double best = ds_inf();
+    // the run's best point (bs_best_point; run 0 owns point 0 too)
+    double best = bs_inf();
     cplx bval = zero;
     if (n1 > n0) {
-        cplx s1 = gv[2 * t], s2 = gv[2 * t + 1];
-        long long j = (n1 - n0) / P.ups;
-        {
-            const cplx f1 = PHI[j * kDsLanes * 2], f2 = PHI[j * kDsLanes * 2 + 1];
-            const double m = bs_metric(f1, f2, s1, s2);
-            if (m <= best) { best = m; bval = c_div(f1, s1); }
-        }
-        for (long long n = n1; n-- > n0;) {
-            bs_step<false>(q[n], l, -P.eps, U, V);
-            const cplx t1 = U.u00 * s1 + U.u01 * s2, t2 = U.u10 * s1 + U.u11 * s2;
-            s1 = t1; s2 = t2;
-            if (n % P.ups == 0) {
-                j--;
-                if (n > n0 || t == 0) {
-                    const cplx f1 = PHI[j * kDsLanes * 2], f2 = PHI[j * kDsLanes * 2 + 1];
-                    const double m = bs_metric(f1, f2, s1, s2);
-                    if (m <= best) { best = m; bval = c_div(f1, s1); }
-                }
-            }
-        }
+        cplx s[2] = {gv[2 * t], gv[2 * t + 1]};
+        bs_best_point(q, n0, n1, P.ups, l, P.eps, s, PHI, (long long)kDsLanes * 2, t == 0, best, bval);
     }
     double *lm = (double *)gm;                // lanes: best metric
     int *li = (int *)(lm + kDsLanes);         // lanes: its lane (grid order)
-    lm[t] = best;
-    li[t] = (best < ds_inf()) ? t : 0x7fffffff;
-    FA_SYNC();
-    for (int h = kDsLanes / 2; h >= 1; h >>= 1) {
-        if (t < h) {
-            const double mo = lm[t + h];
-            const int io = li[t + h];
-            if (mo < lm[t] || (mo == lm[t] && io < li[t])) { lm[t] = mo; li[t] = io; }
-        }
-        FA_SYNC();
-    }
+    bs_argmin(lm, li, t, kDsLanes, best, (best < bs_inf()) ? t : 0x7fffffff);
     const int win = li[0];
     if (t != ((win != 0x7fffffff) ? win : 0)) return;
     if (win == 0x7fffffff) bval = zero;

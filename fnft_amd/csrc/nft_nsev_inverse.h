@@ -468,14 +468,11 @@ public:
         if (rc == NFT_SUCCESS && mode == 0) {
             be.template run<KInvSolitons>((int)((D + 255) / 256), 1, P);
         } else if (rc == NFT_SUCCESS) {
-            // eigenfunctions of the seed, :908-1007: two half steps per sample interval = the chunk-parallel
-            // scatterer of the discrete spectrum on the signal q' = (q0, q1, q1, q2, q2, ...) with step eps_t/2
+            // eigenfunctions of the seed on the half-step signal (nft_bs_eigenfunctions)
             const size_t D2 = 2 * (D - 1);
             BsParams B;
             std::memset(&B, 0, sizeof(B));
-            size_t L = (D2 + 16383) / 16384;
-            if (L < 16) L = 16;
-            if (L % 2) L++;
+            const size_t L = nft_bs_chunk_len(D2);
             const size_t nchunk = (D2 + L - 1) / L;
             ok = pl.alloc(dq2, D2) && pl.alloc(cm, K * nchunk * 8) && pl.alloc(bnd, K * (nchunk + 1) * 2)
                  && pl.alloc(bndp, K * (nchunk + 1) * 2) && pl.alloc(PHI, K * D * 2) && pl.alloc(PSI, K * D * 2)
@@ -487,20 +484,11 @@ public:
                 std::memset(&O, 0, sizeof(O));
                 O.op = INV_DOUBLE_Q; O.n = (long long)D2; O.a = dq; O.out = dq2;
                 be.template run<KInvOp>((int)((D2 + 255) / 256), 1, O);
-                B.q = dq2; B.D = (long long)D2; B.ups = 2; B.lscale = 1.0;
-                B.eps = 0.5 * eps_t;
-                B.T0 = T[0] + 0.5 * B.eps;                 // the combine kernels start at T0 - eps/2 and end at T1 + eps/2
-                B.T1 = T[1] - 0.5 * B.eps;
+                B.q = dq2; B.D = (long long)D2;
                 B.K = (int)K; B.lam = dbs; B.L = (int)L; B.nchunk = (int)nchunk;
                 B.cm = cm; B.bnd = bnd; B.bndp = bndp; B.PHI = PHI; B.PSI = PSI;
                 B.a = dout; B.aprime = dout + K; B.b = dout + 2 * K;
-                const int gx = (int)((nchunk + 63) / 64);
-                be.template run<KBsChunk<false>>(gx, (int)K, B);
-                be.template run<KBsCombine<false>>((int)K, 1, B);
-                be.template run<KBsPhi>(gx, (int)K, B);
-                be.template run<KBsChunk<true>>(gx, (int)K, B);
-                be.template run<KBsCombine<true>>((int)K, 1, B);
-                be.template run<KBsPsi>(gx, (int)K, B);
+                nft_bs_eigenfunctions(be, (int)((nchunk + 63) / 64), (int)K, B, T, eps_t);
                 P.PHI = PHI; P.PSI = PSI;
                 be.template run<KInvCdt>((int)((D + 255) / 256), 1, P);
             }
@@ -549,25 +537,17 @@ public:
         bytes += b;
         return true;
     }
-    // chunks of the chunk-parallel scatterer over n samples (NftDiscSpec::scatter, NftInverseDev::add_discrete)
-    static size_t chunk_len(size_t n)
-    {
-        size_t l = (n + 16383) / 16384;
-        if (l < 16) l = 16;
-        if (l % 2) l++;
-        return l;
-    }
     size_t work_per_signal() const { return (mode ? 2 : 1) * K * D; }
     int init()
     {
         bool ok = alloc(bs, B * K) && alloc(nc, B * K) && alloc(work, B * work_per_signal());
         if (mode == 1) {
             const size_t D2 = 2 * (D - 1);
-            L = chunk_len(D2);
+            L = nft_bs_chunk_len(D2);
             nchunk = (D2 + L - 1) / L;
             ncm = nchunk;
             if (residues && seed_cs) {          // a(lambda_k) of the seed, BO scheme on its D samples
-                Lr = chunk_len(D);
+                Lr = nft_bs_chunk_len(D);
                 nchunk_r = (D + Lr - 1) / Lr;
                 ncm = std::max(ncm, nchunk_r);
             }
@@ -630,9 +610,7 @@ public:
                 P.D = (long long)D; P.ups = 1; P.lscale = 1.0;
                 P.T0 = T[0]; P.T1 = T1; P.eps = (T1 - T[0]) / (double)(D - 1);
                 P.L = (int)Lr; P.nchunk = (int)nchunk_r;
-                const int gx = (int)((nchunk_r + 63) / 64);
-                be.template run<KBsChunk<false>>(gx, (int)(ns * K), P);
-                be.template run<KBsCombine<false>>((int)(ns * K), 1, P);
+                nft_bs_forward(be, (int)((nchunk_r + 63) / 64), (int)(ns * K), P);
             }
             InvDsPrepParams R;
             std::memset(&R, 0, sizeof(R));
@@ -645,8 +623,7 @@ public:
                 be.template run<KInvSolitons>(gx, (int)std::min(kMaxGridY, B - s0), ds_params(d_q, T[0], eps_t, zc, s0));
             return;
         }
-        // eigenfunctions of the seed, :908-1007 (NftInverseDev::add_discrete): the chunk-parallel scatterer on the
-        // half-step signal q' = (q0, q1, q1, q2, q2, ...) with step eps_t/2
+        // eigenfunctions of the seed on the half-step signal (nft_bs_eigenfunctions)
         const size_t D2 = 2 * (D - 1);
         for (size_t s0 = 0; s0 < B; s0 += kMaxGridY) {
             InvOpParams O;
@@ -658,18 +635,9 @@ public:
         for (size_t s0 = 0; s0 < B; s0 += per_y) {
             const size_t ns = std::min(per_y, B - s0);
             BsParams P = bs_params(q2, D2, s0);
-            P.D = (long long)D2; P.ups = 2; P.lscale = 1.0;
-            P.eps = 0.5 * eps_t;
-            P.T0 = T[0] + 0.5 * P.eps;                 // the combine kernels start at T0 - eps/2 and end at T1 + eps/2
-            P.T1 = T[1] - 0.5 * P.eps;
+            P.D = (long long)D2;
             P.L = (int)L; P.nchunk = (int)nchunk;
-            const int gxc = (int)((nchunk + 63) / 64), gy = (int)(ns * K);
-            be.template run<KBsChunk<false>>(gxc, gy, P);
-            be.template run<KBsCombine<false>>(gy, 1, P);
-            be.template run<KBsPhi>(gxc, gy, P);
-            be.template run<KBsChunk<true>>(gxc, gy, P);
-            be.template run<KBsCombine<true>>(gy, 1, P);
-            be.template run<KBsPsi>(gxc, gy, P);
+            nft_bs_eigenfunctions(be, (int)((nchunk + 63) / 64), (int)(ns * K), P, T, eps_t);
         }
         for (size_t s0 = 0; s0 < B; s0 += kMaxGridY)
             be.template run<KInvCdt>(gx, (int)std::min(kMaxGridY, B - s0), ds_params(d_q, T[0], eps_t, zc, s0));

@@ -1,4 +1,5 @@
-"""Registers of the batched discrete-spectrum kernels (KDsBox, KDsNewton, KDsFilter, KDsNorm), without a GPU: fp64 2x2
+"""Registers of the batched discrete-spectrum kernels (KDsBox, KDsNewton, KDsFilter, KDsNorm) and of the chunk-parallel
+scatterer (KBs*), without a GPU: fp64 2x2
 complex products with derivative maps are register-heavy, and a spilled register is a round trip to HBM inside every
 Newton iteration.  None may spill a VGPR or use scratch.  The figures are the code-object metadata of the built
 library, read with the ROCm LLVM tools like test_kernel_resources_cpu.py does; the test prints them."""
@@ -19,6 +20,16 @@ KERNELS = {
     "_Z12kernel_entryI9KDsFilterEvNT_6ParamsE": "KDsFilter",
     "_Z12kernel_entryI7KDsNormILb0EEEvNT_6ParamsE": "KDsNorm<false>",
     "_Z12kernel_entryI7KDsNormILb1EEEvNT_6ParamsE": "KDsNorm<true>",
+    # the chunk-parallel scatterer the batched kernels share their 2x2 map arithmetic with
+    "_Z12kernel_entryI8KBsChunkILb0EEEvNT_6ParamsE": "KBsChunk<false>",
+    "_Z12kernel_entryI8KBsChunkILb1EEEvNT_6ParamsE": "KBsChunk<true>",
+    "_Z12kernel_entryI10KBsCombineILb0EEEvNT_6ParamsE": "KBsCombine<false>",
+    "_Z12kernel_entryI10KBsCombineILb1EEEvNT_6ParamsE": "KBsCombine<true>",
+    "_Z12kernel_entryI9KBsMatrixEvNT_6ParamsE": "KBsMatrix",
+    "_Z12kernel_entryI6KBsPhiEvNT_6ParamsE": "KBsPhi",
+    "_Z12kernel_entryI6KBsPsiEvNT_6ParamsE": "KBsPsi",
+    "_Z12kernel_entryI9KBsMetricEvNT_6ParamsE": "KBsMetric",
+    "_Z12kernel_entryI7KBsPickEvNT_6ParamsE": "KBsPick",
 }
 KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
         "group_segment_fixed_size")
