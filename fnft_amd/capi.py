@@ -108,6 +108,8 @@ EXPORTED = [
     "fnft_amd_nsev_inverse_discrete_device",
     "fnft_amd_discspec_plan_create", "fnft_amd_discspec_plan_destroy", "fnft_amd_discspec_plan_workspace_bytes",
     "fnft_amd_nsev_discspec_device", "fnft_amd_discspec_plan_finish",
+    "fnft_amd_slow_plan_create", "fnft_amd_slow_plan_destroy", "fnft_amd_slow_plan_workspace_bytes",
+    "fnft_amd_nsev_slow_device", "fnft_amd_slow_plan_finish", "fnft_amd_slow_plan_chunks",
 ]
 
 _lib = None
@@ -264,6 +266,18 @@ def load(path=None):
     L.fnft_amd_nsev_discspec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.fnft_amd_discspec_plan_finish.restype = i32
     L.fnft_amd_discspec_plan_finish.argtypes = [vp, vp, vp, vp]
+    L.fnft_amd_slow_plan_create.restype = i32
+    L.fnft_amd_slow_plan_create.argtypes = [C.POINTER(vp), sz, sz, sz, C.POINTER(NsevOpts), C.c_int]
+    L.fnft_amd_slow_plan_destroy.restype = None
+    L.fnft_amd_slow_plan_destroy.argtypes = [vp]
+    L.fnft_amd_slow_plan_chunks.restype = sz
+    L.fnft_amd_slow_plan_chunks.argtypes = [sz, sz, sz, C.POINTER(sz)]
+    L.fnft_amd_slow_plan_workspace_bytes.restype = sz
+    L.fnft_amd_slow_plan_workspace_bytes.argtypes = [vp]
+    L.fnft_amd_nsev_slow_device.restype = i32
+    L.fnft_amd_nsev_slow_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    L.fnft_amd_slow_plan_finish.restype = i32
+    L.fnft_amd_slow_plan_finish.argtypes = [vp, vp, vp, vp]
     if path is None:
         _lib = L
     return L
@@ -919,6 +933,100 @@ class DiscSpecPlan:
         ko = np.zeros(self.batch, np.uint64)
         rc = self.L.fnft_amd_discspec_plan_finish(self.h, C.c_void_p(stream), _ptr(st), _ptr(ko))
         return int(rc), st, ko
+
+
+SLOW_DISCS = ("BO", "CF4_2", "CF4_3", "CF5_3", "CF6_4", "ES4", "TES4")
+SLOW_UPSAMPLING = {"BO": 1, "CF4_2": 2, "CF4_3": 3, "CF5_3": 3, "CF6_4": 4, "ES4": 3, "TES4": 3}
+
+
+def slow_plan_chunks(D, M, batch=1):
+    """fnft_amd_slow_plan_chunks: (grid points per chunk, chunks) of a SlowPlan of these sizes.  Needs no GPU."""
+    L = C.c_size_t(0)
+    nc = load().fnft_amd_slow_plan_chunks(int(D), int(M), int(batch), C.byref(L))
+    return int(L.value), int(nc)
+
+
+class SlowPlan:
+    """fnft_amd_slow_plan_t: the continuous spectrum of `batch` signals of D samples on M grid points under one of the
+    slow discretizations (SLOW_DISCS), one set of options (dict as for nsev_opts, or NsevOpts; None: the defaults with
+    BO), device-resident.  Raises RuntimeError (attribute rc) if the plan cannot be created."""
+
+    def __init__(self, D, M, batch=1, opts=None, device=0):
+        self.L = load()
+        self.D, self.M, self.batch = int(D), int(M), int(batch)
+        self.opts = None if opts is None else (opts if isinstance(opts, NsevOpts) else nsev_opts(opts))
+        self.h = C.c_void_p()
+        rc = self.L.fnft_amd_slow_plan_create(C.byref(self.h), self.D, self.M, self.batch,
+                                              None if self.opts is None else C.byref(self.opts), int(device))
+        if rc != FNFT_SUCCESS:
+            err = RuntimeError("fnft_amd_slow_plan_create rc=%d (%s)" % (rc, last_error()))
+            err.rc = int(rc)
+            raise err
+
+    def close(self):
+        if self.h:
+            self.L.fnft_amd_slow_plan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def workspace_bytes(self):
+        return int(self.L.fnft_amd_slow_plan_workspace_bytes(self.h))
+
+    @property
+    def cs_len(self):
+        """complex128 values per signal of the output: M, 2M or 3M by contspec_type."""
+        return self.M * CS_FACTOR[CSTYPE["REFLECTION_COEFFICIENT"] if self.opts is None else int(self.opts.contspec_type)]
+
+    def run_device(self, q_ptr, T, XI, out_ptr, kappa=1, stream=0):
+        """Enqueue one call on raw device addresses: q_ptr (batch*D complex128) -> out_ptr (batch*cs_len)."""
+        return int(self.L.fnft_amd_nsev_slow_device(
+            self.h, C.c_void_p(q_ptr or None), None if T is None else _d2(T), C.c_void_p(out_ptr or None),
+            None if XI is None else _d2(XI), int(kappa), C.c_void_p(stream or None)))
+
+    def __call__(self, q, T, XI, kappa=1, out=None, stream=None):
+        """q: complex128 torch tensor (batch, D) on the plan's device.  Enqueues the transform on `stream` (a
+        torch.cuda.Stream; None: the current one) and returns the (batch, cs_len) output tensor without waiting."""
+        import torch
+        assert q.is_cuda and q.dtype == torch.complex128 and q.is_contiguous() and q.numel() == self.batch * self.D
+        if out is None:
+            out = torch.empty((self.batch, self.cs_len), dtype=torch.complex128, device=q.device)
+        assert out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous() and out.numel() == self.batch * self.cs_len
+        st = torch.cuda.current_stream(q.device) if stream is None else stream
+        self._stream = int(st.cuda_stream)
+        rc = self.run_device(q.data_ptr(), T, XI, out.data_ptr(), kappa, self._stream)
+        if rc != FNFT_SUCCESS:
+            err = RuntimeError("fnft_amd_nsev_slow_device rc=%d (%s)" % (rc, last_error()))
+            err.rc = rc
+            raise err
+        return out
+
+    def finish(self, stream=None):
+        """Waits for `stream` (None: the stream of the last __call__): (rc, status[batch], warnings[batch])."""
+        s = getattr(self, "_stream", 0) if stream is None else (stream if isinstance(stream, int) else int(stream.cuda_stream))
+        st = np.zeros(self.batch, np.int32)
+        wn = np.zeros(self.batch, np.int32)
+        rc = self.L.fnft_amd_slow_plan_finish(self.h, C.c_void_p(s or None), _ptr(st), _ptr(wn))
+        return int(rc), st, wn
+
+
+def nsev_slow(q, T, M, XI, kappa=1, discretization="BO", contspec_type="REFLECTION_COEFFICIENT", richardson=0):
+    """One signal through a SlowPlan of its own: (rc, contspec as numpy, warnings).  q: host array of D samples."""
+    import torch
+    q = np.ascontiguousarray(q, np.complex128)
+    plan = SlowPlan(q.size, M, 1, {"discretization": discretization, "contspec_type": contspec_type,
+                                   "richardson_extrapolation_flag": int(richardson)})
+    try:
+        out = plan(torch.from_numpy(q).cuda().reshape(1, -1), T, XI, kappa)
+        rc, st, wn = plan.finish()
+        return rc, out.cpu().numpy().reshape(-1), int(wn[0])
+    finally:
+        plan.close()
 
 
 def poly_fmult2x2_device(deg, n, p_ptr, out_ptr, stream=0):

@@ -1208,6 +1208,128 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
     return first;
 }
 
+// ---- batched, device-resident continuous spectrum of fnft_nsev under the slow discretizations ----------------------
+// Size and option checks run before any HIP call, with fnft_nsev's codes (fnft_nsev_host.c) in its order.
+struct fnft_amd_slow_plan {
+    HipBackend be;
+    NftSlowPlan<HipBackend> *sp = nullptr;
+    int device = 0;
+    hipStream_t last_stream = nullptr;
+    std::vector<int> st, wn;
+    std::mutex mtx;
+};
+
+FNFT_INT fnft_amd_slow_plan_create(fnft_amd_slow_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
+                                   fnft_nsev_opts_t const *opts, int device)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(D < 2, D);
+    SEAM_CHECK(M < 2, M);
+    SEAM_CHECK(batch == 0, batch);
+    fnft_nsev_opts_t o = opts ? *opts : fnft_nsev_default_opts();
+    if (!opts) o.discretization = fnft_nse_discretization_BO;
+    const int disc = (int)o.discretization;
+    NftSlowOpts so;
+    so.nse_disc = disc;
+    so.cstype = (int)o.contspec_type;
+    so.richardson = o.richardson_extrapolation_flag == 1 ? 1 : 0;
+    if (nft_slow_scheme(disc) < 0) {
+        SEAM_CHECK(nft_nse_to_akns(disc) < 0, opts->discretization);
+        return fnft_amd__raise(FNFT_EC_INVALID_ARGUMENT, __func__, __LINE__,
+                               "Invalid argument opts->discretization. A fast (polynomial) discretization: use "
+                               "fnft_amd_plan_create.");
+    }
+    if (so.cstype < 0 || so.cstype > 2)   // fnft_nsev_host.c:227-233: raised inside nsev_compute_contspec, wrapped twice
+        return inv_subroutine(__func__, __LINE__,
+                              inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_type")));
+    const int scheme = nft_slow_scheme(disc);
+    SEAM_CHECK(scheme >= 1 && scheme <= 4 && D <= 2, D);   // the resampler needs more than two samples, fnft__misc.c:331-332
+    fnft_amd_slow_plan *P = new (std::nothrow) fnft_amd_slow_plan();
+    if (!P) return FNFT_EC_NOMEM;
+    P->sp = new (std::nothrow) NftSlowPlan<HipBackend>(P->be, (size_t)D, (size_t)M, (size_t)batch, so);
+    if (!P->sp) { delete P; return FNFT_EC_NOMEM; }
+    if (P->sp->too_large()) {
+        delete P->sp;
+        delete P;
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (slow discretizations: more than 2^31 - 1 workgroups).");
+    }
+    DeviceGuard dg(device);
+    if (!dg.ok) { delete P->sp; delete P; return FNFT_EC_OTHER; }
+    P->device = device;
+    const int rc = P->sp->init();
+    if (rc != NFT_SUCCESS || P->be.failed) {
+        (void)P->be.sync();
+        P->sp->destroy();
+        delete P->sp;
+        delete P;
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = P;
+    return FNFT_SUCCESS;
+}
+
+void fnft_amd_slow_plan_destroy(fnft_amd_slow_plan_t *plan)
+{
+    if (!plan) return;
+    {
+        DeviceGuard dg(plan->device);
+        plan_quiesce(plan->last_stream);
+        plan->sp->destroy();
+        delete plan->sp;
+        plan->be.destroy_events();
+    }
+    delete plan;
+}
+
+FNFT_UINT fnft_amd_slow_plan_chunks(FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch, FNFT_UINT *points_per_chunk)
+{
+    if (D < 2 || M < 2 || batch == 0) return 0;
+    size_t L = 0;
+    const size_t nc = nft_slow_chunks((size_t)D, (size_t)M, (size_t)batch, &L);
+    if (points_per_chunk) *points_per_chunk = (FNFT_UINT)L;
+    return (FNFT_UINT)nc;
+}
+
+FNFT_UINT fnft_amd_slow_plan_workspace_bytes(const fnft_amd_slow_plan_t *plan)
+{
+    return plan ? plan->sp->workspace_bytes() : 0;
+}
+
+FNFT_INT fnft_amd_nsev_slow_device(fnft_amd_slow_plan_t *plan, const void *d_q, const FNFT_REAL *T, void *d_contspec,
+                                   const FNFT_REAL *XI, FNFT_INT kappa, void *stream)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(!d_q, q);
+    SEAM_CHECK(T == NULL || !(T[0] < T[1]), T);
+    SEAM_CHECK(!d_contspec, contspec);
+    SEAM_CHECK(XI == NULL || !(XI[0] < XI[1]), XI);
+    SEAM_CHECK(kappa != +1 && kappa != -1, kappa);
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    const int rc = plan->sp->run((const cplx *)d_q, T, (cplx *)d_contspec, XI, (int)kappa);
+    if (plan->be.failed) return FNFT_EC_OTHER;
+    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+}
+
+FNFT_INT fnft_amd_slow_plan_finish(fnft_amd_slow_plan_t *plan, void *stream, FNFT_INT *status, int *warnings)
+{
+    SEAM_CHECK(!plan, plan);
+    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    const int rc = plan->sp->read(plan->st, plan->wn);
+    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
+    FNFT_INT first = FNFT_SUCCESS;
+    for (size_t b = 0; b < plan->st.size(); b++) {
+        // src/fnft_nsev.c:850-853 through the two callers that wrap it, as the fast plan reports it
+        const FNFT_INT s = (plan->st[b] & 1) ? -FNFT_EC_DIV_BY_ZERO : FNFT_SUCCESS;
+        if (status) status[b] = s;
+        if (warnings) warnings[b] = (plan->wn[b] & 4) ? 1 : 0;
+        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
+    }
+    return first;
+}
+
 FNFT_INT fnft_amd_poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const double *A,
                               const double *W, const FNFT_UINT M, FNFT_COMPLEX *const result)
 {

@@ -116,6 +116,31 @@ template <bool LDSQ> struct KDsNorm {
     static constexpr size_t lds_bytes() { return ((size_t)kDsLanes * 10 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx); }
     static FA_DEV void body(const Params &p) { body_ds_norm<LDSQ>(p); }
 };
+// slow discretizations (nft_nsev_slow.h): FAM 0 CF family (REALK: real ks), 1 ES4, 2 TES4
+struct KSlowPrep {
+    using Params = SlowParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_slow_prep(p); }
+};
+template <int FAM, bool REALK> struct KSlowScatter {
+    using Params = SlowParams;
+    static constexpr int THREADS = kSlowLanes;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_slow_scatter<FAM, REALK>(p); }
+};
+struct KSlowReduce {
+    using Params = SlowParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_slow_reduce(p); }
+};
+struct KSlowCombine {
+    using Params = SlowParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_slow_combine(p); }
+};
 struct KGridMark {
     using Params = GridSearchParams;
     static constexpr int THREADS = 256;
@@ -889,4 +914,15 @@ template <class BE> bool dispatch_rleaf_strang(BE &be, const LeafParams &lp)
     case 18: be.template run<KRLeafStrang<8, true>>(g, 1, lp); return true;
     default: return false;
     }
+}
+
+// fam: 0 CF family, 1 ES4, 2 TES4; realk: the CF family's real-ks variant
+template <class BE> bool dispatch_slow_scatter(BE &be, int g, const SlowParams &P, int fam, bool realk)
+{
+    if (fam == 0 && realk) be.template run<KSlowScatter<0, true>>(g, 1, P);
+    else if (fam == 0) be.template run<KSlowScatter<0, false>>(g, 1, P);
+    else if (fam == 1) be.template run<KSlowScatter<1, false>>(g, 1, P);
+    else if (fam == 2) be.template run<KSlowScatter<2, false>>(g, 1, P);
+    else return false;
+    return true;
 }

@@ -2225,6 +2225,7 @@ struct ResampleParams {
     double delta_over_span;   // delta / (Din * eps_t)
     double w0, w1;            // 0.25 + sqrt(3)/6, 0.25 - sqrt(3)/6
     int *status;              // bit 2: "signal does not appear to be bandlimited" (body_band_check)
+    long long sstat = 0;      // status words between two signals: 0 one word for the batch, 1 one word per signal
 };
 
 // fnft__misc.c:371-381: the resampler's own check that the spectrum has decayed -- the l2 norms (trapezoidal rule,
@@ -2252,7 +2253,7 @@ FA_DEV void body_band_check(const ResampleParams &P)
         for (int t = 0; t < FA_BDIM; t++) { ta += red[t]; tl += red[FA_BDIM + t]; th += red[2 * FA_BDIM + t]; }
         // tmp = sqrt(lo + hi)/sqrt(all) > sqrt(eps)  <=>  lo + hi > eps * all   (Dlp >= 2: the reference's norm of fewer
         // than two points is NaN and never warns)
-        if (Dlp >= 2 && (tl + th) > 2.220446049250313e-16 * ta) fa_atomic_or_i32(P.status, 4);
+        if (Dlp >= 2 && (tl + th) > 2.220446049250313e-16 * ta) fa_atomic_or_i32(P.status + (size_t)FA_BID * P.sstat, 4);
     }
 }
 
@@ -4095,4 +4096,359 @@ FA_DEV void body_aberth_apply(const AberthParams &P)
     const int slot = fa_wave_append_slot(P.cnt, moved);
     if (moved) P.idx_out[slot] = (int)k;
     fa_wave_atomic_max_f64bits(P.maxcorr, rel);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Slow discretizations of fnft_nsev: BO, CF4_2, CF4_3, CF5_3, CF6_4, ES4, TES4 (nft_nsev_slow.h).  No polynomial
+// transfer matrix: one 2x2 step matrix per (sample, xi), src/private/fnft__akns_scatter_matrix.c:112-241 (CF family)
+// and :312-520 (ES4, TES4: exponentials by the Pauli expansion), derivative_flag == 0.
+//   body_slow_prep      src/private/fnft__nse_discretization.c:445-633 after the band-limited shifts: per-sample
+//                       records with everything that does not depend on xi
+//   body_slow_scatter   one lane = one xi of one signal, the product of its chunk of step matrices in registers; the
+//                       records are the same for the whole workgroup (uniform addresses: scalar loads)
+//   body_slow_reduce    products of groups of chunk maps (many short chunks: few xi, long signals)
+//   body_slow_combine   chunk or group maps in order, boundary and phase factors (src/fnft_nsev.c:836-884,
+//                       fnft__nse_discretization.c:240-375), Richardson extrapolation (src/fnft_nsev.c:396-405)
+// Records (complex values): CF family, one per table entry: {q, r, q r, lambda weight}; ES4, one per grid point:
+// {tmp1[0..2], c1, c2} with a1 = tmp1[0] + l c1, a2 = tmp1[1] + l c2, a3 = tmp1[2] - i eps l; TES4, one per grid point:
+// {E1 (c, u01, u10), P, B, C, E3 (c, u01, u10)}: the two xi-independent exponentials written out, and the middle one as
+// w^2 = P - a3^2, u01 = s B, u10 = s C.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSlowLanes = 64;
+constexpr int kSlowRecCf = 4, kSlowRecEs = 5, kSlowRecTes = 9;
+struct SlowParams {
+    // preprocessing
+    const cplx *q;          // batch * D input samples
+    const cplx *Q12;        // batch * 2 * D: the two shifted copies times D (CF4_2 ... CF6_4); NULL: D < kSlowDirectBelow,
+                            // the shifts are summed directly (slow_shift_direct)
+    double dsteps;          // the shift of the two copies in input steps
+    const cplx *wtab;       // 12 resampling weights, then 4 lambda weights
+    cplx *rec;              // batch * srec: records of this pass
+    long long D, Dsub, nskip, srec;
+    int batch, kappa;
+    int scheme;             // 0 BO, 1 CF4_2, 2 CF4_3, 3 CF5_3, 4 CF6_4, 5 ES4, 6 TES4
+    int npos;               // table entries per grid point in the CF family
+    double eps;             // step of the kept grid, (Tsub[1] - Tsub[0])/(Dsub - 1)
+    double eps_fd;          // eps_t * nskip: the step of the finite differences (fnft__nse_discretization.c:617)
+    // scatter
+    long long M;
+    double xi0, dxi;
+    long long L;            // grid points per chunk
+    int nchunk, ntile;
+    cplx *cm;               // batch * nchunk * 4 planes of M: chunk maps (chunk 0: its first column in planes 0 and 2,
+                            // zeros in 1 and 3, so that products with it keep the first column of the whole product)
+    // reduce: groups of gsize consecutive chunk maps of cm (nchunk of them) -> cmr (ngroup maps per signal)
+    cplx *cmr;
+    int gsize, ngroup;
+    // combine
+    const cplx *cm2;        // the Richardson pass (NULL: none), nchunk2 chunks
+    int nchunk2;
+    double pf[3], pf2[3];   // phase factors of rho, a, b: the full pass, the Richardson pass
+    double scl_num, scl_den, xi_lim;
+    int cstype;             // 0 rho, 1 a b, 2 rho a b
+    cplx *out;
+    int *status;            // batch: bit 0 a(xi) == 0 where rho is asked for
+};
+
+FA_DEV void c_sin_cos(cplx z, cplx &sn, cplx &cs)
+{
+    double s, c;
+    fa_sincos(z.x, &s, &c);
+    const double ch = cosh(z.y), sh = sinh(z.y);
+    sn = cmake(s * ch, c * sh);
+    cs = cmake(c * ch, -s * sh);
+}
+FA_DEV cplx slow_r_of(cplx q, int kappa) { return kappa < 0 ? cmake(q.x, -q.y) : cmake(-q.x, q.y); }
+// exp(a1 s1 + a2 s2 + a3 s3) from w^2 = -(a1^2 + a2^2 + a3^2) given as w2: c = cos w, s = sin(w)/w (1 at w == 0)
+FA_DEV void slow_pauli_cs(cplx w2, cplx &c, cplx &s)
+{
+    const cplx w = c_sqrt(w2);
+    cplx sn;
+    c_sin_cos(w, sn, c);
+    s = (w.x != 0.0 || w.y != 0.0) ? c_div(sn, w) : cmake(1.0, 0.0);
+}
+FA_DEV cplx slow_neg_sq2(cplx a1, cplx a2) { return cmake(0.0, 0.0) - a1 * a1 - a2 * a2; }
+
+// fnft__misc_resample (src/private/fnft__misc.c:364-397) at one sample of a short signal without the transforms:
+//   q_new[i] = sum_n q[n] K(i - n),  K(m) = 1/D sum_f exp(i th f),  th = 2 pi (m + delta)/D,  f = -(D - D/2) ... D/2 - 1
+//            = 1/D exp(i th c) sin(pi (m + delta)) / sin(th / 2),  c = -1/2 for even D, -1 for odd D,
+// with sin(pi (m + delta)) = (-1)^m sin(pi delta); m is taken modulo D next to 0 (delta is never an integer).
+// The resampling front end of NftPlan evaluates its DFTs as chirp z-transforms of at least 8192 points, which rounds
+// about three times as coarsely as a D-point transform; in a product of a few dozen steps that is the largest error.
+// Below kSlowDirectBelow samples the reference's band check can never warn (its 5 % bands hold fewer than two bins).
+constexpr long long kSlowDirectBelow = 40;
+FA_DEV cplx slow_shift_direct(const cplx *q, long long D, long long i, double delta)
+{
+    const double pi = 3.141592653589793238462643383279502884;
+    const double sd = sin(pi * delta);
+    cplx acc = cmake(0.0, 0.0);
+    for (long long n = 0; n < D; n++) {
+        long long m = i - n;
+        if (m >= (D + 1) / 2) m -= D;
+        else if (m < -(D / 2)) m += D;
+        double s1, c1;
+        fa_sincos(pi * (((double)m + delta) / (double)D), &s1, &c1);
+        const double mag = ((m & 1) ? -sd : sd) / s1;
+        const cplx K = (D & 1) ? cmake(mag * (c1 * c1 - s1 * s1), mag * (-2.0 * s1 * c1)) : cmake(mag * c1, -mag * s1);
+        acc = acc + q[n] * K;
+    }
+    return acc;   // times 1/D by the caller, like the transformed copies
+}
+
+// one lane per kept grid point of one signal
+FA_DEV void body_slow_prep(const SlowParams &P)
+{
+    const long long gid = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (gid >= (long long)P.batch * P.Dsub) return;
+    const long long b = gid / P.Dsub, is = gid - b * P.Dsub;
+    const long long i = is * P.nskip;
+    const cplx *q = P.q + (size_t)b * P.D;
+    const cplx q0 = q[i];
+    if (P.scheme <= 4) {
+        cplx *o = P.rec + (size_t)b * P.srec + (size_t)is * P.npos * kSlowRecCf;
+        cplx src[3] = {q0, q0, q0};
+        int nsrc = 1;
+        if (P.scheme >= 1) {
+            const double inv = 1.0 / (double)P.D;
+            const cplx q1 = (P.Q12 ? P.Q12[(size_t)(2 * b) * P.D + i] : slow_shift_direct(q, P.D, i, -P.dsteps)) * inv;
+            const cplx q3 = (P.Q12 ? P.Q12[(size_t)(2 * b + 1) * P.D + i] : slow_shift_direct(q, P.D, i, P.dsteps)) * inv;
+            src[0] = q1;
+            if (P.scheme == 1) { src[1] = q3; nsrc = 2; }
+            else { src[2] = q3; nsrc = 3; }
+        }
+        for (int p = 0; p < P.npos; p++) {
+            cplx qp = q0, rp = slow_r_of(q0, P.kappa);
+            if (P.scheme >= 1) {
+                const cplx *w = P.wtab + p * nsrc;
+                qp = w[0] * src[0];
+                rp = w[0] * slow_r_of(src[0], P.kappa);
+                qp = qp + w[1] * src[1];
+                rp = rp + w[1] * slow_r_of(src[1], P.kappa);
+                if (nsrc == 3) {
+                    qp = qp + w[2] * src[2];
+                    rp = rp + w[2] * slow_r_of(src[2], P.kappa);
+                }
+            }
+            o[0] = qp; o[1] = rp; o[2] = qp * rp; o[3] = P.wtab[12 + p];
+            o += kSlowRecCf;
+        }
+        return;
+    }
+    // ES4, TES4: q, q', q'' by central differences, zero outside the kept samples (:609-633)
+    const cplx z = cmake(0.0, 0.0);
+    const cplx qm = (is > 0) ? q[i - P.nskip] : z, qn = (is + 1 < P.Dsub) ? q[i + P.nskip] : z;
+    const double h = P.eps_fd, h2 = h * h;
+    const cplx qd = cmake((qn.x - qm.x) / (2.0 * h), (qn.y - qm.y) / (2.0 * h));
+    const cplx t = qn - q0 * 2.0 + qm;
+    const cplx qdd = cmake(t.x / h2, t.y / h2);
+    const cplx r0 = slow_r_of(q0, P.kappa), rd = slow_r_of(qd, P.kappa), rdd = slow_r_of(qdd, P.kappa);
+    const double e = P.eps, e2 = e * e, e3 = e * e * e;
+    const cplx I = cmake(0.0, 1.0);
+    if (P.scheme == 5) {
+        cplx *o = P.rec + (size_t)b * P.srec + (size_t)is * kSlowRecEs;
+        o[0] = (qdd + rdd) * (e3 / 48.0) + (q0 + r0) * (e * 0.5);
+        o[1] = I * ((q0 - r0) * (e * 0.5)) + I * ((qdd - rdd) * (e3 / 48.0));
+        o[2] = (q0 * rd - qd * r0) * (-e3 / 12.0);
+        o[3] = I * ((qd - rd) * (e3 / 12.0));
+        o[4] = (qd + rd) * (-e3 / 12.0);
+        return;
+    }
+    cplx *o = P.rec + (size_t)b * P.srec + (size_t)is * kSlowRecTes;
+    const cplx sdd = (qdd + rdd) * (e3 / 96.0), ddd = I * ((qdd - rdd) * (e3 / 96.0));
+    const cplx sd = (qd + rd) * (e2 / 24.0), dd = I * ((qd - rd) * (e2 / 24.0));
+    for (int k = 0; k < 2; k++) {   // tmp1 (first exponential), tmp2 (third)
+        const cplx a1 = k == 0 ? sdd - sd : sdd + sd, a2 = k == 0 ? ddd - dd : ddd + dd;
+        cplx c, s;
+        slow_pauli_cs(slow_neg_sq2(a1, a2), c, s);
+        cplx *u = o + (k == 0 ? 0 : 6);
+        u[0] = c;
+        u[1] = s * (a1 - I * a2);
+        u[2] = s * (a1 + I * a2);
+    }
+    const cplx a1 = (q0 + r0) * (e * 0.5), a2 = I * ((q0 - r0) * (e * 0.5));
+    o[3] = slow_neg_sq2(a1, a2);
+    o[4] = a1 - I * a2;
+    o[5] = a1 + I * a2;
+}
+
+// one more step matrix on the left: of the first column v of the product (vec, the chunk that starts the signal: only S11
+// and S21 are wanted) or of the whole map T.  `vec` is the same for the workgroup.
+FA_DEV void slow_push(bool vec, const cplx *U, cplx *v, cplx *T)
+{
+    if (vec) bs_map_apply(U, v);
+    else bs_map_mul(U, T);
+}
+// FAM 0: CF family, n table entries; 1: ES4, 2: TES4, n grid points.  REALK (CF family with real weights and
+// r = -kappa conj(q) on a real grid): ks = q r - l^2 is real, so cosh(k eps) and sinh(k eps)/k take one expm1 or one sincos
+template <int FAM, bool REALK>
+FA_DEV void slow_run(const cplx *__restrict__ R, long long n, double xi, double e, bool vec, cplx *v, cplx *T)
+{
+    for (long long j = 0; j < n; j++) {
+        cplx U[4];
+        if (FAM == 0) {
+            const cplx q = R[0], r = R[1], qr = R[2], lw = R[3];
+            R += kSlowRecCf;
+            if (REALK) {
+                const double l = xi * lw.x, ks = qr.x - l * l;
+                double ch = 1.0, sh = e;   // ks == 0, :223-226
+                if (ks > 0.0) {
+                    const double k = sqrt(ks), em1 = expm1(k * e), E = em1 + 1.0, Ei = 1.0 / E;
+                    ch = 0.5 * (E + Ei);
+                    sh = 0.5 * (em1 + em1 * Ei) / k;
+                } else if (ks < 0.0) {
+                    const double k = sqrt(-ks);
+                    double s, c;
+                    fa_sincos(k * e, &s, &c);
+                    ch = c;
+                    sh = s / k;
+                }
+                U[0] = cmake(ch, -l * sh);
+                U[1] = q * sh;
+                U[2] = r * sh;
+                U[3] = cmake(ch, l * sh);
+            } else {
+                const cplx l = lw * xi, ks = qr - l * l, k = c_sqrt(ks);
+                cplx ch, shk;
+                c_cosh_sinh(k * e, ch, shk);
+                const cplx sh = (ks.x != 0.0 || ks.y != 0.0) ? c_div(shk, k) : cmake(e, 0.0);
+                const cplx ilsh = cmake(-l.y, l.x) * sh;
+                U[0] = ch - ilsh;
+                U[1] = q * sh;
+                U[2] = r * sh;
+                U[3] = ch + ilsh;
+            }
+            slow_push(vec, U, v, T);
+        } else if (FAM == 1) {
+            const cplx a1 = R[0] + R[3] * xi, a2 = R[1] + R[4] * xi, a3 = R[2] - cmake(0.0, e * xi);
+            R += kSlowRecEs;
+            cplx c, s;
+            slow_pauli_cs(slow_neg_sq2(a1, a2) - a3 * a3, c, s);
+            const cplx sa3 = s * a3, ia2 = cmake(-a2.y, a2.x);
+            U[0] = c + sa3;
+            U[1] = s * (a1 - ia2);
+            U[2] = s * (a1 + ia2);
+            U[3] = c - sa3;
+            slow_push(vec, U, v, T);
+        } else {
+            U[0] = R[0]; U[1] = R[1]; U[2] = R[2]; U[3] = R[0];
+            slow_push(vec, U, v, T);
+            const cplx a3 = cmake(0.0, -e * xi);
+            cplx c, s;
+            slow_pauli_cs(R[3] - a3 * a3, c, s);
+            const cplx sa3 = s * a3;
+            U[0] = c + sa3; U[1] = s * R[4]; U[2] = s * R[5]; U[3] = c - sa3;
+            slow_push(vec, U, v, T);
+            U[0] = R[6]; U[1] = R[7]; U[2] = R[8]; U[3] = R[6];
+            slow_push(vec, U, v, T);
+            R += kSlowRecTes;
+        }
+    }
+}
+
+// grid.x = (xi tile, chunk, signal), tile fastest
+template <int FAM, bool REALK> FA_DEV void body_slow_scatter(const SlowParams &P)
+{
+    const int tile = FA_BID % P.ntile, rest = FA_BID / P.ntile;
+    const int c = rest % P.nchunk;
+    const long long b = rest / P.nchunk;
+    const long long m = (long long)tile * FA_BDIM + FA_TID;
+    if (m >= P.M) return;
+    long long g0, g1;
+    bs_run_bounds<long long>((long long)c, P.L, P.Dsub, g0, g1);
+    const int per = FAM == 0 ? P.npos * kSlowRecCf : (FAM == 1 ? kSlowRecEs : kSlowRecTes);
+    const cplx *R = P.rec + (size_t)b * P.srec + (size_t)g0 * per;
+    const long long n = (g1 - g0) * (FAM == 0 ? P.npos : 1);
+    const double xi = P.xi0 + P.dxi * (double)m;
+    cplx *o = P.cm + ((size_t)b * P.nchunk + c) * 4 * P.M + m;
+    cplx v[2] = {cmake(1.0, 0.0), cmake(0.0, 0.0)}, T[4];
+    bs_map_identity(T);
+    slow_run<FAM, REALK>(R, n, xi, P.eps, c == 0, v, T);
+    if (c == 0) {
+        o[0] = v[0];
+        o[P.M] = cmake(0.0, 0.0);
+        o[2 * P.M] = v[1];
+        o[3 * P.M] = cmake(0.0, 0.0);
+    } else {
+        for (int k = 0; k < 4; k++) o[(size_t)k * P.M] = T[k];
+    }
+}
+
+// one lane per (signal, group, xi): the product of the group's chunk maps, in order.  With thousands of short chunks
+// (few xi, long signals) the walk of body_slow_combine would be the longest serial chain of the call; two levels of
+// about sqrt(nchunk) maps each replace it.
+FA_DEV void body_slow_reduce(const SlowParams &P)
+{
+    const long long gid = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (gid >= (long long)P.batch * P.ngroup * P.M) return;
+    const long long m = gid % P.M, bg = gid / P.M;
+    const long long g = bg % P.ngroup, b = bg / P.ngroup;
+    int c0, c1;
+    bs_run_bounds<int>((int)g, P.gsize, P.nchunk, c0, c1);
+    const cplx *p = P.cm + ((size_t)b * P.nchunk + c0) * 4 * P.M + m;
+    cplx T[4] = {p[0], p[P.M], p[2 * P.M], p[3 * P.M]};
+    for (int c = c0 + 1; c < c1; c++) {
+        p += 4 * P.M;
+        const cplx U[4] = {p[0], p[P.M], p[2 * P.M], p[3 * P.M]};
+        bs_map_mul(U, T);
+    }
+    cplx *o = P.cmr + ((size_t)b * P.ngroup + g) * 4 * P.M + m;
+    for (int k = 0; k < 4; k++) o[(size_t)k * P.M] = T[k];
+}
+
+// (S11, S21) of signal b at grid point m: chunk 0's column through the later chunks' maps, in order
+FA_DEV void slow_chain(const cplx *cm, int nchunk, long long M, long long b, long long m, cplx *v)
+{
+    const cplx *p = cm + (size_t)b * nchunk * 4 * M + m;
+    v[0] = p[0];
+    v[1] = p[2 * M];
+    for (int c = 1; c < nchunk; c++) {
+        p += 4 * M;
+        const cplx T[4] = {p[0], p[M], p[2 * M], p[3 * M]};
+        bs_map_apply(T, v);
+    }
+}
+// rho, a, b from (S11, S21), src/fnft_nsev.c:846-876; returns whether a division by S11 == 0 was asked for
+FA_DEV bool slow_spectrum(const cplx *v, double xi, const double *pf, int cstype, cplx *X)
+{
+    bool zero = false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if ((k == 0 && cstype == 1) || (k > 0 && cstype == 0)) continue;
+        double s, c;
+        fa_sincos(xi * pf[k], &s, &c);
+        const cplx ph = cmake(c, s);
+        if (k == 0) {
+            zero = (v[0].x == 0.0 && v[0].y == 0.0);
+            X[0] = c_div(v[1] * ph, v[0]);
+        } else {
+            X[k] = v[k - 1] * ph;
+        }
+    }
+    return zero;
+}
+// one lane per (signal, xi)
+FA_DEV void body_slow_combine(const SlowParams &P)
+{
+    const long long gid = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (gid >= (long long)P.batch * P.M) return;
+    const long long b = gid / P.M, m = gid - b * P.M;
+    const double xi = P.xi0 + P.dxi * (double)m;
+    cplx v[2], X[3], Y[3];
+    slow_chain(P.cm, P.nchunk, P.M, b, m, v);
+    bool zero = slow_spectrum(v, xi, P.pf, P.cstype, X);
+    if (P.cm2) {
+        slow_chain(P.cm2, P.nchunk2, P.M, b, m, v);
+        zero = slow_spectrum(v, xi, P.pf2, P.cstype, Y) || zero;
+    }
+    const bool rich = P.cm2 && fabs(xi) < P.xi_lim;
+    const int k0 = (P.cstype == 1) ? 1 : 0, k1 = (P.cstype == 0) ? 1 : 3;
+    cplx *o = P.out + (size_t)b * (k1 - k0) * P.M + m;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (k < k0 || k >= k1) continue;
+        cplx x = X[k];
+        if (rich) x = cmake((P.scl_num * x.x - Y[k].x) / P.scl_den, (P.scl_num * x.y - Y[k].y) / P.scl_den);
+        o[(size_t)(k - k0) * P.M] = x;
+    }
+    if (zero) fa_atomic_or_i32(P.status + b, 1);
 }

@@ -201,6 +201,8 @@ public:
     static size_t sub_count(size_t Din_, size_t nskip_) { return (size_t)std::llround((double)Din_ / (double)nskip_); }
     // call before init(): this plan was constructed with D = ups_ * sub_count(Din_, nskip_)
     void set_front(size_t Din_, size_t nskip_, int ups_) { Din = Din_; nskip = nskip_; ups = ups_; }
+    // call before init(): only run_resample will be used, so neither the tree's nor the evaluation's buffers are made
+    bool front_only = false;
 
     template <class T> bool alloc(T *&p, size_t count)
     {
@@ -258,16 +260,17 @@ public:
         const size_t topN = (Dpad > 1) ? nft_product_len(Dpad / 2 * (size_t)deg0) : 2;
         if (topN > kMaxSplitTree) return NFT_EC_NOT_YET_IMPLEMENTED;
         bool ok = true;
-        for (int i = 0; i < 2; i++) {
+        for (int i = 0; i < 2 && !front_only; i++) {
             ok = ok && alloc(body[i], 4 * plane) && alloc(tail[i], 4 * n0) && alloc(scale[i], n0)
                  && alloc(wexp[i], n0);
         }
         {   // split levels hold at most n0*deg0/2048 matrices, kMax2Slots slots each
             const size_t nm = n0 * (size_t)deg0 / 32 + 4 * (size_t)kMax2Slots;
-            ok = ok && alloc(max2[0], nm) && alloc(max2[1], nm) && alloc(status, 4);
+            if (!front_only) ok = ok && alloc(max2[0], nm) && alloc(max2[1], nm);
+            ok = ok && alloc(status, 4);
             if (ok) be.memset0(status, 4 * sizeof(int));
         }
-        {   // scratch of the split transforms: 4*n_in polynomials of N forward, 4*n_out inverse,
+        if (!front_only) {   // scratch of the split transforms: 4*n_in polynomials of N forward, 4*n_out inverse,
             // maximised over the levels that use them (N can exceed 2d when d is not 2^k)
             size_t needY = 0, needZ = 0, n = n0, d = (size_t)deg0;
             while (n / batch > 1) {
@@ -281,14 +284,14 @@ public:
             }
             if (needY) ok = ok && alloc(Y, needY) && alloc(Z, needZ) && alloc(Z2, needZ);
         }
-        if (M > 0) {
+        if (M > 0 && !front_only) {
             const size_t Np = D * (size_t)deg0 + 1;
             Lc = nft_nextpow2(Np + M - 1);
             if (Lc < 2 * (size_t)kRowChirp) Lc = 2 * (size_t)kRowChirp;
             if (Lc > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
             ok = ok && alloc(chY, batch * 2 * Lc) && alloc(chV, Lc) && alloc(chVS, Lc);
         }
-        ok = ok && alloc(tm_out, batch * 4 * (D * (size_t)deg0 + 1));
+        if (!front_only) ok = ok && alloc(tm_out, batch * 4 * (D * (size_t)deg0 + 1));
         ok = ok && alloc(twtab, (size_t)2 * kMaxTwTable) && alloc(twlo, kTwLoEntries);
         if (kdv) ok = ok && alloc(tw3tab, (size_t)3 << (kTw3MaxLog + 1)) && alloc(twlo3, (size_t)1 << kFineLog2);
         if (kdv) {
@@ -302,7 +305,8 @@ public:
             Lr = nft_nextpow2(2 * Din - 1);
             if (Lr < 2 * (size_t)kRowChirp) Lr = 2 * (size_t)kRowChirp;
             if (Lr > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-            ok = ok && alloc(qpre, batch * D) && alloc(rsX, batch * Din) && alloc(rsX12, batch * 2 * Din)
+            if (!front_only) ok = ok && alloc(qpre, batch * D);
+            ok = ok && alloc(rsX, batch * Din) && alloc(rsX12, batch * 2 * Din)
                  && alloc(rsQ12, batch * 2 * Din) && alloc(rsY, batch * 2 * Lr) && alloc(rsV, Lr);
         }
         CoeffProgramHost prog;
@@ -404,6 +408,24 @@ public:
         Tsub[0] = T[0];
         Tsub[1] = T[0] + (double)((Dsub - 1) * nskip) * eps_in;
         const double eps_t = (Tsub[1] - Tsub[0]) / (double)(Dsub - 1);
+        // shifts -/+ sqrt(3)/6 of the kept step (:482-485), then the weighted pairs (:493-499)
+        const double scl = std::sqrt(3.0) / 6.0;
+        ResampleParams R;
+        const int rc = run_resample(d_q, scl * (double)nskip, status, 0, true, R);
+        if (rc != NFT_SUCCESS) return rc;
+        R.qpre = qpre;
+        R.Dsub = (long long)Dsub; R.nskip = (long long)nskip;
+        R.w0 = 0.25 + scl;
+        R.w1 = 0.25 - scl;
+        be.template run<KResampleCombine>((int)((batch * Dsub + 255) / 256), 1, R);
+        return run_coeffs(qpre, nullptr, eps_t, kappa, false);
+    }
+
+    // fnft__misc_resample for every signal of the batch and the two shifts -/+ delta_steps input steps: leaves the
+    // shifted copies times Din in rsQ12 (signal b: rows 2b and 2b + 1).  fwd: transform the signal first and check its
+    // band (bit 2 of wstat[b * wstride]); without it the spectrum of the last call with the same signal is used again.
+    int run_resample(const void *d_q, double delta_steps, int *wstat, long long wstride, bool fwd, ResampleParams &R)
+    {
         // forward DFT of every signal (fnft__misc.c:366-370)
         ChirpParams C;
         std::memset(&C, 0, sizeof(C));
@@ -418,29 +440,27 @@ public:
         C.cstype = -1;
         C.dft_len = (long long)Din;
         C.dft_sign = -1;
-        int rc = run_chirp(C);
-        if (rc != NFT_SUCCESS) return rc;
-        // phase ramps for the shifts -/+ sqrt(3)/6 of the kept step (:482-485, fnft__misc.c:383-393)
-        ResampleParams R;
-        R.X = rsX; R.X12 = rsX12; R.Q12 = rsQ12; R.qpre = qpre;
-        R.Din = (long long)Din; R.Dsub = (long long)Dsub; R.nskip = (long long)nskip;
+        int rc = NFT_SUCCESS;
+        if (fwd) {
+            rc = run_chirp(C);
+            if (rc != NFT_SUCCESS) return rc;
+        }
+        // phase ramps for the two shifts (fnft__misc.c:383-393)
+        R.X = rsX; R.X12 = rsX12; R.Q12 = rsQ12; R.qpre = nullptr;
+        R.Din = (long long)Din; R.Dsub = 0; R.nskip = 1;
         R.batch = (int)batch;
-        const double scl = std::sqrt(3.0) / 6.0;
-        R.delta_over_span = scl * (double)nskip / (double)Din;
-        R.w0 = 0.25 + scl;
-        R.w1 = 0.25 - scl;
-        R.status = status;
-        be.template run<KBandCheck>((int)batch, 1, R);     // fnft__misc.c:371-381 (warning only)
+        R.delta_over_span = delta_steps / (double)Din;
+        R.w0 = R.w1 = 0.0;
+        R.status = wstat;
+        R.sstat = wstride;
+        if (fwd) be.template run<KBandCheck>((int)batch, 1, R);     // fnft__misc.c:371-381 (warning only)
         be.template run<KResamplePhase>((int)((batch * Din + 255) / 256), 1, R);
-        // inverse DFTs (:395-399), then the weighted pairs (:493-499)
+        // inverse DFTs (:395-399)
         C.poly = rsX12;
         C.npoly = 2;
         C.Hbuf = rsQ12;
         C.dft_sign = +1;
-        rc = run_chirp(C);
-        if (rc != NFT_SUCCESS) return rc;
-        be.template run<KResampleCombine>((int)((batch * Dsub + 255) / 256), 1, R);
-        return run_coeffs(qpre, nullptr, eps_t, kappa, false);
+        return run_chirp(C);
     }
 
     // ---- level 0 from samples (fnft__akns_fscatter.c:116-917) --------------------------------

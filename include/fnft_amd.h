@@ -550,6 +550,41 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
 FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *stream, FNFT_INT *status,
                                        FNFT_UINT *K_out);
 
+/* ---- slow discretizations: batched, device-resident continuous spectrum ---------------------
+ * fnft_nsev's contspec of `batch` signals of D samples on one xi-grid of M points with opts->discretization one of
+ * BO, CF4_2, CF4_3, CF5_3, CF6_4, ES4, TES4: the schemes without a polynomial transfer matrix, one 2x2 step matrix
+ * per (sample, xi).  Per signal the plan produces what the reference's fnft_nsev writes to contspec for that signal
+ * alone.  Options read: discretization, contspec_type, richardson_extrapolation_flag; opts == NULL: the defaults
+ * with BO.  Preprocessing (band-limited resampling, finite differences), the step matrices, boundary and phase
+ * factors and the Richardson pass all run on the device; every workspace is allocated at create.
+ * Create-time errors, before any HIP call: FNFT_EC_INVALID_ARGUMENT for plan == NULL, D < 2, M < 2, batch == 0, an
+ * unknown discretization, a fast discretization (those go to fnft_amd_plan_create), and D == 2 under the four
+ * resampling schemes (the reference's resampler rejects it); -FNFT_EC_INVALID_ARGUMENT for contspec_type out of
+ * range (raised two callers down in the reference); FNFT_EC_OTHER if the device cannot be used. */
+typedef struct fnft_amd_slow_plan fnft_amd_slow_plan_t;
+FNFT_INT fnft_amd_slow_plan_create(fnft_amd_slow_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
+                                   fnft_nsev_opts_t const *opts, int device);
+/* Waits for the plan's last stream, then gives its workspace back.  NULL is ignored. */
+void fnft_amd_slow_plan_destroy(fnft_amd_slow_plan_t *plan);
+/* Chunks a plan of these sizes cuts the sample axis of one signal into (chosen at create from D, M and batch), and the
+ * grid points per chunk.  Two calls give bitwise equal results for a signal only if their plans use the same chunks.
+ * Needs no device; 0 for sizes a plan cannot have. */
+FNFT_UINT fnft_amd_slow_plan_chunks(FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch, FNFT_UINT *points_per_chunk);
+/* Bytes of HBM the plan holds. */
+FNFT_UINT fnft_amd_slow_plan_workspace_bytes(const fnft_amd_slow_plan_t *plan);
+/* d_q: batch*D complex128 on the device (signal b at +b*D), NOT modified.  d_contspec: batch*M*{1,2,3} complex128 out,
+ * per signal in the reference's layout (rho | a, b | rho, a, b by contspec_type).  T, XI: host pairs shared by the
+ * batch.  FNFT_EC_INVALID_ARGUMENT, before anything is enqueued, for a NULL pointer, T[0] >= T[1], XI[0] >= XI[1] or
+ * |kappa| != 1.  Asynchronous on `stream` (a hipStream_t, NULL = default stream): allocates nothing, never waits,
+ * copies nothing to the host. */
+FNFT_INT fnft_amd_nsev_slow_device(fnft_amd_slow_plan_t *plan, const void *d_q, const FNFT_REAL *T,
+                                   void *d_contspec, const FNFT_REAL *XI, FNFT_INT kappa, void *stream);
+/* Waits for `stream`.  status[b] (may be NULL): 0, or -FNFT_EC_DIV_BY_ZERO where a(xi) == 0 exactly at a grid point
+ * of signal b and rho was asked for.  warnings[b] (may be NULL): bit 0, the resampler found signal b not band-limited
+ * (as fnft_amd_plan_last_warnings; CF4_2, CF4_3, CF5_3 and CF6_4 only).  Returns 0, or the status of the
+ * lowest-index failing signal; a failing signal leaves the others unchanged. */
+FNFT_INT fnft_amd_slow_plan_finish(fnft_amd_slow_plan_t *plan, void *stream, FNFT_INT *status, int *warnings);
+
 /* ======================================================================================== */
 /* 4.Korteweg-de Vries equation, vanishing boundaries (include/fnft_kdvv.h)                  */
 /* ======================================================================================== */
