@@ -653,17 +653,8 @@ def kdv_fscatter(u, eps_t, discretization, normalize=True):
     return int(rc), dd, res[: 4 * (dd + 1)].reshape(4, dd + 1).copy(), int(W.value)
 
 
-class KdvvPlan:
-    """Device-resident KdV transform (fnft_amd_kdvv_plan_create)."""
-
-    def __init__(self, D, M, batch=1, discretization="2SPLIT8B", device=0):
-        self.L = load()
-        self.D, self.M, self.batch = int(D), int(M), int(batch)
-        self.disc = KDV_DISC[discretization] if isinstance(discretization, str) else int(discretization)
-        self.h = C.c_void_p()
-        rc = self.L.fnft_amd_kdvv_plan_create(C.byref(self.h), self.D, self.M, self.batch, self.disc, int(device))
-        if rc != FNFT_SUCCESS:
-            raise RuntimeError("fnft_amd_kdvv_plan_create rc=%d (%s)" % (rc, last_error()))
+class _TreePlan:
+    """What Plan and KdvvPlan share: self.h is a fnft_amd_plan_t of the library self.L."""
 
     def close(self):
         if self.h:
@@ -675,10 +666,6 @@ class KdvvPlan:
             self.close()
         except Exception:
             pass
-
-    def set_real_mode(self, mode):
-        """-1: ask the device whether u is real (default); 1: u is real (real-coefficient tree); 0: complex tree."""
-        return int(self.L.fnft_amd_kdvv_plan_set_real_mode(self.h, int(mode)))
 
     def set_timing(self, on=True):
         self.L.fnft_amd_plan_set_timing(self.h, 1 if on else 0)
@@ -698,18 +685,35 @@ class KdvvPlan:
     def last_ms(self, which=2):
         return float(self.L.fnft_amd_plan_last_ms(self.h, which))
 
+    def finish(self, stream=0):
+        return int(self.L.fnft_amd_plan_finish(self.h, C.c_void_p(stream)))
+
+
+class KdvvPlan(_TreePlan):
+    """Device-resident KdV transform (fnft_amd_kdvv_plan_create)."""
+
+    def __init__(self, D, M, batch=1, discretization="2SPLIT8B", device=0):
+        self.L = load()
+        self.D, self.M, self.batch = int(D), int(M), int(batch)
+        self.disc = KDV_DISC[discretization] if isinstance(discretization, str) else int(discretization)
+        self.h = C.c_void_p()
+        rc = self.L.fnft_amd_kdvv_plan_create(C.byref(self.h), self.D, self.M, self.batch, self.disc, int(device))
+        if rc != FNFT_SUCCESS:
+            raise RuntimeError("fnft_amd_kdvv_plan_create rc=%d (%s)" % (rc, last_error()))
+
+    def set_real_mode(self, mode):
+        """-1: ask the device whether u is real (default); 1: u is real (real-coefficient tree); 0: complex tree."""
+        return int(self.L.fnft_amd_kdvv_plan_set_real_mode(self.h, int(mode)))
+
     def contspec_device(self, u_ptr, out_ptr, T, XI, stream=0):
         return int(self.L.fnft_amd_kdvv_contspec_device(self.h, C.c_void_p(u_ptr), C.c_void_p(out_ptr),
                                                         _d2(T), _d2(XI), C.c_void_p(stream)))
-
-    def finish(self, stream=0):
-        return int(self.L.fnft_amd_plan_finish(self.h, C.c_void_p(stream)))
 
 
 # --------------------------------------------------------------------------------------------
 # device-resident plan (inputs already in HBM)
 # --------------------------------------------------------------------------------------------
-class Plan:
+class Plan(_TreePlan):
     """fnft_amd_plan_t: `batch` signals of D samples, M spectral points, one discretization."""
 
     def __init__(self, D, M, batch=1, discretization="2SPLIT2_MODAL", device=0, nskip=1):
@@ -722,17 +726,6 @@ class Plan:
         if rc != FNFT_SUCCESS:
             raise RuntimeError("fnft_amd_plan_create rc=%d (%s)" % (rc, last_error()))
 
-    def close(self):
-        if self.h:
-            self.L.fnft_amd_plan_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     @property
     def workspace_bytes(self):
         return int(self.L.fnft_amd_plan_workspace_bytes(self.h))
@@ -741,24 +734,6 @@ class Plan:
         c = CSTYPE[contspec_type] if isinstance(contspec_type, str) else int(contspec_type)
         return self.M * CS_FACTOR[c]
 
-    def set_timing(self, on=True):
-        self.L.fnft_amd_plan_set_timing(self.h, 1 if on else 0)
-
-    def set_launch_timing(self, on=True):
-        self.L.fnft_amd_plan_set_launch_timing(self.h, 1 if on else 0)
-
-    def launch_times(self):
-        """[(kernel name, ms)] of every launch since set_launch_timing(True); the stream must be idle."""
-        out = []
-        buf = C.create_string_buffer(128)
-        for i in range(int(self.L.fnft_amd_plan_launch_count(self.h))):
-            ms = float(self.L.fnft_amd_plan_launch_ms(self.h, i, buf, len(buf)))
-            out.append((buf.value.decode(), ms))
-        return out
-
-    def last_ms(self, which=2):
-        return float(self.L.fnft_amd_plan_last_ms(self.h, which))
-
     def contspec_device(self, q_ptr, out_ptr, T, XI, kappa=1, contspec_type="BOTH",
                         normalization_flag=1, stream=0):
         """Enqueue one pass.  q_ptr/out_ptr are raw device addresses (e.g. tensor.data_ptr())."""
@@ -766,9 +741,6 @@ class Plan:
         return int(self.L.fnft_amd_nsev_contspec_device(
             self.h, C.c_void_p(q_ptr), C.c_void_p(out_ptr), _d2(T), _d2(XI), int(kappa), c,
             int(normalization_flag), C.c_void_p(stream)))
-
-    def finish(self, stream=0):
-        return int(self.L.fnft_amd_plan_finish(self.h, C.c_void_p(stream)))
 
     def contspec_from_tm_device(self, tm_ptr, W, out_ptr, T, XI, contspec_type="BOTH", stream=0):
         """Continuous spectrum from a transfer matrix in device memory (fnft_amd_nsev_contspec_from_tm_device)."""
@@ -803,25 +775,15 @@ class Plan:
         return int(rc), d, buf[: 4 * (d + 1)].reshape(4, d + 1).copy(), int(W.value)
 
 
-class InversePlan:
-    """fnft_amd_inverse_plan_t: `batch` inverse transforms of M spectral values to D samples each, one set of options
-    (dict as for fnft_nsev_inverse), device-resident.  K = 0: the continuous part (run_device); K > 0: K bound states
-    per signal on top of it, or alone with M = 0 (run_device_discrete).  Raises RuntimeError (attribute rc) if the
-    plan cannot be created."""
+class _BatchPlan:
+    """What InversePlan, DiscSpecPlan and SlowPlan share: self.h is the plan of the library self.L, _DESTROY and
+    _FINISH name its entries."""
+    _DESTROY = _FINISH = None
 
-    def __init__(self, D, M, batch=1, opts=None, device=0, K=0):
-        self.L = load()
-        self.D, self.M, self.batch, self.K = int(D), int(M), int(batch), int(K)
-        self.opts = inverse_opts(opts)
+    def _create(self, fn, *args):
+        """self.h = the plan made by the entry `fn`, or RuntimeError with the entry's code in its attribute rc."""
         self.h = C.c_void_p()
-        if self.K > 0:
-            fn = "fnft_amd_inverse_plan_create_discrete"
-            rc = self.L.fnft_amd_inverse_plan_create_discrete(C.byref(self.h), self.D, self.M, self.K, self.batch,
-                                                              C.byref(self.opts), int(device))
-        else:
-            fn = "fnft_amd_inverse_plan_create"
-            rc = self.L.fnft_amd_inverse_plan_create(C.byref(self.h), self.D, self.M, self.batch, C.byref(self.opts),
-                                                     int(device))
+        rc = getattr(self.L, fn)(C.byref(self.h), *args)
         if rc != FNFT_SUCCESS:
             err = RuntimeError("%s rc=%d (%s)" % (fn, rc, last_error()))
             err.rc = int(rc)
@@ -829,7 +791,7 @@ class InversePlan:
 
     def close(self):
         if self.h:
-            self.L.fnft_amd_inverse_plan_destroy(self.h)
+            getattr(self.L, self._DESTROY)(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -837,6 +799,31 @@ class InversePlan:
             self.close()
         except Exception:
             pass
+
+    def _finish(self, stream, second=np.int32):
+        """(rc, status[batch], second per-signal array[batch]) once `stream` is done."""
+        st = np.zeros(self.batch, np.int32)
+        x = np.zeros(self.batch, second)
+        rc = getattr(self.L, self._FINISH)(self.h, C.c_void_p(stream), _ptr(st), _ptr(x))
+        return int(rc), st, x
+
+
+class InversePlan(_BatchPlan):
+    """fnft_amd_inverse_plan_t: `batch` inverse transforms of M spectral values to D samples each, one set of options
+    (dict as for fnft_nsev_inverse), device-resident.  K = 0: the continuous part (run_device); K > 0: K bound states
+    per signal on top of it, or alone with M = 0 (run_device_discrete).  Raises RuntimeError (attribute rc) if the
+    plan cannot be created."""
+    _DESTROY, _FINISH = "fnft_amd_inverse_plan_destroy", "fnft_amd_inverse_plan_finish"
+
+    def __init__(self, D, M, batch=1, opts=None, device=0, K=0):
+        self.L = load()
+        self.D, self.M, self.batch, self.K = int(D), int(M), int(batch), int(K)
+        self.opts = inverse_opts(opts)
+        if self.K > 0:
+            self._create("fnft_amd_inverse_plan_create_discrete", self.D, self.M, self.K, self.batch,
+                         C.byref(self.opts), int(device))
+        else:
+            self._create("fnft_amd_inverse_plan_create", self.D, self.M, self.batch, C.byref(self.opts), int(device))
 
     def workspace_bytes(self):
         return int(self.L.fnft_amd_inverse_plan_workspace_bytes(self.h))
@@ -859,10 +846,7 @@ class InversePlan:
 
     def finish(self, stream=0):
         """Waits for `stream`: (rc, status[batch], warnings[batch])."""
-        st = np.zeros(self.batch, np.int32)
-        wn = np.zeros(self.batch, np.int32)
-        rc = self.L.fnft_amd_inverse_plan_finish(self.h, C.c_void_p(stream), _ptr(st), _ptr(wn))
-        return int(rc), st, wn
+        return self._finish(stream)
 
 
 def nsev_opts(opts=None):
@@ -884,33 +868,18 @@ def nsev_opts(opts=None):
     return o
 
 
-class DiscSpecPlan:
+class DiscSpecPlan(_BatchPlan):
     """fnft_amd_discspec_plan_t: the discrete spectrum (NEWTON) of `batch` signals of D samples with K guesses each,
     one set of options (dict as for nsev_opts; None: the defaults with NEWTON), device-resident.  Raises RuntimeError
     (attribute rc) if the plan cannot be created."""
+    _DESTROY, _FINISH = "fnft_amd_discspec_plan_destroy", "fnft_amd_discspec_plan_finish"
 
     def __init__(self, D, K, batch=1, opts=None, device=0):
         self.L = load()
         self.D, self.K, self.batch = int(D), int(K), int(batch)
         self.opts = None if opts is None else (opts if isinstance(opts, NsevOpts) else nsev_opts(opts))
-        self.h = C.c_void_p()
-        rc = self.L.fnft_amd_discspec_plan_create(C.byref(self.h), self.D, self.K, self.batch,
-                                                  None if self.opts is None else C.byref(self.opts), int(device))
-        if rc != FNFT_SUCCESS:
-            err = RuntimeError("fnft_amd_discspec_plan_create rc=%d (%s)" % (rc, last_error()))
-            err.rc = int(rc)
-            raise err
-
-    def close(self):
-        if self.h:
-            self.L.fnft_amd_discspec_plan_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("fnft_amd_discspec_plan_create", self.D, self.K, self.batch,
+                     None if self.opts is None else C.byref(self.opts), int(device))
 
     def workspace_bytes(self):
         return int(self.L.fnft_amd_discspec_plan_workspace_bytes(self.h))
@@ -929,10 +898,7 @@ class DiscSpecPlan:
 
     def finish(self, stream=0):
         """Waits for `stream`: (rc, status[batch], K_out[batch])."""
-        st = np.zeros(self.batch, np.int32)
-        ko = np.zeros(self.batch, np.uint64)
-        rc = self.L.fnft_amd_discspec_plan_finish(self.h, C.c_void_p(stream), _ptr(st), _ptr(ko))
-        return int(rc), st, ko
+        return self._finish(stream, np.uint64)
 
 
 SLOW_DISCS = ("BO", "CF4_2", "CF4_3", "CF5_3", "CF6_4", "ES4", "TES4")
@@ -946,33 +912,18 @@ def slow_plan_chunks(D, M, batch=1):
     return int(L.value), int(nc)
 
 
-class SlowPlan:
+class SlowPlan(_BatchPlan):
     """fnft_amd_slow_plan_t: the continuous spectrum of `batch` signals of D samples on M grid points under one of the
     slow discretizations (SLOW_DISCS), one set of options (dict as for nsev_opts, or NsevOpts; None: the defaults with
     BO), device-resident.  Raises RuntimeError (attribute rc) if the plan cannot be created."""
+    _DESTROY, _FINISH = "fnft_amd_slow_plan_destroy", "fnft_amd_slow_plan_finish"
 
     def __init__(self, D, M, batch=1, opts=None, device=0):
         self.L = load()
         self.D, self.M, self.batch = int(D), int(M), int(batch)
         self.opts = None if opts is None else (opts if isinstance(opts, NsevOpts) else nsev_opts(opts))
-        self.h = C.c_void_p()
-        rc = self.L.fnft_amd_slow_plan_create(C.byref(self.h), self.D, self.M, self.batch,
-                                              None if self.opts is None else C.byref(self.opts), int(device))
-        if rc != FNFT_SUCCESS:
-            err = RuntimeError("fnft_amd_slow_plan_create rc=%d (%s)" % (rc, last_error()))
-            err.rc = int(rc)
-            raise err
-
-    def close(self):
-        if self.h:
-            self.L.fnft_amd_slow_plan_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("fnft_amd_slow_plan_create", self.D, self.M, self.batch,
+                     None if self.opts is None else C.byref(self.opts), int(device))
 
     @property
     def workspace_bytes(self):
@@ -1009,10 +960,7 @@ class SlowPlan:
     def finish(self, stream=None):
         """Waits for `stream` (None: the stream of the last __call__): (rc, status[batch], warnings[batch])."""
         s = getattr(self, "_stream", 0) if stream is None else (stream if isinstance(stream, int) else int(stream.cuda_stream))
-        st = np.zeros(self.batch, np.int32)
-        wn = np.zeros(self.batch, np.int32)
-        rc = self.L.fnft_amd_slow_plan_finish(self.h, C.c_void_p(s or None), _ptr(st), _ptr(wn))
-        return int(rc), st, wn
+        return self._finish(s or None)
 
 
 def nsev_slow(q, T, M, XI, kappa=1, discretization="BO", contspec_type="REFLECTION_COEFFICIENT", richardson=0):

@@ -2,6 +2,7 @@
 // include/fnft_amd.h plus the internal entries the C drivers call) over NftPlan<HipBackend>.  The kernels
 // are instantiated in hip_kernels_*.hip (see hip_be.h).  gfx950 only.
 #include <map>
+#include <memory>
 #include <mutex>
 #include <tuple>
 
@@ -105,7 +106,7 @@ void fa_pool_free(void *p)
 
 struct fnft_amd_plan {
     HipBackend be;
-    Plan *pl = nullptr;
+    std::unique_ptr<Plan> pl;   // after be: its arena hands the blocks back through be
     int device = 0;
     int nse_disc = 0;
     int kdv_disc = -1;   // >= 0: plan made by fnft_amd_kdvv_plan_create
@@ -169,6 +170,112 @@ static std::mutex g_cache_mtx;     // the two plan caches below
 static std::map<std::tuple<int, size_t, size_t, int, size_t>, fnft_amd_plan *> g_nsev_cache;   // (dev, D, M, disc, nskip)
 static std::map<std::tuple<int, size_t, size_t, int>, fnft_amd_plan *> g_kdvv_cache;           // (dev, D, M, disc)
 
+// ---- the parts of the three batched plans' entry points that do not depend on the plan ---------------------------------
+// One handle for the three batched plans: the back end, the plan core (NftInverseBatch, NftDiscSpecBatch,
+// NftSlowPlan), the device it lives on, the stream of its last call (destroy waits for it), the status words finish
+// reads back, and the lock that makes calls on one plan take turns.  The public opaque types add their few own fields.
+template <class CoreT> struct BatchHandle {
+    typedef CoreT Core;
+    HipBackend be;
+    std::unique_ptr<Core> core;   // after be: its arenas hand the blocks back through be
+    int device = 0;
+    hipStream_t last_stream = nullptr;
+    std::vector<int> st;
+    std::mutex mtx;
+};
+struct fnft_amd_inverse_plan : BatchHandle<NftInverseBatch<HipBackend>> {
+    int cstype = 0;
+    size_t K = 0;                 // fnft_amd_inverse_plan_create_discrete: bound states per signal (>= 1)
+};
+struct fnft_amd_discspec_plan : BatchHandle<NftDiscSpecBatch<HipBackend>> {
+    const unsigned long long *last_K = nullptr;   // d_K_out of the last call
+    std::vector<unsigned long long> kout;
+};
+struct fnft_amd_slow_plan : BatchHandle<NftSlowPlan<HipBackend>> {
+    std::vector<int> wn;
+};
+
+// create, first half: the handle and its core from the accepted sizes and options.  No core constructor makes a HIP call
+// (they size things and nothing else), so every size or option check of a create entry -- a core's too_large() included
+// -- returns its code on a machine without a GPU.  NULL: out of host memory.
+template <class H, class... A> static std::unique_ptr<H> batch_new(A &&...args)
+{
+    std::unique_ptr<H> h(new (std::nothrow) H());
+    if (h) h->core.reset(new (std::nothrow) typename H::Core(h->be, std::forward<A>(args)...));
+    if (h && !h->core) h.reset();
+    return h;
+}
+// create, second half: the first HIP call (the device), then the core's workspace
+template <class H> static FNFT_INT batch_init(H **plan, std::unique_ptr<H> h, int device)
+{
+    if (!h) return FNFT_EC_NOMEM;
+    DeviceGuard dg(device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    h->device = device;
+    const int rc = h->core->init();
+    if (rc != NFT_SUCCESS || h->be.failed) {
+        (void)h->be.sync();
+        h.reset();                // on the plan's device
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = h.release();
+    return FNFT_SUCCESS;
+}
+
+// destroy: the pool hands the plan's blocks to the next allocation, so nothing it enqueued may still be writing them
+static void plan_quiesce(hipStream_t last_stream)
+{
+    if (last_stream) (void)hipStreamSynchronize(last_stream);
+    (void)hipDeviceSynchronize();
+}
+template <class H> static void batch_destroy(H *plan)
+{
+    if (!plan) return;
+    {
+        DeviceGuard dg(plan->device);
+        plan_quiesce(plan->last_stream);
+        plan->core.reset();
+        plan->be.destroy_events();
+    }
+    delete plan;
+}
+
+// one call on a plan: its lock, its device, its stream.  last_stream != NULL (the *_device entries): the stream is also
+// the one destroy waits for, and the failure flag starts clear
+struct PlanCall {
+    std::lock_guard<std::mutex> lk;
+    DeviceGuard dg;
+    const bool ok;
+    PlanCall(std::mutex &m, int device, HipBackend &be, hipStream_t *last_stream, void *stream)
+        : lk(m), dg(device), ok(dg.ok)
+    {
+        if (!ok) return;
+        be.stream = (hipStream_t)stream;
+        if (last_stream) {
+            *last_stream = (hipStream_t)stream;
+            be.failed = false;
+        }
+    }
+};
+
+// finish: wait for the stream and read the status words (read: the core's own call, which fills plan->st), then every
+// signal's word through the plan's mapping to_status(b, word) -- which also stores the plan's second per-signal output
+template <class H, class Read, class Map>
+static FNFT_INT batch_finish(H *plan, void *stream, FNFT_INT *status, Read read, Map to_status)
+{
+    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    const int rc = read(*plan->core);
+    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
+    FNFT_INT first = FNFT_SUCCESS;
+    for (size_t b = 0; b < plan->st.size(); b++) {
+        const FNFT_INT s = to_status(b, plan->st[b]);
+        if (status) status[b] = s;
+        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
+    }
+    return first;
+}
+
 extern "C" {
 
 int fnft_amd_device_count(void)
@@ -202,7 +309,7 @@ FNFT_INT fnft_amd_plan_create_sub(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT
     P->device = device;
     P->nse_disc = (int)discretization;
     const size_t Dtree = (ups == 1) ? (size_t)D : 2 * Plan::sub_count((size_t)D, (size_t)nskip);
-    P->pl = new (std::nothrow) Plan(P->be, Dtree, M, batch, akns, nft_akns_degree(akns));
+    P->pl.reset(new (std::nothrow) Plan(P->be, Dtree, M, batch, akns, nft_akns_degree(akns)));
     if (!P->pl) { delete P; return FNFT_EC_NOMEM; }
     P->pl->set_front((size_t)D, (size_t)nskip, ups);
 #ifdef FNFT_AMD_ABLATION   // diagnostic builds only; the product library reads no environment variable
@@ -210,8 +317,6 @@ FNFT_INT fnft_amd_plan_create_sub(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT
 #endif
     const int rc = P->pl->init();
     if (rc != NFT_SUCCESS || P->be.failed) {
-        P->pl->destroy();
-        delete P->pl;
         delete P;
         return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
     }
@@ -225,13 +330,12 @@ void fnft_amd_plan_destroy(fnft_amd_plan_t *plan)
     if (!plan) return;
     DeviceGuard dg(plan->device);
     (void)hipDeviceSynchronize();
-    plan->pl->destroy();
+    plan->pl.reset();
     plan->be.destroy_events();
-    delete plan->pl;
     delete plan;
 }
 
-FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->pl->bytes : 0; }
+FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->pl->mem.bytes : 0; }
 
 int fnft_amd_plan_device(const fnft_amd_plan_t *plan) { return plan ? plan->device : -1; }
 
@@ -270,8 +374,7 @@ extern "C" int fnft_amd_debug_stamps(fnft_amd_plan_t *plan, int level, unsigned 
     DeviceGuard dg(plan->device);
     Plan &pl = *plan->pl;
     if (!pl.dbg_stamps) {
-        pl.dbg_stamps = (unsigned long long *)plan->be.alloc((size_t)4096 * 16 * 8);
-        if (!pl.dbg_stamps) return -1;
+        if (!pl.mem.get(pl.dbg_stamps, (size_t)4096 * 16)) return -1;
         (void)hipMemset(pl.dbg_stamps, 0, (size_t)4096 * 16 * 8);
     }
     pl.stamp_level = level;
@@ -407,13 +510,11 @@ FNFT_INT fnft_amd_kdvv_plan_create(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UIN
     P->device = device;
     P->nse_disc = -1;
     P->kdv_disc = kd;
-    P->pl = new (std::nothrow) Plan(P->be, D, M, batch, akns, nft_akns_degree(akns));
+    P->pl.reset(new (std::nothrow) Plan(P->be, D, M, batch, akns, nft_akns_degree(akns)));
     if (!P->pl) { delete P; return FNFT_EC_NOMEM; }
     P->pl->kdv = true;
     const int rc = P->pl->init();
     if (rc != NFT_SUCCESS || P->be.failed) {
-        P->pl->destroy();
-        delete P->pl;
         delete P;
         return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
     }
@@ -561,7 +662,6 @@ FNFT_INT fnft_amd_poly_fmult2x2_device(FNFT_UINT deg, FNFT_UINT n, const void *d
         *W_out = W;
         if (deg_out) *deg_out = pl.res_deg;
     }
-    pl.destroy();
     if (be.failed) return FNFT_EC_OTHER;
     return rc;
 }
@@ -795,10 +895,9 @@ extern "C" FNFT_INT fnft_amd__inverse_add_discrete(FNFT_UINT K, const FNFT_COMPL
         if (contspec_flag) {
             // the non-solitonic part of the potential contributes to the residues: a(lambda_k) of the seed, BO scheme
             NftDiscSpec<HipBackend> ds(be);
-            NftDiscSpec<HipBackend>::Prepared P;
+            NftDiscSpec<HipBackend>::Prepared P(be);
             rc = ds.prepare(D, q, T, D, (int)fnft_nse_discretization_2SPLIT4B, P, false);
             if (rc == FNFT_SUCCESS) rc = ds.scatter(P, K, bs.data(), acs.data(), ap.data(), bdummy.data(), true);
-            ds.release(P);
             if (rc != FNFT_SUCCESS || be.failed) return be.failed ? FNFT_EC_OTHER : rc;
         }
         for (size_t i = 0; i < K; i++) {
@@ -821,17 +920,6 @@ extern "C" FNFT_INT fnft_amd__inverse_add_discrete(FNFT_UINT K, const FNFT_COMPL
 // ---- batched, device-resident fnft_nsev_inverse (continuous part) ----------------------------------------------------
 // Argument checks follow fnft_nsev_inverse (fnft_nsev_inverse_host.c) in its order and with its codes; those that only
 // depend on sizes and options run at create time, before any HIP call.
-struct fnft_amd_inverse_plan {
-    HipBackend be;
-    NftInverseBatch<HipBackend> *inv = nullptr;
-    int device = 0;
-    int cstype = 0;
-    size_t K = 0;                 // fnft_amd_inverse_plan_create_discrete: bound states per signal (>= 1)
-    hipStream_t last_stream = nullptr;
-    std::vector<int> st;
-    std::mutex mtx;
-};
-
 static FNFT_INT inv_subroutine(const char *func, int line, FNFT_INT ec)
 {
     return fnft_amd__raise(-std::abs((int)ec), func, line, "Subroutine failure.");
@@ -865,62 +953,29 @@ static FNFT_INT inv_cstype(const char *func, const fnft_nsev_inverse_opts_t &o, 
     return FNFT_SUCCESS;
 }
 
+// what a *_device entry returns after its core's run(): a failure is raised in the name of the public entry
+static FNFT_INT batch_run_result(const HipBackend &be, int rc, const char *func, int line)
+{
+    if (be.failed) return FNFT_EC_OTHER;
+    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(func, line, rc);
+}
+
 // the plan and its workspace, once the options are accepted.  K = 0: no discrete part
 static FNFT_INT inv_plan_new(fnft_amd_inverse_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
                              const fnft_nsev_inverse_opts_t &o, int device, int cstype, FNFT_UINT K, int ds_mode,
                              int residues)
 {
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    fnft_amd_inverse_plan *P = new (std::nothrow) fnft_amd_inverse_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->device = device;
-    P->cstype = cstype;
-    P->K = K;
-    P->inv = new (std::nothrow) NftInverseBatch<HipBackend>(
-        P->be, (size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
-        o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0, (size_t)K, ds_mode, residues);
-    if (!P->inv) { delete P; return FNFT_EC_NOMEM; }
-    const int rc = P->inv->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        (void)P->be.sync();
-        delete P->inv;
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
-    }
-    *plan = P;
-    return FNFT_SUCCESS;
-}
-
-// one call on a plan: its lock, its device, its stream.  last_stream != NULL (the *_device entries): the stream is also
-// the one destroy waits for, and the failure flag starts clear
-struct PlanCall {
-    std::lock_guard<std::mutex> lk;
-    DeviceGuard dg;
-    const bool ok;
-    PlanCall(std::mutex &m, int device, HipBackend &be, hipStream_t *last_stream, void *stream)
-        : lk(m), dg(device), ok(dg.ok)
-    {
-        if (!ok) return;
-        be.stream = (hipStream_t)stream;
-        if (last_stream) {
-            *last_stream = (hipStream_t)stream;
-            be.failed = false;
-        }
-    }
-};
-
-// destroy: the pool hands the plan's blocks to the next allocation, so nothing it enqueued may still be writing them
-static void plan_quiesce(hipStream_t last_stream)
-{
-    if (last_stream) (void)hipStreamSynchronize(last_stream);
-    (void)hipDeviceSynchronize();
+    auto h = batch_new<fnft_amd_inverse_plan>((size_t)D, (size_t)M, (size_t)batch, cstype, (size_t)o.oversampling_factor,
+                                              o.discretization == fnft_nse_discretization_2SPLIT2_MODAL ? 1 : 0,
+                                              (size_t)K, ds_mode, residues);
+    if (h) { h->cstype = cstype; h->K = K; }
+    return batch_init(plan, std::move(h), device);
 }
 
 // step size and phase factor exactly as the host driver forms them (fnft_nsev_inverse_host.c)
 static FNFT_REAL inv_phase_factor(const fnft_amd_inverse_plan &plan, const FNFT_REAL *T, FNFT_REAL *eps_t_out)
 {
-    const size_t D = plan.inv->D;
+    const size_t D = plan.core->D;
     const FNFT_REAL eps_t = (T[1] - T[0]) / (D - 1);
     const FNFT_REAL pf_rho = -2.0 * (T[1] + eps_t * 0.5) + eps_t;
     const FNFT_REAL pf_b = -eps_t * D - (T[1] + eps_t * 0.5) - (T[0] - eps_t * 0.5) + eps_t;
@@ -949,21 +1004,11 @@ FNFT_INT fnft_amd_inverse_plan_create(fnft_amd_inverse_plan_t **plan, FNFT_UINT 
     return inv_plan_new(plan, D, M, batch, o, device, cstype, 0, 0, 0);
 }
 
-void fnft_amd_inverse_plan_destroy(fnft_amd_inverse_plan_t *plan)
-{
-    if (!plan) return;
-    {
-        DeviceGuard dg(plan->device);
-        plan_quiesce(plan->last_stream);
-        delete plan->inv;
-        plan->be.destroy_events();
-    }
-    delete plan;
-}
+void fnft_amd_inverse_plan_destroy(fnft_amd_inverse_plan_t *plan) { batch_destroy(plan); }
 
 FNFT_UINT fnft_amd_inverse_plan_workspace_bytes(const fnft_amd_inverse_plan_t *plan)
 {
-    return plan ? plan->inv->bytes : 0;
+    return plan ? plan->core->workspace_bytes() : 0;
 }
 
 FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void *d_contspec, const FNFT_REAL *XI,
@@ -982,9 +1027,8 @@ FNFT_INT fnft_amd_nsev_inverse_device(fnft_amd_inverse_plan_t *plan, const void 
     if (!call.ok) return FNFT_EC_OTHER;
     FNFT_REAL eps_t;
     const FNFT_REAL pf = inv_phase_factor(*plan, T, &eps_t);
-    const int rc = plan->inv->run((const cplx *)d_contspec, XI, (cplx *)d_q, eps_t, (int)kappa, pf);
-    if (plan->be.failed) return FNFT_EC_OTHER;
-    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+    const int rc = plan->core->run((const cplx *)d_contspec, XI, (cplx *)d_q, eps_t, (int)kappa, pf);
+    return batch_run_result(plan->be, rc, __func__, __LINE__);
 }
 
 // K > 0: the continuous part as above (M > 0) or none (M = 0), then the discrete part (fnft_nsev_inverse_host.c and
@@ -1033,7 +1077,7 @@ FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, co
 {
     SEAM_CHECK(!plan, plan);
     if (!plan->K) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));  // K = 0 plan
-    const size_t M = plan->inv->M;
+    const size_t M = plan->core->M;
     SEAM_CHECK(M > 0 && !d_contspec, contspec);                        // fnft_nsev_inverse_host.c, in its order
     SEAM_CHECK(M == 0 && d_contspec, M);                               // a contspec with M = 0 fails M < D there
     SEAM_CHECK(!d_q, q);
@@ -1051,50 +1095,31 @@ FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, co
     if (!call.ok) return FNFT_EC_OTHER;
     FNFT_REAL eps_t;
     const FNFT_REAL pf = inv_phase_factor(*plan, T, &eps_t);
-    const int rc = plan->inv->run_discrete((const cplx *)d_contspec, XI, (const cplx *)d_bound_states,
-                                           (const cplx *)d_normconsts_or_residues, (cplx *)d_q, T, eps_t, (int)kappa, pf);
-    if (plan->be.failed) return FNFT_EC_OTHER;
-    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+    const int rc = plan->core->run_discrete((const cplx *)d_contspec, XI, (const cplx *)d_bound_states,
+                                            (const cplx *)d_normconsts_or_residues, (cplx *)d_q, T, eps_t, (int)kappa, pf);
+    return batch_run_result(plan->be, rc, __func__, __LINE__);
 }
 
 FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *stream, FNFT_INT *status, int *warnings)
 {
     SEAM_CHECK(!plan, plan);
-    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
-    if (!call.ok) return FNFT_EC_OTHER;
-    const int rc = plan->inv->read_status(plan->st);
-    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
-    FNFT_INT first = FNFT_SUCCESS;
-    for (size_t b = 0; b < plan->st.size(); b++) {
-        const int h = plan->st[b];
-        // the drop-in, in its order: a bound state with Im <= 0 (bit 6) fails before anything runs; then
-        // fnft__nse_finvscatter with FNFT_EC_OTHER (bits 4, 5) and the discrete part on equal bound states (bit 7),
-        // both returned as subroutine failures
-        FNFT_INT s = FNFT_SUCCESS;
-        if (h & 64) s = FNFT_EC_SANITY_CHECK_FAILED;
-        else if (h & 48) s = -FNFT_EC_OTHER;
-        else if (h & 128) s = -FNFT_EC_SANITY_CHECK_FAILED;
-        if (status) status[b] = s;
-        if (warnings) warnings[b] = ((h & 8) && !(h & 64)) ? 1 : 0;
-        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
-    }
-    return first;
+    return batch_finish(
+        plan, stream, status, [&](NftInverseBatch<HipBackend> &c) { return c.read_status(plan->st); },
+        [&](size_t b, int h) -> FNFT_INT {
+            if (warnings) warnings[b] = ((h & 8) && !(h & 64)) ? 1 : 0;
+            // the drop-in, in its order: a bound state with Im <= 0 (bit 6) fails before anything runs; then
+            // fnft__nse_finvscatter with FNFT_EC_OTHER (bits 4, 5) and the discrete part on equal bound states (bit 7),
+            // both returned as subroutine failures
+            if (h & 64) return FNFT_EC_SANITY_CHECK_FAILED;
+            if (h & 48) return -FNFT_EC_OTHER;
+            if (h & 128) return -FNFT_EC_SANITY_CHECK_FAILED;
+            return FNFT_SUCCESS;
+        });
 }
 
 // ---- batched, device-resident discrete spectrum of fnft_nsev (NEWTON) ----------------------------------------------
 // Size and option checks follow fnft_nsev (fnft_nsev_host.c) in its order, with its codes and message texts, and run
 // before any HIP call.
-struct fnft_amd_discspec_plan {
-    HipBackend be;
-    NftDiscSpecBatch<HipBackend> *ds = nullptr;
-    int device = 0;
-    hipStream_t last_stream = nullptr;
-    const unsigned long long *last_K = nullptr;   // d_K_out of the last call
-    std::vector<int> st;
-    std::vector<unsigned long long> kout;
-    std::mutex mtx;
-};
-
 FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UINT D, FNFT_UINT K, FNFT_UINT batch,
                                        fnft_nsev_opts_t const *opts, int device)
 {
@@ -1124,44 +1149,17 @@ FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UIN
     if (K > NftDiscSpecBatch<HipBackend>::kMaxK || batch > NftDiscSpecBatch<HipBackend>::kMaxGroups / K)
         return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
                                "Not yet implemented (batched discrete spectrum: K > 65535 or batch*K > 2^31 - 1).");
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    fnft_amd_discspec_plan *P = new (std::nothrow) fnft_amd_discspec_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->device = device;
     NftDsOpts d;
     d.bsfilt = (int)o.bound_state_filtering; d.bsloc = 1; d.niter = o.niter; d.Dsub = 0;
     d.dstype = (int)o.discspec_type; d.nse_disc = disc; d.richardson = 0;
-    P->ds = new (std::nothrow) NftDiscSpecBatch<HipBackend>(P->be, (size_t)D, (size_t)K, (size_t)batch, d);
-    if (!P->ds) { delete P; return FNFT_EC_NOMEM; }
-    const int rc = P->ds->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        (void)P->be.sync();
-        P->ds->destroy();
-        delete P->ds;
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
-    }
-    *plan = P;
-    return FNFT_SUCCESS;
+    return batch_init(plan, batch_new<fnft_amd_discspec_plan>((size_t)D, (size_t)K, (size_t)batch, d), device);
 }
 
-void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
-{
-    if (!plan) return;
-    {
-        DeviceGuard dg(plan->device);
-        plan_quiesce(plan->last_stream);
-        plan->ds->destroy();
-        delete plan->ds;
-        plan->be.destroy_events();
-    }
-    delete plan;
-}
+void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan) { batch_destroy(plan); }
 
 FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan)
 {
-    return plan ? plan->ds->workspace_bytes() : 0;
+    return plan ? plan->core->workspace_bytes() : 0;
 }
 
 FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
@@ -1177,48 +1175,32 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
     PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
     if (!call.ok) return FNFT_EC_OTHER;
     plan->last_K = (const unsigned long long *)d_K_out;
-    const int rc = plan->ds->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
-                                 (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
-    if (plan->be.failed) return FNFT_EC_OTHER;
-    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+    const int rc = plan->core->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
+                                   (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
+    return batch_run_result(plan->be, rc, __func__, __LINE__);
 }
 
 FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *stream, FNFT_INT *status,
                                        FNFT_UINT *K_out)
 {
     SEAM_CHECK(!plan, plan);
-    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
-    if (!call.ok) return FNFT_EC_OTHER;
-    const int rc = plan->ds->read(plan->st, plan->kout, plan->last_K);
-    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
-    FNFT_INT first = FNFT_SUCCESS;
-    for (size_t b = 0; b < plan->st.size(); b++) {
-        const int h = plan->st[b];
-        // the drop-in on this signal alone, in its order: the MODAL step-size check of the transform it runs first
-        // (fnft__akns_fscatter.c:122-126), an empty bounding box, a' = 0 in the refinement or the residues -- each
-        // passed on as a subroutine failure (negative)
-        FNFT_INT s = FNFT_SUCCESS;
-        if (h & 1) s = -FNFT_EC_OTHER;
-        else if (h & 4) s = -FNFT_EC_INVALID_ARGUMENT;
-        else if (h & 2) s = -FNFT_EC_DIV_BY_ZERO;
-        if (status) status[b] = s;
-        if (K_out) K_out[b] = (FNFT_UINT)plan->kout[b];
-        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
-    }
-    return first;
+    return batch_finish(
+        plan, stream, status,
+        [&](NftDiscSpecBatch<HipBackend> &c) { return c.read(plan->st, plan->kout, plan->last_K); },
+        [&](size_t b, int h) -> FNFT_INT {
+            if (K_out) K_out[b] = (FNFT_UINT)plan->kout[b];
+            // the drop-in on this signal alone, in its order: the MODAL step-size check of the transform it runs first
+            // (fnft__akns_fscatter.c:122-126), an empty bounding box, a' = 0 in the refinement or the residues -- each
+            // passed on as a subroutine failure (negative)
+            if (h & 1) return -FNFT_EC_OTHER;
+            if (h & 4) return -FNFT_EC_INVALID_ARGUMENT;
+            if (h & 2) return -FNFT_EC_DIV_BY_ZERO;
+            return FNFT_SUCCESS;
+        });
 }
 
 // ---- batched, device-resident continuous spectrum of fnft_nsev under the slow discretizations ----------------------
 // Size and option checks run before any HIP call, with fnft_nsev's codes (fnft_nsev_host.c) in its order.
-struct fnft_amd_slow_plan {
-    HipBackend be;
-    NftSlowPlan<HipBackend> *sp = nullptr;
-    int device = 0;
-    hipStream_t last_stream = nullptr;
-    std::vector<int> st, wn;
-    std::mutex mtx;
-};
-
 FNFT_INT fnft_amd_slow_plan_create(fnft_amd_slow_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
                                    fnft_nsev_opts_t const *opts, int device)
 {
@@ -1244,43 +1226,14 @@ FNFT_INT fnft_amd_slow_plan_create(fnft_amd_slow_plan_t **plan, FNFT_UINT D, FNF
                               inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "opts->contspec_type")));
     const int scheme = nft_slow_scheme(disc);
     SEAM_CHECK(scheme >= 1 && scheme <= 4 && D <= 2, D);   // the resampler needs more than two samples, fnft__misc.c:331-332
-    fnft_amd_slow_plan *P = new (std::nothrow) fnft_amd_slow_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->sp = new (std::nothrow) NftSlowPlan<HipBackend>(P->be, (size_t)D, (size_t)M, (size_t)batch, so);
-    if (!P->sp) { delete P; return FNFT_EC_NOMEM; }
-    if (P->sp->too_large()) {
-        delete P->sp;
-        delete P;
+    auto h = batch_new<fnft_amd_slow_plan>((size_t)D, (size_t)M, (size_t)batch, so);
+    if (h && h->core->too_large())
         return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
                                "Not yet implemented (slow discretizations: more than 2^31 - 1 workgroups).");
-    }
-    DeviceGuard dg(device);
-    if (!dg.ok) { delete P->sp; delete P; return FNFT_EC_OTHER; }
-    P->device = device;
-    const int rc = P->sp->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        (void)P->be.sync();
-        P->sp->destroy();
-        delete P->sp;
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
-    }
-    *plan = P;
-    return FNFT_SUCCESS;
+    return batch_init(plan, std::move(h), device);
 }
 
-void fnft_amd_slow_plan_destroy(fnft_amd_slow_plan_t *plan)
-{
-    if (!plan) return;
-    {
-        DeviceGuard dg(plan->device);
-        plan_quiesce(plan->last_stream);
-        plan->sp->destroy();
-        delete plan->sp;
-        plan->be.destroy_events();
-    }
-    delete plan;
-}
+void fnft_amd_slow_plan_destroy(fnft_amd_slow_plan_t *plan) { batch_destroy(plan); }
 
 FNFT_UINT fnft_amd_slow_plan_chunks(FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch, FNFT_UINT *points_per_chunk)
 {
@@ -1293,7 +1246,7 @@ FNFT_UINT fnft_amd_slow_plan_chunks(FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch, F
 
 FNFT_UINT fnft_amd_slow_plan_workspace_bytes(const fnft_amd_slow_plan_t *plan)
 {
-    return plan ? plan->sp->workspace_bytes() : 0;
+    return plan ? plan->core->workspace_bytes() : 0;
 }
 
 FNFT_INT fnft_amd_nsev_slow_device(fnft_amd_slow_plan_t *plan, const void *d_q, const FNFT_REAL *T, void *d_contspec,
@@ -1307,27 +1260,20 @@ FNFT_INT fnft_amd_nsev_slow_device(fnft_amd_slow_plan_t *plan, const void *d_q, 
     SEAM_CHECK(kappa != +1 && kappa != -1, kappa);
     PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
     if (!call.ok) return FNFT_EC_OTHER;
-    const int rc = plan->sp->run((const cplx *)d_q, T, (cplx *)d_contspec, XI, (int)kappa);
-    if (plan->be.failed) return FNFT_EC_OTHER;
-    return rc == NFT_SUCCESS ? FNFT_SUCCESS : inv_subroutine(__func__, __LINE__, rc);
+    const int rc = plan->core->run((const cplx *)d_q, T, (cplx *)d_contspec, XI, (int)kappa);
+    return batch_run_result(plan->be, rc, __func__, __LINE__);
 }
 
 FNFT_INT fnft_amd_slow_plan_finish(fnft_amd_slow_plan_t *plan, void *stream, FNFT_INT *status, int *warnings)
 {
     SEAM_CHECK(!plan, plan);
-    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
-    if (!call.ok) return FNFT_EC_OTHER;
-    const int rc = plan->sp->read(plan->st, plan->wn);
-    if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
-    FNFT_INT first = FNFT_SUCCESS;
-    for (size_t b = 0; b < plan->st.size(); b++) {
-        // src/fnft_nsev.c:850-853 through the two callers that wrap it, as the fast plan reports it
-        const FNFT_INT s = (plan->st[b] & 1) ? -FNFT_EC_DIV_BY_ZERO : FNFT_SUCCESS;
-        if (status) status[b] = s;
-        if (warnings) warnings[b] = (plan->wn[b] & 4) ? 1 : 0;
-        if (s != FNFT_SUCCESS && first == FNFT_SUCCESS) first = s;
-    }
-    return first;
+    return batch_finish(
+        plan, stream, status, [&](NftSlowPlan<HipBackend> &c) { return c.read(plan->st, plan->wn); },
+        [&](size_t b, int h) -> FNFT_INT {
+            if (warnings) warnings[b] = (plan->wn[b] & 4) ? 1 : 0;
+            // src/fnft_nsev.c:850-853 through the two callers that wrap it, as the fast plan reports it
+            return (h & 1) ? -FNFT_EC_DIV_BY_ZERO : FNFT_SUCCESS;
+        });
 }
 
 FNFT_INT fnft_amd_poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const double *A,
@@ -1381,12 +1327,12 @@ FNFT_INT fnft__poly_roots_fasteigen(const FNFT_UINT deg, FNFT_COMPLEX const *con
     std::lock_guard<std::mutex> host_lk(host_call_mutex());
     HipBackend be;
     NftDiscSpec<HipBackend> ds(be);
-    cplx *d_coef = (cplx *)be.alloc((deg + 1) * sizeof(cplx));
-    if (!d_coef) return FNFT_EC_NOMEM;
+    DevArena<HipBackend> tmp(be);
+    cplx *d_coef = nullptr;
+    if (!tmp.get(d_coef, deg + 1)) return FNFT_EC_NOMEM;
     be.h2d(d_coef, p, (deg + 1) * sizeof(cplx));
     std::vector<std::complex<double>> z;
     int rc = ds.roots(d_coef, deg, z);
-    be.free(d_coef);
     if (be.failed) return FNFT_EC_OTHER;
     if (rc != NFT_SUCCESS) return -abs(rc);   // E_SUBROUTINE, :44-47
     for (size_t i = 0; i < deg; i++) roots[i] = z[i];
@@ -1421,7 +1367,7 @@ FNFT_INT fnft__nse_scatter_bound_states(const FNFT_UINT D, FNFT_COMPLEX const *c
     std::lock_guard<std::mutex> host_lk(host_call_mutex());
     HipBackend be;
     NftDiscSpec<HipBackend> ds(be);
-    NftDiscSpec<HipBackend>::Prepared P;
+    NftDiscSpec<HipBackend>::Prepared P(be);
     int rc;
     if (cf42) {
         // CF4_2 (the scatterer fnft_nsev uses with 4SPLIT4A/B, :188-197): q holds the D preprocessed samples, two per
@@ -1430,8 +1376,7 @@ FNFT_INT fnft__nse_scatter_bound_states(const FNFT_UINT D, FNFT_COMPLEX const *c
         P.Deff = D; P.Dsub = D / 2;
         P.T[0] = T[0]; P.T[1] = T[1];
         P.eps_t = (T[1] - T[0]) / (double)(D / 2 - 1);
-        P.d_in = (cplx *)be.alloc(D * sizeof(cplx));
-        rc = P.d_in ? NFT_SUCCESS : NFT_EC_NOMEM;
+        rc = P.mem.get(P.d_in, D) ? NFT_SUCCESS : NFT_EC_NOMEM;
         if (rc == NFT_SUCCESS) {
             be.h2d(P.d_in, q, D * sizeof(cplx));
             P.d_qpre = P.d_in;
@@ -1443,7 +1388,6 @@ FNFT_INT fnft__nse_scatter_bound_states(const FNFT_UINT D, FNFT_COMPLEX const *c
     if (rc == NFT_SUCCESS)
         rc = ds.scatter(P, K, (const std::complex<double> *)bound_states, (std::complex<double> *)a_vals,
                         (std::complex<double> *)aprime_vals, (std::complex<double> *)b, skip_b_flag != 0);
-    ds.release(P);
     if (be.failed) return FNFT_EC_OTHER;
     return rc;
 }
@@ -1459,11 +1403,12 @@ static int gridsearch_common(const size_t deg, const std::complex<double> *p, si
     const std::complex<double> W(std::cos(eps), std::sin(eps));
     HipBackend be;
     const size_t nblk = (M + 255) / 256, rings = paraherm ? 1 : 3;
-    cplx *vals = (cplx *)be.alloc(rings * M * sizeof(cplx)), *cand = (cplx *)be.alloc(M * sizeof(cplx));
-    cplx *out = (cplx *)be.alloc(M * sizeof(cplx));
-    int *keep = (int *)be.alloc(M * sizeof(int)), *bcnt = (int *)be.alloc(nblk * sizeof(int));
-    int *boff = (int *)be.alloc(nblk * sizeof(int)), *dstatus = (int *)be.alloc(4 * sizeof(int));
-    int rc = (vals && cand && out && keep && bcnt && boff && dstatus) ? FNFT_SUCCESS : FNFT_EC_NOMEM;
+    DevArena<HipBackend> tmp(be);
+    cplx *vals = nullptr, *cand = nullptr, *out = nullptr;
+    int *keep = nullptr, *bcnt = nullptr, *boff = nullptr, *dstatus = nullptr;
+    // no early return on a failed request: the back end's failure flag decides the code below, as for any other fault
+    int rc = (tmp.get(vals, rings * M) && tmp.get(cand, M) && tmp.get(out, M) && tmp.get(keep, M) && tmp.get(bcnt, nblk)
+              && tmp.get(boff, nblk) && tmp.get(dstatus, 4)) ? FNFT_SUCCESS : FNFT_EC_NOMEM;
     size_t nroots = 0;
     if (rc == FNFT_SUCCESS) {
         be.memset0(dstatus, 4 * sizeof(int));
@@ -1495,7 +1440,6 @@ static int gridsearch_common(const size_t deg, const std::complex<double> *p, si
             rc = be.sync();
         }
     }
-    be.free(vals); be.free(cand); be.free(out); be.free(keep); be.free(bcnt); be.free(boff); be.free(dstatus);
     if (be.failed) return FNFT_EC_OTHER;
     if (rc == FNFT_SUCCESS) *M_ptr = nroots;
     return rc;
@@ -1558,10 +1502,11 @@ FNFT_INT fnft__nse_scatter_matrix(const FNFT_UINT D, FNFT_COMPLEX const *const q
     const size_t L = nft_bs_chunk_len(D);
     const size_t nchunk = (D + L - 1) / L;
     const size_t w = derivative_flag ? 8 : 4;
-    cplx *dq = (cplx *)be.alloc(D * sizeof(cplx)), *dr = r ? (cplx *)be.alloc(D * sizeof(cplx)) : nullptr;
-    cplx *dl = (cplx *)be.alloc(K * sizeof(cplx)), *cm = (cplx *)be.alloc(K * nchunk * 8 * sizeof(cplx));
-    cplx *ds = (cplx *)be.alloc(K * w * sizeof(cplx));
-    int rc = (dq && dl && cm && ds && (!r || dr)) ? FNFT_SUCCESS : FNFT_EC_NOMEM;
+    DevArena<HipBackend> tmp(be);
+    cplx *dq = nullptr, *dr = nullptr, *dl = nullptr, *cm = nullptr, *ds = nullptr;
+    // no early return on a failed request: the back end's failure flag decides the code below, as for any other fault
+    int rc = (tmp.get(dq, D) && (!r || tmp.get(dr, D)) && tmp.get(dl, K) && tmp.get(cm, K * nchunk * 8)
+              && tmp.get(ds, K * w)) ? FNFT_SUCCESS : FNFT_EC_NOMEM;
     if (rc == FNFT_SUCCESS) {
         be.h2d(dq, q, D * sizeof(cplx));
         if (r) be.h2d(dr, r, D * sizeof(cplx));
@@ -1580,7 +1525,6 @@ FNFT_INT fnft__nse_scatter_matrix(const FNFT_UINT D, FNFT_COMPLEX const *const q
         be.d2h(result, ds, K * w * sizeof(cplx));
         rc = be.sync();
     }
-    be.free(dq); be.free(dr); be.free(dl); be.free(cm); be.free(ds);
     if (be.failed) return FNFT_EC_OTHER;
     return rc;
 }

@@ -4,6 +4,30 @@
 #pragma once
 #include "nft_plan.h"
 
+// the root of the tree to the caller: export, read back W, coefficients times 2^W if the caller takes no exponent.
+// use_status: wait through pl.read_status() (the scatterers: its bits are theirs to raise), else a plain sync
+template <class BE>
+int api_export_result(NftPlan<BE> &pl, std::complex<double> *result, size_t *deg_ptr, int32_t *W_ptr, bool use_status)
+{
+    BE &be = pl.be;
+    pl.export_tm();
+    const size_t cnt = 4 * (pl.res_deg + 1);
+    be.d2h(result, pl.tm_out, cnt * sizeof(cplx));
+    int W = 0;
+    be.d2h(&W, pl.wexp[pl.cur], sizeof(int));
+    int rc = use_status ? pl.read_status() : be.sync();
+    if (rc == -NFT_EC_OTHER) rc = NFT_EC_OTHER;  // raised by the scatterer itself
+    if (rc != NFT_SUCCESS) return rc;
+    *deg_ptr = pl.res_deg;
+    if (W_ptr) {
+        *W_ptr = W;
+    } else {  // caller asked for un-normalised coefficients
+        const double s = std::ldexp(1.0, W);
+        for (size_t i = 0; i < cnt; i++) result[i] *= s;
+    }
+    return NFT_SUCCESS;
+}
+
 // fnft__poly_fmult2x2, src/private/fnft__poly_fmult.c:381-546 (host buffers in and out)
 template <class BE>
 int api_poly_fmult2x2(BE &be, size_t *d, size_t n, std::complex<double> *p,
@@ -16,24 +40,7 @@ int api_poly_fmult2x2(BE &be, size_t *d, size_t n, std::complex<double> *p,
     int rc = pl.init();
     if (rc == NFT_SUCCESS) rc = pl.load_level0_from_host(p);
     if (rc == NFT_SUCCESS) rc = pl.run_tree();
-    if (rc == NFT_SUCCESS) {
-        pl.export_tm();
-        const size_t cnt = 4 * (pl.res_deg + 1);
-        be.d2h(result, pl.tm_out, cnt * sizeof(cplx));
-        int W = 0;
-        be.d2h(&W, pl.wexp[pl.cur], sizeof(int));
-        rc = be.sync();
-        if (rc == NFT_SUCCESS) {
-            *d = pl.res_deg;
-            if (W_ptr) {
-                *W_ptr = W;
-            } else {  // caller asked for un-normalised coefficients
-                const double s = std::ldexp(1.0, W);
-                for (size_t i = 0; i < cnt; i++) result[i] *= s;
-            }
-        }
-    }
-    pl.destroy();
+    if (rc == NFT_SUCCESS) rc = api_export_result(pl, result, d, W_ptr, false);
     return rc;
 }
 
@@ -47,37 +54,14 @@ int api_akns_fscatter(BE &be, size_t D, const std::complex<double> *q, const std
     if (deg0 == 0) return NFT_EC_INVALID_ARGUMENT;
     NftPlan<BE> pl(be, D, 0, 1, akns_disc, deg0);
     int rc = pl.init();
+    if (rc != NFT_SUCCESS) return rc;
     cplx *dq = nullptr, *dr = nullptr;
-    if (rc == NFT_SUCCESS) {
-        if (!pl.alloc(dq, D) || (r && !pl.alloc(dr, D))) rc = NFT_EC_NOMEM;
-    }
-    if (rc == NFT_SUCCESS) {
-        be.h2d(dq, q, D * sizeof(cplx));
-        if (r) be.h2d(dr, r, D * sizeof(cplx));
-        rc = pl.run_coeffs(dq, dr, eps_t, kappa);
-    }
+    if (!pl.mem.get(dq, D) || (r && !pl.mem.get(dr, D))) return NFT_EC_NOMEM;
+    be.h2d(dq, q, D * sizeof(cplx));
+    if (r) be.h2d(dr, r, D * sizeof(cplx));
+    rc = pl.run_coeffs(dq, dr, eps_t, kappa);
     if (rc == NFT_SUCCESS) rc = pl.run_tree();
-    if (rc == NFT_SUCCESS) {
-        pl.export_tm();
-        const size_t cnt = 4 * (pl.res_deg + 1);
-        be.d2h(result, pl.tm_out, cnt * sizeof(cplx));
-        int W = 0;
-        be.d2h(&W, pl.wexp[pl.cur], sizeof(int));
-        rc = pl.read_status();
-        if (rc == -NFT_EC_OTHER) rc = NFT_EC_OTHER;  // raised by akns_fscatter itself
-        if (rc == NFT_SUCCESS) {
-            *deg_ptr = pl.res_deg;
-            if (W_ptr) {
-                *W_ptr = W;
-            } else {
-                const double s = std::ldexp(1.0, W);
-                for (size_t i = 0; i < cnt; i++) result[i] *= s;
-            }
-        }
-    }
-    be.free(dq);
-    be.free(dr);
-    pl.destroy();
+    if (rc == NFT_SUCCESS) rc = api_export_result(pl, result, deg_ptr, W_ptr, true);
     return rc;
 }
 
@@ -95,32 +79,12 @@ int api_kdv_fscatter(BE &be, size_t D, const std::complex<double> *u, double eps
     pl.kdv = true;
     pl.want_real = real;
     int rc = pl.init();
+    if (rc != NFT_SUCCESS) return rc;
     cplx *dq = nullptr;
-    if (rc == NFT_SUCCESS && !pl.alloc(dq, D)) rc = NFT_EC_NOMEM;
-    if (rc == NFT_SUCCESS) {
-        be.h2d(dq, u, D * sizeof(cplx));
-        rc = pl.run_coeffs(dq, pl.rneg, eps_t, 1);
-    }
+    if (!pl.mem.get(dq, D)) return NFT_EC_NOMEM;
+    be.h2d(dq, u, D * sizeof(cplx));
+    rc = pl.run_coeffs(dq, pl.rneg, eps_t, 1);
     if (rc == NFT_SUCCESS) rc = pl.run_tree();
-    if (rc == NFT_SUCCESS) {
-        pl.export_tm();
-        const size_t cnt = 4 * (pl.res_deg + 1);
-        be.d2h(result, pl.tm_out, cnt * sizeof(cplx));
-        int W = 0;
-        be.d2h(&W, pl.wexp[pl.cur], sizeof(int));
-        rc = pl.read_status();
-        if (rc == -NFT_EC_OTHER) rc = NFT_EC_OTHER;
-        if (rc == NFT_SUCCESS) {
-            *deg_ptr = pl.res_deg;
-            if (W_ptr) {
-                *W_ptr = W;
-            } else {
-                const double s = std::ldexp(1.0, W);
-                for (size_t i = 0; i < cnt; i++) result[i] *= s;
-            }
-        }
-    }
-    be.free(dq);
-    pl.destroy();
+    if (rc == NFT_SUCCESS) rc = api_export_result(pl, result, deg_ptr, W_ptr, true);
     return rc;
 }

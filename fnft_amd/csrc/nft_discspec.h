@@ -99,20 +99,22 @@ public:
 
     // one preprocessed signal on the device
     struct Prepared {
+        DevArena<BE> mem;             // owns d_in
         std::unique_ptr<NftPlan<BE>> pl;
-        cplx *d_in = nullptr;         // uploaded samples (owned)
+        cplx *d_in = nullptr;         // uploaded samples
         const cplx *d_qpre = nullptr; // preprocessed samples (d_in or the plan's buffer)
         std::vector<cd> h_qpre;       // host copy (bounding box)
         size_t Deff = 0, Dsub = 0;
         int ups = 1, deg0 = 0;
         double T[2] = {0, 0}, eps_t = 0;
         bool coeffs_done = false;
+        explicit Prepared(BE &be_) : mem(be_) {}
     };
+    // before the end of P's scope: its device memory back now
     void release(Prepared &P)
     {
-        if (P.pl) P.pl->destroy();
         P.pl.reset();
-        be.free(P.d_in);
+        P.mem.clear();
         P.d_in = nullptr;
     }
 
@@ -148,8 +150,7 @@ public:
         }
         int rc = NFT_SUCCESS;
         if (!need_tree && P.ups == 1) {
-            P.d_in = (cplx *)be.alloc(Din * sizeof(cplx));
-            if (!P.d_in) return NFT_EC_NOMEM;
+            if (!P.mem.get(P.d_in, Din)) return NFT_EC_NOMEM;
             be.h2d(P.d_in, src, Din * sizeof(cplx));
             P.d_qpre = P.d_in;
             P.h_qpre.assign(src, src + Din);
@@ -159,8 +160,7 @@ public:
         P.pl->set_front(Din, P.ups == 1 ? 1 : nskip, P.ups);
         rc = P.pl->init();
         if (rc != NFT_SUCCESS) return rc;
-        P.d_in = (cplx *)be.alloc(Din * sizeof(cplx));
-        if (!P.d_in) return NFT_EC_NOMEM;
+        if (!P.mem.get(P.d_in, Din)) return NFT_EC_NOMEM;
         be.h2d(P.d_in, src, Din * sizeof(cplx));
         double Tfront[2] = {T[0], P.ups == 1 ? P.T[1] : T[1]}, Tsub[2];
         rc = P.pl->run_front(P.d_in, Tfront, +1, Tsub);   // resampling (4SPLIT) + level 0 of the tree
@@ -194,43 +194,34 @@ public:
         B.L = (int)L;
         B.nchunk = (int)((P.Deff + L - 1) / L);
         const size_t Dg = P.Deff / (size_t)P.ups;
-        cplx *d_lam = (cplx *)be.alloc(K * sizeof(cplx));
-        cplx *d_out = (cplx *)be.alloc(3 * K * sizeof(cplx));
-        cplx *cm = (cplx *)be.alloc(K * (size_t)B.nchunk * 8 * sizeof(cplx));
-        cplx *bnd = (cplx *)be.alloc(K * (size_t)(B.nchunk + 1) * 2 * sizeof(cplx));
-        cplx *bndp = nullptr, *PHI = nullptr, *best = nullptr;
-        bool ok = d_lam && d_out && cm && bnd;
+        DevArena<BE> tmp(be);
+        cplx *d_lam = nullptr, *d_out = nullptr, *cm = nullptr, *bnd = nullptr, *bndp = nullptr, *PHI = nullptr, *best = nullptr;
+        bool ok = tmp.get(d_lam, K) && tmp.get(d_out, 3 * K) && tmp.get(cm, K * (size_t)B.nchunk * 8)
+                  && tmp.get(bnd, K * (size_t)(B.nchunk + 1) * 2);
+        if (!skip_b)
+            ok = ok && tmp.get(bndp, K * (size_t)(B.nchunk + 1) * 2) && tmp.get(PHI, K * (Dg + 1) * 2)
+                 && tmp.get(best, K * (size_t)B.nchunk * 2);
+        if (!ok) return NFT_EC_NOMEM;
+        be.h2d(d_lam, lam, K * sizeof(cplx));
+        B.lam = d_lam; B.cm = cm; B.bnd = bnd; B.bndp = bndp; B.PHI = PHI; B.best = best;
+        B.a = d_out; B.aprime = d_out + K; B.b = d_out + 2 * K;
+        const int gx = (B.nchunk + 63) / 64;
+        nft_bs_forward(be, gx, (int)K, B);
         if (!skip_b) {
-            bndp = (cplx *)be.alloc(K * (size_t)(B.nchunk + 1) * 2 * sizeof(cplx));
-            PHI = (cplx *)be.alloc(K * (Dg + 1) * 2 * sizeof(cplx));
-            best = (cplx *)be.alloc(K * (size_t)B.nchunk * 2 * sizeof(cplx));
-            ok = ok && bndp && PHI && best;
+            be.template run<KBsPhi>(gx, (int)K, B);
+            be.template run<KBsChunk<true>>(gx, (int)K, B);
+            be.template run<KBsCombine<true>>((int)K, 1, B);
+            be.template run<KBsMetric>(gx, (int)K, B);
+            be.template run<KBsPick>((int)K, 1, B);
         }
-        int rc = ok ? NFT_SUCCESS : NFT_EC_NOMEM;
-        if (ok) {
-            be.h2d(d_lam, lam, K * sizeof(cplx));
-            B.lam = d_lam; B.cm = cm; B.bnd = bnd; B.bndp = bndp; B.PHI = PHI; B.best = best;
-            B.a = d_out; B.aprime = d_out + K; B.b = d_out + 2 * K;
-            const int gx = (B.nchunk + 63) / 64;
-            nft_bs_forward(be, gx, (int)K, B);
-            if (!skip_b) {
-                be.template run<KBsPhi>(gx, (int)K, B);
-                be.template run<KBsChunk<true>>(gx, (int)K, B);
-                be.template run<KBsCombine<true>>((int)K, 1, B);
-                be.template run<KBsMetric>(gx, (int)K, B);
-                be.template run<KBsPick>((int)K, 1, B);
-            }
-            std::vector<cd> h(3 * K);
-            be.d2h(h.data(), d_out, (skip_b ? 2 : 3) * K * sizeof(cplx));
-            rc = be.sync();
-            for (size_t i = 0; i < K; i++) {
-                a[i] = h[i];
-                ap[i] = h[K + i];
-                if (!skip_b) b[i] = h[2 * K + i];
-            }
+        std::vector<cd> h(3 * K);
+        be.d2h(h.data(), d_out, (skip_b ? 2 : 3) * K * sizeof(cplx));
+        const int rc = be.sync();
+        for (size_t i = 0; i < K; i++) {
+            a[i] = h[i];
+            ap[i] = h[K + i];
+            if (!skip_b) b[i] = h[2 * K + i];
         }
-        be.free(d_lam); be.free(d_out); be.free(cm); be.free(bnd);
-        be.free(bndp); be.free(PHI); be.free(best);
         return rc;
     }
 
@@ -293,19 +284,17 @@ public:
         // segments of the two O(n^2) kernels: about BE::kTargetWorkgroups (2048) workgroups of 256 lanes per launch.  The segment arrays
         // hold kSegCap values per estimate; with fewer estimates left, a sweep uses more segments.
         constexpr size_t kSegCap = 16;
-        cplx *zbuf[2] = {(cplx *)be.alloc(n * sizeof(cplx)), (cplx *)be.alloc(n * sizeof(cplx))};
-        int *ibuf[2] = {(int *)be.alloc(n * sizeof(int)), (int *)be.alloc(n * sizeof(int))};
-        A.pp = (cplx *)be.alloc(kSegCap * n * sizeof(cplx));
-        A.pd = (cplx *)be.alloc(kSegCap * n * sizeof(cplx));
-        A.ps = (cplx *)be.alloc(kSegCap * n * sizeof(cplx));
-        A.pe = (double *)be.alloc(kSegCap * n * sizeof(double));
-        A.hit = (int *)be.alloc(n * sizeof(int));
-        // {bits of the largest correction, number of estimates that moved}
-        unsigned long long *d_state = (unsigned long long *)be.alloc(2 * sizeof(unsigned long long));
+        DevArena<BE> tmp(be);
+        cplx *zbuf[2] = {nullptr, nullptr};
+        int *ibuf[2] = {nullptr, nullptr};
+        // d_state: {bits of the largest correction, number of estimates that moved}
+        unsigned long long *d_state = nullptr;
+        if (!(tmp.get(zbuf[0], n) && tmp.get(zbuf[1], n) && tmp.get(ibuf[0], n) && tmp.get(ibuf[1], n)
+              && tmp.get(A.pp, kSegCap * n) && tmp.get(A.pd, kSegCap * n) && tmp.get(A.ps, kSegCap * n)
+              && tmp.get(A.pe, kSegCap * n) && tmp.get(A.hit, n) && tmp.get(d_state, 2)))
+            rc = NFT_EC_NOMEM;
         A.maxcorr = d_state;
         A.cnt = (int *)(d_state + 1);
-        if (!zbuf[0] || !zbuf[1] || !ibuf[0] || !ibuf[1] || !A.pp || !A.pd || !A.ps || !A.pe || !A.hit || !d_state)
-            rc = NFT_EC_NOMEM;
         int cur = 0, icur = 0;
         double mc = 1.0;
         size_t na = n;
@@ -391,8 +380,6 @@ public:
                 rc = be.sync();
             }
         }
-        be.free(zbuf[0]); be.free(zbuf[1]); be.free(ibuf[0]); be.free(ibuf[1]);
-        be.free(A.pp); be.free(A.pd); be.free(A.ps); be.free(A.pe); be.free(A.hit); be.free(d_state);
         last_root_corr = mc;
         if (rc == NFT_SUCCESS && !(mc < kAberthTol)) {
             // the sweep limit was reached: the reference's QR (eiscor) reports non-convergence as an error of
@@ -527,7 +514,7 @@ public:
     int run(size_t D, const cd *q, const double T[2], const NftDsOpts &o, size_t *K_ptr, cd *bound_states,
             cd *normconsts_or_residues)
     {
-        Prepared full, sub;
+        Prepared full(be), sub(be);
         std::vector<cd> bs, nc, ap;
         NftDsOpts ob = o;
         NftDsClock clk;
@@ -564,7 +551,7 @@ public:
         }
         // Richardson extrapolation of the discrete spectrum, :340-364, :376-392, :406-441
         if (rc == NFT_SUCCESS && o.richardson && !bs.empty()) {
-            Prepared half;
+            Prepared half(be);
             std::vector<cd> bs_s(bs), nc_s, ap_s;
             rc = prepare(D, q, T, D / 2, o.nse_disc, half, false);
             if (rc == NFT_SUCCESS) rc = base(half, ob, 1, bs_s, normconsts_or_residues ? &nc_s : nullptr, &ap_s);
@@ -591,9 +578,7 @@ public:
                     }
                 }
             }
-            release(half);
         }
-        release(full);
         if (rc != NFT_SUCCESS) return rc;
         const size_t K = bs.size();
         std::copy(bs.begin(), bs.end(), bound_states);

@@ -13,6 +13,7 @@
 template <class BE> class NftDiscSpecBatch {
 public:
     BE &be;
+    DevArena<BE> mem;                 // owns lam, box, status, phi
     const size_t D, K, batch;
     const NftDsOpts o;
     int ups = 1, deg0 = 0, akns = -1;
@@ -24,13 +25,12 @@ public:
     int *status = nullptr;            // batch
     cplx *phi = nullptr;              // slab * K * sphi
     size_t slab = 0, sphi = 0;        // signals per launch of the norming kernel; phi values per (signal, eigenvalue)
-    size_t bytes = 0;
     static constexpr size_t kMaxK = 65535;                      // the merge is one lane's O(K^2) loop per signal
     static constexpr size_t kMaxGroups = 0x7fffffff;            // batch*K workgroups on grid.x
     static constexpr size_t kPhiBytes = (size_t)256 << 20;      // phi workspace of one norming launch
 
     NftDiscSpecBatch(BE &be_, size_t D_, size_t K_, size_t batch_, const NftDsOpts &o_)
-        : be(be_), D(D_), K(K_), batch(batch_), o(o_)
+        : be(be_), mem(be_), D(D_), K(K_), batch(batch_), o(o_)
     {
         akns = nft_nse_to_akns(o.nse_disc);
         ups = nft_nse_upsampling(o.nse_disc);
@@ -40,15 +40,6 @@ public:
         g = (g + (size_t)ups - 1) / (size_t)ups * (size_t)ups;
         G = (int)g;
         sphi = ((size_t)G / (size_t)ups + 1) * (size_t)kDsLanes * 2;
-    }
-
-    template <class T> bool alloc(T *&p, size_t count)
-    {
-        const size_t b = count * sizeof(T);
-        p = (T *)be.alloc(b ? b : 16);
-        if (!p) return false;
-        bytes += b;
-        return true;
     }
 
     int init()
@@ -66,19 +57,15 @@ public:
         slab = kPhiBytes / per_signal;
         if (slab < 1) slab = 1;
         if (slab > batch) slab = batch;
-        bool ok = alloc(lam, batch * K) && alloc(box, batch * 4) && alloc(status, batch) && alloc(phi, slab * K * sphi);
+        const bool ok = mem.get(lam, batch * K) && mem.get(box, batch * 4) && mem.get(status, batch)
+                        && mem.get(phi, slab * K * sphi);
         return ok ? NFT_SUCCESS : NFT_EC_NOMEM;
     }
 
-    void destroy()
-    {
-        if (front) front->destroy();
-        front.reset();
-        be.free(lam); be.free(box); be.free(status); be.free(phi);
-        lam = nullptr; box = nullptr; status = nullptr; phi = nullptr;
-    }
+    // the workspace back before the plan goes out of scope (the destructor does the same); init() again before reuse
+    void destroy() { front.reset(); mem.clear(); }
 
-    size_t workspace_bytes() const { return bytes + (front ? front->bytes : 0); }
+    size_t workspace_bytes() const { return mem.bytes + (front ? front->mem.bytes : 0); }
 
     // enqueues everything; waits for nothing.  d_nc may be NULL (no norming constants / residues)
     int run(const cplx *d_q, const double T[2], const cplx *d_guess, cplx *d_bs, cplx *d_nc,

@@ -9,6 +9,7 @@
 #include <complex>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -41,27 +42,33 @@ public:
     static constexpr size_t kLeaf = 256;
     static constexpr size_t kOneLaunchMaxDeg = 1024;   // products up to this degree: KPeelProduct
     BE &be;
+    DevArena<BE> mem;            // owns the status words and the work arrays
     double eps_t;
     int kappa, modal;
     size_t batch = 1;
     int rc = NFT_SUCCESS;
     int *d_status = nullptr;     // max(4, batch) ints: signal s's status at d_status[s]
-    std::map<size_t, NftPlan<BE> *> plans;
+    std::map<size_t, std::unique_ptr<NftPlan<BE>>> plans;
     struct Work { cplx *T2i = nullptr, *T1 = nullptr, *T1i = nullptr; };
     std::vector<Work> work;
 
-    NftLayerPeelingDev(BE &b, double eps, int kap, int is_modal) : be(b), eps_t(eps), kappa(kap), modal(is_modal) {}
+    NftLayerPeelingDev(BE &b, double eps, int kap, int is_modal)
+        : be(b), mem(b), eps_t(eps), kappa(kap), modal(is_modal) {}
     size_t status_words() const { return std::max<size_t>(4, batch); }
-    ~NftLayerPeelingDev() { destroy(); }
+    // everything back, the object stays usable: the resident peeler of the host-pointer entries is emptied and reused
     void destroy()
     {
-        for (auto &kv : plans) { kv.second->destroy(); delete kv.second; }
         plans.clear();
-        for (auto &w : work) { be.free(w.T2i); be.free(w.T1); be.free(w.T1i); }
         work.clear();
         work_deg = 0;
-        be.free(d_status);
+        mem.clear();
         d_status = nullptr;
+    }
+    size_t workspace_bytes() const
+    {
+        size_t b = mem.bytes;
+        for (const auto &kv : plans) b += kv.second->mem.bytes;
+        return b;
     }
     // status word, work arrays for a transfer matrix of degree deg (kept and reused by later calls of the same or a
     // smaller size: depth 0 is always the largest)
@@ -69,22 +76,18 @@ public:
     int init(size_t deg)
     {
         rc = NFT_SUCCESS;
-        if (!d_status) {
-            d_status = (int *)be.alloc(status_words() * sizeof(int));
-            if (!d_status) return NFT_EC_NOMEM;
-        }
+        if (!d_status && !mem.get(d_status, status_words())) return NFT_EC_NOMEM;
         be.memset0(d_status, status_words() * sizeof(int));
         if (deg > work_deg) {
-            for (auto &w : work) { be.free(w.T2i); be.free(w.T1); be.free(w.T1i); }
+            for (auto &w : work) { mem.give_back(w.T2i); mem.give_back(w.T1); mem.give_back(w.T1i); }
             work.clear();
             work_deg = 0;
             for (size_t d = deg; d > kLeaf; d /= 2) {
                 Work w;
-                w.T2i = (cplx *)be.alloc(batch * 4 * (d + 1) * sizeof(cplx));
-                w.T1 = (cplx *)be.alloc(batch * 4 * (2 * d + 1) * sizeof(cplx));
-                w.T1i = (cplx *)be.alloc(batch * 4 * (d / 2 + 1) * sizeof(cplx));
-                work.push_back(w);
-                if (!w.T2i || !w.T1 || !w.T1i) return NFT_EC_NOMEM;
+                const bool ok = mem.get(w.T2i, batch * 4 * (d + 1)) && mem.get(w.T1, batch * 4 * (2 * d + 1))
+                                && mem.get(w.T1i, batch * 4 * (d / 2 + 1));
+                work.push_back(w);   // an incomplete set too: the next call gives it back
+                if (!ok) return NFT_EC_NOMEM;
                 // the upper half of T2i (coefficients 0 .. d/2 - 1 of every entry) is never written: zero once
                 be.memset0(w.T2i, batch * 4 * (d + 1) * sizeof(cplx));
             }
@@ -95,13 +98,12 @@ public:
     NftPlan<BE> *plan_for(size_t deg)
     {
         auto it = plans.find(deg);
-        if (it != plans.end()) return it->second;
-        NftPlan<BE> *pl = new (std::nothrow) NftPlan<BE>(be, 2, 0, batch, -1, (int)deg);
+        if (it != plans.end()) return it->second.get();
+        std::unique_ptr<NftPlan<BE>> pl(new (std::nothrow) NftPlan<BE>(be, 2, 0, batch, -1, (int)deg));
         if (!pl) { rc = NFT_EC_NOMEM; return nullptr; }
         const int r = pl->init();
-        if (r != NFT_SUCCESS) { rc = r; pl->destroy(); delete pl; return nullptr; }
-        plans[deg] = pl;
-        return pl;
+        if (r != NFT_SUCCESS) { rc = r; return nullptr; }
+        return (plans[deg] = std::move(pl)).get();
     }
     // every plan and work array a peeling of degree deg will use (the batched call allocates nothing while it runs)
     int prepare(size_t deg)
@@ -180,13 +182,13 @@ public:
     int run_host(size_t deg, const std::complex<double> *tm, std::complex<double> *q)
     {
         int r = init(deg);
-        cplx *dT = (cplx *)be.alloc(4 * (deg + 1) * sizeof(cplx)), *dq = (cplx *)be.alloc(deg * sizeof(cplx));
-        if (r == NFT_SUCCESS && (!dT || !dq)) r = NFT_EC_NOMEM;
-        if (r == NFT_SUCCESS) {
-            be.h2d(dT, tm, 4 * (deg + 1) * sizeof(cplx));
-            peel(deg, dT, deg + 1, 0, nullptr, 0, 0, dq, 0);
-            r = rc;
-        }
+        if (r != NFT_SUCCESS) return r;
+        DevArena<BE> tmp(be);
+        cplx *dT = nullptr, *dq = nullptr;
+        if (!(tmp.get(dT, 4 * (deg + 1)) && tmp.get(dq, deg))) return NFT_EC_NOMEM;
+        be.h2d(dT, tm, 4 * (deg + 1) * sizeof(cplx));
+        peel(deg, dT, deg + 1, 0, nullptr, 0, 0, dq, 0);
+        r = rc;
         if (r == NFT_SUCCESS) {
             int hst[4] = {0, 0, 0, 0};
             be.d2h(q, dq, deg * sizeof(cplx));
@@ -194,7 +196,6 @@ public:
             r = be.sync();
             if (r == NFT_SUCCESS && (hst[0] & 48)) r = NFT_EC_OTHER;      // :173-176 (bit 5: a leaf gave up waiting)
         }
-        be.free(dT); be.free(dq);
         return r;      // plans and work arrays stay for the next call (destroy() releases them)
     }
 };
@@ -203,15 +204,15 @@ template <class BE> class NftInverseDev {
 public:
     typedef std::complex<double> cd;
     BE &be;
-    NftPlan<BE> pl;
+    NftPlan<BE> pl;              // twiddle tables only
+    DevArena<BE> mem;            // owns the DFT workspace below; the entry points' temporaries have arenas of their own
     size_t Lcap = 0;
     cplx *dY = nullptr, *dV = nullptr;
     int *dstatus = nullptr;
     double *dacc = nullptr;
     size_t acc_cap = 0;
 
-    explicit NftInverseDev(BE &b) : be(b), pl(b, 2, 0, 1, 0, 1) {}   // only the twiddle tables of the plan are used
-    ~NftInverseDev() { destroy(); }
+    explicit NftInverseDev(BE &b) : be(b), pl(b), mem(b) {}
 
     static size_t dft_L(size_t n)
     {
@@ -224,22 +225,13 @@ public:
     {
         const size_t L = dft_L(nmax);
         if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-        bool ok = pl.alloc(pl.twtab, (size_t)2 * kMaxTwTable) && pl.alloc(pl.twlo, kTwLoEntries);
-        ok = ok && pl.alloc(dY, L) && pl.alloc(dV, L) && pl.alloc(dstatus, 4);
         acc_cap = (nmax + 255) / 256;
-        ok = ok && pl.alloc(dacc, acc_cap);
-        if (!ok) return NFT_EC_NOMEM;
+        if (!(pl.init_twiddles_only() && mem.get(dY, L) && mem.get(dV, L) && mem.get(dstatus, 4)
+              && mem.get(dacc, acc_cap)))
+            return NFT_EC_NOMEM;
         Lcap = L;
-        pl.upload_twiddles();
         be.memset0(dstatus, 4 * sizeof(int));
         return NFT_SUCCESS;
-    }
-    void destroy()
-    {
-        be.free(dY); be.free(dV); be.free(dstatus); be.free(dacc);
-        be.free(pl.twtab); be.free(pl.twlo);
-        dY = dV = nullptr; dstatus = nullptr; dacc = nullptr;
-        pl.twtab = nullptr; pl.twlo = nullptr;
     }
     // out[k] = sum_n in[n] exp(sign * 2 pi i n k / n), un-normalised (fft_wrapper_execute_plan)
     int dft(const cplx *d_in, cplx *d_out, size_t n, int sign)
@@ -305,18 +297,16 @@ public:
         const size_t Mf = specfact_len(deg, oversampling);
         int rc = init(Mf);
         if (rc != NFT_SUCCESS) return rc;
+        DevArena<BE> tmp(be);
         cplx *dp = nullptr, *dr = nullptr, *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
-        const bool ok = pl.alloc(dp, deg + 1) && pl.alloc(dr, deg + 1) && pl.alloc(w0, Mf) && pl.alloc(w1, Mf) && pl.alloc(w2, Mf);
-        rc = ok ? NFT_SUCCESS : NFT_EC_NOMEM;
-        if (ok) {
-            be.h2d(dp, poly, (deg + 1) * sizeof(cplx));
-            rc = specfact(deg, dp, dr, oversampling, kappa, w0, w1, w2, warn);
-            if (rc == NFT_SUCCESS) {
-                be.d2h(result, dr, (deg + 1) * sizeof(cplx));
-                rc = be.sync();
-            }
+        if (!(tmp.get(dp, deg + 1) && tmp.get(dr, deg + 1) && tmp.get(w0, Mf) && tmp.get(w1, Mf) && tmp.get(w2, Mf)))
+            return NFT_EC_NOMEM;
+        be.h2d(dp, poly, (deg + 1) * sizeof(cplx));
+        rc = specfact(deg, dp, dr, oversampling, kappa, w0, w1, w2, warn);
+        if (rc == NFT_SUCCESS) {
+            be.d2h(result, dr, (deg + 1) * sizeof(cplx));
+            rc = be.sync();
         }
-        be.free(dp); be.free(dr); be.free(w0); be.free(w1); be.free(w2);
         return rc;
     }
 
@@ -337,14 +327,15 @@ public:
         int rc = init(std::max(M, Mf));
         if (rc != NFT_SUCCESS) return rc;
         const double eps_t = (T[1] - T[0]) / (double)(D - 1);
+        DevArena<BE> tmp(be);
         cplx *dc = nullptr, *dr = nullptr, *db = nullptr, *da = nullptr, *dbs = nullptr;
         cplx *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
-        bool ok = pl.alloc(dc, M) && pl.alloc(dr, M) && pl.alloc(db, std::max(M, deg + 1)) && pl.alloc(da, deg + 1)
-                  && pl.alloc(dbs, K ? K : 1);
-        if (need_sf) ok = ok && pl.alloc(w0, Mf) && pl.alloc(w1, Mf) && pl.alloc(w2, Mf);
-        rc = ok ? NFT_SUCCESS : NFT_EC_NOMEM;
+        bool ok = tmp.get(dc, M) && tmp.get(dr, M) && tmp.get(db, std::max(M, deg + 1)) && tmp.get(da, deg + 1)
+                  && tmp.get(dbs, K ? K : 1);
+        if (need_sf) ok = ok && tmp.get(w0, Mf) && tmp.get(w1, Mf) && tmp.get(w2, Mf);
         std::vector<cd> hb, ha;
         for (size_t i = 0; i < 4 * (deg + 1); i++) tm[i] = 0.0;
+        if (!ok) return NFT_EC_NOMEM;
         if (rc == NFT_SUCCESS && cstype != 2) {
             // :251-296 (and :1013-1033 for the reflection coefficient): phases off, FFT order
             const double eps_xi = (XI[1] - XI[0]) / (double)(M - 1);
@@ -439,7 +430,6 @@ public:
                     tm[3 * (deg + 1) + i] = ha[D - 1 - i];
                 }
         }
-        be.free(dc); be.free(dr); be.free(db); be.free(da); be.free(dbs); be.free(w0); be.free(w1); be.free(w2);
         return rc;
     }
 
@@ -451,55 +441,47 @@ public:
         const double eps_t = (T[1] - T[0]) / (double)(D - 1);
         InvDsParams P;
         std::memset(&P, 0, sizeof(P));
+        DevArena<BE> tmp(be);
         cplx *dbs = nullptr, *dnc = nullptr, *dq = nullptr, *work = nullptr;
-        bool ok = pl.alloc(dbs, K) && pl.alloc(dnc, K) && pl.alloc(dq, D) && pl.alloc(work, (mode ? 2 : 1) * K * D);
-        int rc = ok ? NFT_SUCCESS : NFT_EC_NOMEM;
+        if (!(tmp.get(dbs, K) && tmp.get(dnc, K) && tmp.get(dq, D) && tmp.get(work, (mode ? 2 : 1) * K * D)))
+            return NFT_EC_NOMEM;
         cplx *dq2 = nullptr, *cm = nullptr, *bnd = nullptr, *bndp = nullptr, *PHI = nullptr, *PSI = nullptr, *dout = nullptr;
-        if (rc == NFT_SUCCESS) {
-            be.h2d(dbs, bs, K * sizeof(cplx));
-            be.h2d(dnc, nc, K * sizeof(cplx));
-            P.D = (long long)D; P.K = (int)K; P.bs = dbs; P.nc = dnc; P.T0 = T[0]; P.eps_t = eps_t;
-            P.q = dq; P.work = work;
-            size_t zc = 0;                                    // :726-733: first sample with t >= 0 (0 if none)
-            for (size_t i = 0; i < D; i++)
-                if (T[0] + eps_t * (double)i >= 0.0) { zc = i; break; }
-            P.zc = (long long)zc;
-        }
-        if (rc == NFT_SUCCESS && mode == 0) {
+        be.h2d(dbs, bs, K * sizeof(cplx));
+        be.h2d(dnc, nc, K * sizeof(cplx));
+        P.D = (long long)D; P.K = (int)K; P.bs = dbs; P.nc = dnc; P.T0 = T[0]; P.eps_t = eps_t;
+        P.q = dq; P.work = work;
+        size_t zc = 0;                                    // :726-733: first sample with t >= 0 (0 if none)
+        for (size_t i = 0; i < D; i++)
+            if (T[0] + eps_t * (double)i >= 0.0) { zc = i; break; }
+        P.zc = (long long)zc;
+        if (mode == 0) {
             be.template run<KInvSolitons>((int)((D + 255) / 256), 1, P);
-        } else if (rc == NFT_SUCCESS) {
+        } else {
             // eigenfunctions of the seed on the half-step signal (nft_bs_eigenfunctions)
             const size_t D2 = 2 * (D - 1);
             BsParams B;
             std::memset(&B, 0, sizeof(B));
             const size_t L = nft_bs_chunk_len(D2);
             const size_t nchunk = (D2 + L - 1) / L;
-            ok = pl.alloc(dq2, D2) && pl.alloc(cm, K * nchunk * 8) && pl.alloc(bnd, K * (nchunk + 1) * 2)
-                 && pl.alloc(bndp, K * (nchunk + 1) * 2) && pl.alloc(PHI, K * D * 2) && pl.alloc(PSI, K * D * 2)
-                 && pl.alloc(dout, 3 * K);
-            rc = ok ? NFT_SUCCESS : NFT_EC_NOMEM;
-            if (rc == NFT_SUCCESS) {
-                be.h2d(dq, q, D * sizeof(cplx));
-                InvOpParams O;
-                std::memset(&O, 0, sizeof(O));
-                O.op = INV_DOUBLE_Q; O.n = (long long)D2; O.a = dq; O.out = dq2;
-                be.template run<KInvOp>((int)((D2 + 255) / 256), 1, O);
-                B.q = dq2; B.D = (long long)D2;
-                B.K = (int)K; B.lam = dbs; B.L = (int)L; B.nchunk = (int)nchunk;
-                B.cm = cm; B.bnd = bnd; B.bndp = bndp; B.PHI = PHI; B.PSI = PSI;
-                B.a = dout; B.aprime = dout + K; B.b = dout + 2 * K;
-                nft_bs_eigenfunctions(be, (int)((nchunk + 63) / 64), (int)K, B, T, eps_t);
-                P.PHI = PHI; P.PSI = PSI;
-                be.template run<KInvCdt>((int)((D + 255) / 256), 1, P);
-            }
+            if (!(tmp.get(dq2, D2) && tmp.get(cm, K * nchunk * 8) && tmp.get(bnd, K * (nchunk + 1) * 2)
+                  && tmp.get(bndp, K * (nchunk + 1) * 2) && tmp.get(PHI, K * D * 2) && tmp.get(PSI, K * D * 2)
+                  && tmp.get(dout, 3 * K)))
+                return NFT_EC_NOMEM;
+            be.h2d(dq, q, D * sizeof(cplx));
+            InvOpParams O;
+            std::memset(&O, 0, sizeof(O));
+            O.op = INV_DOUBLE_Q; O.n = (long long)D2; O.a = dq; O.out = dq2;
+            be.template run<KInvOp>((int)((D2 + 255) / 256), 1, O);
+            B.q = dq2; B.D = (long long)D2;
+            B.K = (int)K; B.lam = dbs; B.L = (int)L; B.nchunk = (int)nchunk;
+            B.cm = cm; B.bnd = bnd; B.bndp = bndp; B.PHI = PHI; B.PSI = PSI;
+            B.a = dout; B.aprime = dout + K; B.b = dout + 2 * K;
+            nft_bs_eigenfunctions(be, (int)((nchunk + 63) / 64), (int)K, B, T, eps_t);
+            P.PHI = PHI; P.PSI = PSI;
+            be.template run<KInvCdt>((int)((D + 255) / 256), 1, P);
         }
-        if (rc == NFT_SUCCESS) {
-            be.d2h(q, dq, D * sizeof(cplx));
-            rc = be.sync();
-        }
-        be.free(dbs); be.free(dnc); be.free(dq); be.free(work); be.free(dq2); be.free(cm); be.free(bnd); be.free(bndp);
-        be.free(PHI); be.free(PSI); be.free(dout);
-        return rc;
+        be.d2h(q, dq, D * sizeof(cplx));
+        return be.sync();
     }
 };
 
@@ -514,33 +496,20 @@ template <class BE> class NftInverseDiscBatch {
 public:
     static constexpr size_t kMaxGridY = 65535;   // grid.y of one launch: larger batches go in slices of whole signals
     BE &be;
+    DevArena<BE> mem;            // owns every array below
     const size_t D, B, K;
     const int mode;
     const bool residues, seed_cs;
-    size_t L = 0, nchunk = 0, Lr = 0, nchunk_r = 0, ncm = 0, bytes = 0;
+    size_t L = 0, nchunk = 0, Lr = 0, nchunk_r = 0, ncm = 0;
     cplx *bs = nullptr, *nc = nullptr, *work = nullptr;                                  // sorted copies; rho_k or S1, S2
     cplx *q2 = nullptr, *cm = nullptr, *bnd = nullptr, *bndp = nullptr, *PHI = nullptr, *PSI = nullptr, *aout = nullptr;
 
     NftInverseDiscBatch(BE &b, size_t D_, size_t B_, size_t K_, int mode_, bool residues_, bool seed_cs_)
-        : be(b), D(D_), B(B_), K(K_), mode(mode_), residues(residues_), seed_cs(seed_cs_) {}
-    ~NftInverseDiscBatch() { destroy(); }
-    void destroy()
-    {
-        for (cplx *p : {bs, nc, work, q2, cm, bnd, bndp, PHI, PSI, aout}) be.free(p);
-        bs = nc = work = q2 = cm = bnd = bndp = PHI = PSI = aout = nullptr;
-    }
-    template <class T> bool alloc(T *&p, size_t count)
-    {
-        const size_t b = count * sizeof(T);
-        p = (T *)be.alloc(b ? b : 16);
-        if (!p) return false;
-        bytes += b;
-        return true;
-    }
+        : be(b), mem(b), D(D_), B(B_), K(K_), mode(mode_), residues(residues_), seed_cs(seed_cs_) {}
     size_t work_per_signal() const { return (mode ? 2 : 1) * K * D; }
     int init()
     {
-        bool ok = alloc(bs, B * K) && alloc(nc, B * K) && alloc(work, B * work_per_signal());
+        bool ok = mem.get(bs, B * K) && mem.get(nc, B * K) && mem.get(work, B * work_per_signal());
         if (mode == 1) {
             const size_t D2 = 2 * (D - 1);
             L = nft_bs_chunk_len(D2);
@@ -551,9 +520,9 @@ public:
                 nchunk_r = (D + Lr - 1) / Lr;
                 ncm = std::max(ncm, nchunk_r);
             }
-            ok = ok && alloc(q2, B * D2) && alloc(cm, B * K * ncm * 8) && alloc(bnd, B * K * (ncm + 1) * 2)
-                 && alloc(bndp, B * K * (ncm + 1) * 2) && alloc(PHI, B * K * D * 2) && alloc(PSI, B * K * D * 2)
-                 && alloc(aout, 2 * B * K);
+            ok = ok && mem.get(q2, B * D2) && mem.get(cm, B * K * ncm * 8) && mem.get(bnd, B * K * (ncm + 1) * 2)
+                 && mem.get(bndp, B * K * (ncm + 1) * 2) && mem.get(PHI, B * K * D * 2) && mem.get(PSI, B * K * D * 2)
+                 && mem.get(aout, 2 * B * K);
         }
         return ok ? NFT_SUCCESS : NFT_EC_NOMEM;
     }
@@ -659,9 +628,10 @@ public:
     const size_t K;              // bound states per signal
     const int ds_mode, ds_residues;
     NftPlan<BE> pl;              // twiddle tables only
+    DevArena<BE> mem;            // owns the arrays of the continuous part below
     NftLayerPeelingDev<BE> lp;
-    NftInverseDiscBatch<BE> *ds = nullptr;
-    size_t Mf = 0, Lcap = 0, bytes = 0;
+    std::unique_ptr<NftInverseDiscBatch<BE>> ds;
+    size_t Mf = 0, Lcap = 0;
     cplx *dY = nullptr, *dV = nullptr, *dc = nullptr, *dr = nullptr, *db = nullptr, *da = nullptr, *dtm = nullptr;
     cplx *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
     int *dchirp = nullptr;       // status word of the DFTs (DFT mode sets no bit)
@@ -669,22 +639,13 @@ public:
     NftInverseBatch(BE &b, size_t D_, size_t M_, size_t B_, int cstype_, size_t os_, int modal, size_t K_ = 0,
                     int ds_mode_ = 0, int ds_residues_ = 0)
         : be(b), D(D_), M(M_), B(B_), cstype(cstype_), os(os_), K(K_), ds_mode(ds_mode_), ds_residues(ds_residues_),
-          pl(b, 2, 0, 1, 0, 1), lp(b, 1.0, 1, modal)
+          pl(b), mem(b), lp(b, 1.0, 1, modal)
     {
         lp.batch = B;
     }
-    ~NftInverseBatch() { destroy(); }
-    void destroy()
+    size_t workspace_bytes() const
     {
-        delete ds;
-        ds = nullptr;
-        lp.destroy();
-        for (cplx *p : {dY, dV, dc, dr, db, da, dtm, w0, w1, w2}) be.free(p);
-        be.free(dchirp);
-        be.free(pl.twtab); be.free(pl.twlo);
-        dY = dV = dc = dr = db = da = dtm = w0 = w1 = w2 = nullptr;
-        dchirp = nullptr;
-        pl.twtab = nullptr; pl.twlo = nullptr;
+        return pl.mem.bytes + mem.bytes + lp.workspace_bytes() + (ds ? ds->mem.bytes : 0);
     }
     int init()
     {
@@ -694,14 +655,12 @@ public:
         } else {
             const int r = lp.init(0);                 // the status words only
             if (r != NFT_SUCCESS) return r;
-            bytes = lp.status_words() * sizeof(int);
         }
         if (K > 0) {
-            ds = new (std::nothrow) NftInverseDiscBatch<BE>(be, D, B, K, ds_mode, ds_residues != 0, M > 0);
+            ds.reset(new (std::nothrow) NftInverseDiscBatch<BE>(be, D, B, K, ds_mode, ds_residues != 0, M > 0));
             if (!ds) return NFT_EC_NOMEM;
             const int r = ds->init();
             if (r != NFT_SUCCESS) return r;
-            bytes += ds->bytes;
         }
         return be.sync();
     }
@@ -712,21 +671,14 @@ public:
         const size_t L = NftInverseDev<BE>::dft_L(std::max(cstype == 2 ? D : M, Mf));
         if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
         Lcap = L;
-        bool ok = pl.alloc(pl.twtab, (size_t)2 * kMaxTwTable) && pl.alloc(pl.twlo, kTwLoEntries);
-        ok = ok && pl.alloc(dY, B * L) && pl.alloc(dV, L) && pl.alloc(dchirp, 4) && pl.alloc(dtm, B * 4 * (deg + 1));
-        if (cstype != 2) ok = ok && pl.alloc(dc, B * M) && pl.alloc(dr, B * M) && pl.alloc(db, B * M);
-        else ok = ok && pl.alloc(db, B * D) && pl.alloc(da, B * D);
-        if (cstype != 0) ok = ok && pl.alloc(w0, B * Mf) && pl.alloc(w1, B * Mf) && pl.alloc(w2, B * Mf);
+        bool ok = pl.init_twiddles_only() && mem.get(dY, B * L) && mem.get(dV, L) && mem.get(dchirp, 4)
+                  && mem.get(dtm, B * 4 * (deg + 1));
+        if (cstype != 2) ok = ok && mem.get(dc, B * M) && mem.get(dr, B * M) && mem.get(db, B * M);
+        else ok = ok && mem.get(db, B * D) && mem.get(da, B * D);
+        if (cstype != 0) ok = ok && mem.get(w0, B * Mf) && mem.get(w1, B * Mf) && mem.get(w2, B * Mf);
         if (!ok) return NFT_EC_NOMEM;
-        pl.upload_twiddles();
         be.memset0(dchirp, 4 * sizeof(int));
-        const int r = lp.prepare(deg);
-        if (r != NFT_SUCCESS) return r;
-        bytes = pl.bytes + lp.status_words() * sizeof(int);
-        for (size_t d = deg; d > NftLayerPeelingDev<BE>::kLeaf; d /= 2)
-            bytes += B * 4 * ((d + 1) + (2 * d + 1) + (d / 2 + 1)) * sizeof(cplx);
-        for (auto &kv : lp.plans) bytes += kv.second->bytes;
-        return NFT_SUCCESS;
+        return lp.prepare(deg);
     }
     // out[s*n + k] = sum_j in[s*n + j] exp(sign 2 pi i j k / n) for every signal s (NftInverseDev::dft, batched)
     int dft(const cplx *d_in, cplx *d_out, size_t n, int sign)

@@ -120,6 +120,7 @@ inline double nft_slow_weights(int scheme, std::complex<double> *w)
 template <class BE> class NftSlowPlan {
 public:
     BE &be;
+    DevArena<BE> mem;                 // owns every device buffer below
     const size_t D, M, batch;
     const NftSlowOpts o;
     int scheme = -1, ups = 1, fam = 0;
@@ -132,11 +133,10 @@ public:
     cplx *wtab = nullptr, *rec = nullptr, *rec2 = nullptr, *cm = nullptr, *cm2 = nullptr, *cmr = nullptr, *cmr2 = nullptr;
     size_t gsize = 1;                 // chunk maps per group of the reduce stage (1: none)
     int *status = nullptr, *warn = nullptr;
-    size_t bytes = 0;
     static constexpr size_t kMaxGroups = 0x7fffffff;
 
     NftSlowPlan(BE &be_, size_t D_, size_t M_, size_t batch_, const NftSlowOpts &o_)
-        : be(be_), D(D_), M(M_), batch(batch_), o(o_)
+        : be(be_), mem(be_), D(D_), M(M_), batch(batch_), o(o_)
     {
         scheme = nft_slow_scheme(o.nse_disc);
         if (scheme < 0) return;
@@ -167,15 +167,6 @@ public:
         return batch * D / 256 >= lim;                      // record kernel
     }
 
-    template <class T> bool alloc(T *&p, size_t count)
-    {
-        const size_t b = count * sizeof(T);
-        p = (T *)be.alloc(b ? b : 16);
-        if (!p) return false;
-        bytes += b;
-        return true;
-    }
-
     int init()
     {
         if (scheme < 0 || D < 2 || M < 2 || batch == 0) return NFT_EC_INVALID_ARGUMENT;
@@ -191,28 +182,22 @@ public:
             const int rc = front->init();
             if (rc != NFT_SUCCESS) return rc;
         }
-        bool ok = alloc(wtab, 16) && alloc(rec, batch * D * per) && alloc(cm, batch * nchunk * 4 * M)
-                  && alloc(status, batch) && alloc(warn, batch);
-        if (gsize > 1) ok = ok && alloc(cmr, batch * groups(nchunk) * 4 * M);
-        if (o.richardson) ok = ok && alloc(rec2, batch * D2 * per) && alloc(cm2, batch * nchunk2 * 4 * M);
-        if (o.richardson && gsize > 1) ok = ok && alloc(cmr2, batch * groups(nchunk2) * 4 * M);
+        bool ok = mem.get(wtab, 16) && mem.get(rec, batch * D * per) && mem.get(cm, batch * nchunk * 4 * M)
+                  && mem.get(status, batch) && mem.get(warn, batch);
+        if (gsize > 1) ok = ok && mem.get(cmr, batch * groups(nchunk) * 4 * M);
+        if (o.richardson) ok = ok && mem.get(rec2, batch * D2 * per) && mem.get(cm2, batch * nchunk2 * 4 * M);
+        if (o.richardson && gsize > 1) ok = ok && mem.get(cmr2, batch * groups(nchunk2) * 4 * M);
         if (!ok) return NFT_EC_NOMEM;
         be.h2d(wtab, w, sizeof(w));
         return NFT_SUCCESS;
     }
 
-    void destroy()
-    {
-        if (front) front->destroy();
-        front.reset();
-        be.free(wtab); be.free(rec); be.free(rec2); be.free(cm); be.free(cm2); be.free(cmr); be.free(cmr2); be.free(status); be.free(warn);
-        wtab = rec = rec2 = cm = cm2 = cmr = cmr2 = nullptr;
-        status = warn = nullptr;
-    }
-
     size_t groups(size_t nc) const { return (nc + gsize - 1) / gsize; }
 
-    size_t workspace_bytes() const { return bytes + (front ? front->bytes : 0); }
+    // the workspace back before the plan goes out of scope (the destructor does the same); init() again before reuse
+    void destroy() { front.reset(); mem.clear(); }
+
+    size_t workspace_bytes() const { return mem.bytes + (front ? front->mem.bytes : 0); }
 
     // records and chunk maps of one pass: Dk kept grid points, every nskip-th sample, interval Tk
     int pass(SlowParams P, const cplx *d_q, size_t Dk, size_t nskip, const double Tk[2], double eps_in, bool first,

@@ -11,6 +11,7 @@
 //
 // BE (back end) supplies device memory, copies, kernel launches and stage timers; see
 // hip_backend.hip (product) and tests/emu/emu_backend.h (CPU lane emulator, tests only).
+// Every device buffer of a plan comes from its arena `mem` (nft_arena.h) and goes back when the plan is destroyed.
 #pragma once
 #include <cmath>
 #include <complex>
@@ -18,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "nft_arena.h"
 #include "nft_dispatch.h"
 #include "nft_schemes.h"
 
@@ -116,6 +118,7 @@ constexpr size_t kTwLoEntries = ((size_t)1 << kFineLog2) + ((size_t)1 << (kFineL
 template <class BE> class NftPlan {
 public:
     BE &be;
+    DevArena<BE> mem;        // owns every device buffer below; mem.bytes is the plan's workspace size
     size_t D, M, batch;
     int akns_disc, deg0;
     size_t Dpad, plane, n0;
@@ -148,7 +151,7 @@ public:
     cplx *qpre = nullptr, *rsX = nullptr, *rsX12 = nullptr, *rsQ12 = nullptr, *rsY = nullptr, *rsV = nullptr;
     size_t Lr = 0;
     cplx *Y = nullptr, *Z = nullptr, *Z2 = nullptr;   // Z ping-pongs: spectral doubling reads the previous level's Z
-    cplx *chY = nullptr, *chV = nullptr, *chH = nullptr;
+    cplx *chY = nullptr, *chV = nullptr;
     cplx *chVS = nullptr;                 // cached spectrum of the chirp filter
     double vs_key[4] = {0, 0, 0, 0};      // log W (re, im), M, deg+1 it was computed for
     bool vs_valid = false;
@@ -159,7 +162,6 @@ public:
     // back (offset L - 3), and the fine table exp(-2 pi i j/(3*2^22)), j < 4096, of the master pair for 3*2^22
     cplx *tw3tab = nullptr, *twlo3 = nullptr;
     size_t Lc = 0;           // chirp transform length
-    size_t bytes = 0;
     int cur = 0;             // index of the body/tail/scale set holding the current level
     bool tree_valid = false;
     // The last split level leaves its maxima unreduced (64 slots per matrix): turning them into the pending scale and
@@ -190,12 +192,14 @@ public:
     int dbg_flags = 0;       // timing ablation: only builds with -DFNFT_AMD_ABLATION ever set it (hip_backend.hip)
 
     NftPlan(BE &be_, size_t D_, size_t M_, size_t batch_, int akns_disc_, int deg0_)
-        : be(be_), D(D_), M(M_), batch(batch_), akns_disc(akns_disc_), deg0(deg0_)
+        : be(be_), mem(be_), D(D_), M(M_), batch(batch_), akns_disc(akns_disc_), deg0(deg0_)
     {
         Dpad = nft_nextpow2(D);
         n0 = batch * Dpad;
         plane = n0 * (size_t)deg0;
     }
+    // a plan that exists only for its twiddle tables (init_twiddles_only): the stand-alone chirp z-transforms and DFTs
+    explicit NftPlan(BE &be_) : NftPlan(be_, 2, 0, 1, 0, 1) {}
 
     // fnft__nse_discretization.c:419-427: samples kept when every nskip-th of Din is used
     static size_t sub_count(size_t Din_, size_t nskip_) { return (size_t)std::llround((double)Din_ / (double)nskip_); }
@@ -203,15 +207,6 @@ public:
     void set_front(size_t Din_, size_t nskip_, int ups_) { Din = Din_; nskip = nskip_; ups = ups_; }
     // call before init(): only run_resample will be used, so neither the tree's nor the evaluation's buffers are made
     bool front_only = false;
-
-    template <class T> bool alloc(T *&p, size_t count)
-    {
-        const size_t b = count * sizeof(T);
-        p = (T *)be.alloc(b ? b : 16);
-        if (!p) return false;
-        bytes += b;
-        return true;
-    }
 
     const cplx *tw_table(size_t N) const
     {   // tables are stored back to back: N=2 at offset 0, N=4 at 2, N=8 at 6, ... offset = N-2
@@ -261,13 +256,13 @@ public:
         if (topN > kMaxSplitTree) return NFT_EC_NOT_YET_IMPLEMENTED;
         bool ok = true;
         for (int i = 0; i < 2 && !front_only; i++) {
-            ok = ok && alloc(body[i], 4 * plane) && alloc(tail[i], 4 * n0) && alloc(scale[i], n0)
-                 && alloc(wexp[i], n0);
+            ok = ok && mem.get(body[i], 4 * plane) && mem.get(tail[i], 4 * n0) && mem.get(scale[i], n0)
+                 && mem.get(wexp[i], n0);
         }
         {   // split levels hold at most n0*deg0/2048 matrices, kMax2Slots slots each
             const size_t nm = n0 * (size_t)deg0 / 32 + 4 * (size_t)kMax2Slots;
-            if (!front_only) ok = ok && alloc(max2[0], nm) && alloc(max2[1], nm);
-            ok = ok && alloc(status, 4);
+            if (!front_only) ok = ok && mem.get(max2[0], nm) && mem.get(max2[1], nm);
+            ok = ok && mem.get(status, 4);
             if (ok) be.memset0(status, 4 * sizeof(int));
         }
         if (!front_only) {   // scratch of the split transforms: 4*n_in polynomials of N forward, 4*n_out inverse,
@@ -282,20 +277,20 @@ public:
                 n /= 2;
                 d *= 2;
             }
-            if (needY) ok = ok && alloc(Y, needY) && alloc(Z, needZ) && alloc(Z2, needZ);
+            if (needY) ok = ok && mem.get(Y, needY) && mem.get(Z, needZ) && mem.get(Z2, needZ);
         }
         if (M > 0 && !front_only) {
             const size_t Np = D * (size_t)deg0 + 1;
             Lc = nft_nextpow2(Np + M - 1);
             if (Lc < 2 * (size_t)kRowChirp) Lc = 2 * (size_t)kRowChirp;
             if (Lc > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-            ok = ok && alloc(chY, batch * 2 * Lc) && alloc(chV, Lc) && alloc(chVS, Lc);
+            ok = ok && mem.get(chY, batch * 2 * Lc) && mem.get(chV, Lc) && mem.get(chVS, Lc);
         }
-        if (!front_only) ok = ok && alloc(tm_out, batch * 4 * (D * (size_t)deg0 + 1));
-        ok = ok && alloc(twtab, (size_t)2 * kMaxTwTable) && alloc(twlo, kTwLoEntries);
-        if (kdv) ok = ok && alloc(tw3tab, (size_t)3 << (kTw3MaxLog + 1)) && alloc(twlo3, (size_t)1 << kFineLog2);
+        if (!front_only) ok = ok && mem.get(tm_out, batch * 4 * (D * (size_t)deg0 + 1));
+        ok = ok && mem.get(twtab, (size_t)2 * kMaxTwTable) && mem.get(twlo, kTwLoEntries);
+        if (kdv) ok = ok && mem.get(tw3tab, (size_t)3 << (kTw3MaxLog + 1)) && mem.get(twlo3, (size_t)1 << kFineLog2);
         if (kdv) {
-            ok = ok && alloc(rneg, batch * D);
+            ok = ok && mem.get(rneg, batch * D);
             if (ok) {
                 std::vector<cplx> h(batch * D, cmake(-1.0, 0.0));
                 be.h2d(rneg, h.data(), h.size() * sizeof(cplx));
@@ -305,16 +300,16 @@ public:
             Lr = nft_nextpow2(2 * Din - 1);
             if (Lr < 2 * (size_t)kRowChirp) Lr = 2 * (size_t)kRowChirp;
             if (Lr > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-            if (!front_only) ok = ok && alloc(qpre, batch * D);
-            ok = ok && alloc(rsX, batch * Din) && alloc(rsX12, batch * 2 * Din)
-                 && alloc(rsQ12, batch * 2 * Din) && alloc(rsY, batch * 2 * Lr) && alloc(rsV, Lr);
+            if (!front_only) ok = ok && mem.get(qpre, batch * D);
+            ok = ok && mem.get(rsX, batch * Din) && mem.get(rsX12, batch * 2 * Din)
+                 && mem.get(rsQ12, batch * 2 * Din) && mem.get(rsY, batch * 2 * Lr) && mem.get(rsV, Lr);
         }
         CoeffProgramHost prog;
         const bool has_prog = akns_disc >= 11 && akns_disc <= 18;   // 2SPLIT5A .. 2SPLIT8B
         if (has_prog) {
             if (!nft_build_coeff_program(akns_disc, deg0, prog)) return NFT_EC_NOT_YET_IMPLEMENTED;
-            ok = ok && alloc(prog_bfrac, prog.bfrac.size()) && alloc(prog_mw, prog.mw.size())
-                 && alloc(prog_ptr, prog.tgt_ptr.size()) && alloc(prog_fac, prog.mfac.size());
+            ok = ok && mem.get(prog_bfrac, prog.bfrac.size()) && mem.get(prog_mw, prog.mw.size())
+                 && mem.get(prog_ptr, prog.tgt_ptr.size()) && mem.get(prog_fac, prog.mfac.size());
         }
         if (!ok) return NFT_EC_NOMEM;
         if (has_prog) {
@@ -329,14 +324,15 @@ public:
         return NFT_SUCCESS;
     }
 
-    void destroy()
+    // the workspace back before the plan goes out of scope (the destructor does the same); the plan is not usable after
+    void destroy() { mem.clear(); }
+
+    // instead of init(): the two master twiddle tables and nothing else (fill_chirp_geometry, run_chirp, tw_table)
+    bool init_twiddles_only()
     {
-        for (int i = 0; i < 2; i++) { be.free(body[i]); be.free(tail[i]); be.free(scale[i]); be.free(wexp[i]); }
-        be.free(max2[0]); be.free(max2[1]); be.free(status); be.free(Y); be.free(Z); be.free(Z2);
-        be.free(chY); be.free(chV); be.free(chH); be.free(chVS); be.free(tm_out); be.free(twtab); be.free(twlo);
-        be.free(prog_bfrac); be.free(prog_mw); be.free(prog_ptr); be.free(prog_fac);
-        be.free(rneg); be.free(dbg_stamps); be.free(wuser); be.free(tw3tab); be.free(twlo3);
-        be.free(qpre); be.free(rsX); be.free(rsX12); be.free(rsQ12); be.free(rsY); be.free(rsV);
+        if (!(mem.get(twtab, (size_t)2 * kMaxTwTable) && mem.get(twlo, kTwLoEntries))) return false;
+        upload_twiddles();
+        return true;
     }
 
     // host copies of the tables, computed once per process (long-double sines: ~2 ms per plan otherwise)
@@ -861,7 +857,7 @@ public:
     int run_contspec_tm(void *d_contspec, const Contspec &cs, const void *d_tm, int W)
     {
         if (!d_tm) return NFT_EC_INVALID_ARGUMENT;
-        if (!wuser && !alloc(wuser, batch)) return NFT_EC_NOMEM;
+        if (!wuser && !mem.get(wuser, batch)) return NFT_EC_NOMEM;
         std::vector<int> hw(batch, W);
         be.h2d(wuser, hw.data(), batch * sizeof(int));
         return run_contspec_impl(d_contspec, cs, (const cplx *)d_tm, 1);
@@ -998,42 +994,37 @@ public:
                            std::complex<double> A, std::complex<double> Wc, size_t Mo,
                            std::complex<double> *result, cplx *d_out = nullptr)
     {
-        NftPlan pl(be, 2, 0, 1, 0, 1);  // only the twiddle tables of the plan are used
+        NftPlan pl(be);
+        DevArena<BE> tmp(be);
         size_t L = nft_nextpow2(deg + 1 + Mo - 1);
         if (L < 2 * (size_t)kRowChirp) L = 2 * (size_t)kRowChirp;
         if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-        bool ok = pl.alloc(pl.twtab, (size_t)2 * kMaxTwTable) && pl.alloc(pl.twlo, kTwLoEntries);
         cplx *dp = nullptr, *dY = nullptr, *dV = nullptr, *dH = nullptr;
         int *dstatus = nullptr;
-        ok = ok && pl.alloc(dp, deg + 1) && pl.alloc(dY, L) && pl.alloc(dV, L) && pl.alloc(dH, Mo)
-             && pl.alloc(dstatus, 4);
-        int rc = NFT_EC_NOMEM;
-        if (ok) {
-            pl.upload_twiddles();
-            be.h2d(dp, p, (deg + 1) * sizeof(cplx));
-            be.memset0(dstatus, 4 * sizeof(int));
-            const std::complex<double> lA = nft_clog(A), lW = nft_clog(Wc);
-            ChirpParams C;
-            std::memset(&C, 0, sizeof(C));
-            C.poly = dp;
-            C.deg = (long long)deg;
-            C.batch = 1;
-            C.npoly = 1;
-            C.logA[0] = lA.real(); C.logA[1] = lA.imag();
-            C.logW[0] = lW.real(); C.logW[1] = lW.imag();
-            C.M = (long long)Mo;
-            C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = d_out ? d_out : dH;
-            pl.fill_chirp_geometry(C, L);
-            C.status = dstatus;
-            C.cstype = -1;
-            rc = pl.run_chirp(C);
-            if (rc == NFT_SUCCESS) {
-                if (!d_out) be.d2h(result, dH, Mo * sizeof(cplx));
-                rc = be.sync();
-            }
+        const bool ok = pl.init_twiddles_only() && tmp.get(dp, deg + 1) && tmp.get(dY, L) && tmp.get(dV, L)
+                        && tmp.get(dH, Mo) && tmp.get(dstatus, 4);
+        if (!ok) return NFT_EC_NOMEM;
+        be.h2d(dp, p, (deg + 1) * sizeof(cplx));
+        be.memset0(dstatus, 4 * sizeof(int));
+        const std::complex<double> lA = nft_clog(A), lW = nft_clog(Wc);
+        ChirpParams C;
+        std::memset(&C, 0, sizeof(C));
+        C.poly = dp;
+        C.deg = (long long)deg;
+        C.batch = 1;
+        C.npoly = 1;
+        C.logA[0] = lA.real(); C.logA[1] = lA.imag();
+        C.logW[0] = lW.real(); C.logW[1] = lW.imag();
+        C.M = (long long)Mo;
+        C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = d_out ? d_out : dH;
+        pl.fill_chirp_geometry(C, L);
+        C.status = dstatus;
+        C.cstype = -1;
+        int rc = pl.run_chirp(C);
+        if (rc == NFT_SUCCESS) {
+            if (!d_out) be.d2h(result, dH, Mo * sizeof(cplx));
+            rc = be.sync();
         }
-        be.free(dp); be.free(dY); be.free(dV); be.free(dH); be.free(dstatus);
-        be.free(pl.twtab); be.free(pl.twlo);
         return rc;
     }
 
@@ -1042,63 +1033,58 @@ public:
     static int resample_host(BE &be, size_t Dn, double eps_t, const std::complex<double> *q, double delta,
                              std::complex<double> *q_new, int *warn_not_bandlimited = nullptr)
     {
-        NftPlan pl(be, 2, 0, 1, 0, 1);  // only the twiddle tables of the plan are used
+        NftPlan pl(be);
+        DevArena<BE> tmp(be);
         size_t L = nft_nextpow2(2 * Dn - 1);
         if (L < 2 * (size_t)kRowChirp) L = 2 * (size_t)kRowChirp;
         if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-        bool ok = pl.alloc(pl.twtab, (size_t)2 * kMaxTwTable) && pl.alloc(pl.twlo, kTwLoEntries);
         cplx *dq = nullptr, *dX = nullptr, *dX12 = nullptr, *dQ12 = nullptr, *dY = nullptr, *dV = nullptr;
         int *dstatus = nullptr;
-        ok = ok && pl.alloc(dq, Dn) && pl.alloc(dX, Dn) && pl.alloc(dX12, 2 * Dn) && pl.alloc(dQ12, 2 * Dn)
-             && pl.alloc(dY, 2 * L) && pl.alloc(dV, L) && pl.alloc(dstatus, 4);
-        int rc = NFT_EC_NOMEM;
-        if (ok) {
-            pl.upload_twiddles();
-            be.h2d(dq, q, Dn * sizeof(cplx));
-            be.memset0(dstatus, 4 * sizeof(int));
-            ChirpParams C;
-            std::memset(&C, 0, sizeof(C));
-            C.poly = dq;
-            C.deg = (long long)Dn - 1;
-            C.batch = 1;
-            C.npoly = 1;
-            C.M = (long long)Dn;
-            C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = dX;
-            pl.fill_chirp_geometry(C, L);
-            C.status = dstatus;
-            C.cstype = -1;
-            C.dft_len = (long long)Dn;
-            C.dft_sign = -1;
-            rc = pl.run_chirp(C);                                   // X = DFT(q), :366-370
-            if (rc == NFT_SUCCESS) {
-                ResampleParams R;
-                std::memset(&R, 0, sizeof(R));
-                R.X = dX; R.X12 = dX12; R.Q12 = dQ12; R.qpre = nullptr;
-                R.Din = (long long)Dn; R.Dsub = (long long)Dn; R.nskip = 1;
-                R.batch = 1;
-                R.delta_over_span = delta / ((double)Dn * eps_t);    // freq[i]*delta, :383-393
-                R.status = dstatus;
-                be.template run<KBandCheck>(1, 1, R);                // :371-381
-                be.template run<KResamplePhase>((int)((Dn + 255) / 256), 1, R);
-                C.poly = dX12;
-                C.npoly = 2;
-                C.Hbuf = dQ12;
-                C.dft_sign = +1;
-                rc = pl.run_chirp(C);                               // inverse DFTs of the -delta and +delta copies
-            }
-            if (rc == NFT_SUCCESS) {
-                int hst[4] = {0, 0, 0, 0};
-                be.d2h(hst, dstatus, sizeof(hst));
-                be.d2h(q_new, dQ12 + Dn, Dn * sizeof(cplx));        // the +delta copy
-                rc = be.sync();
-                if (warn_not_bandlimited) *warn_not_bandlimited = (hst[0] & 4) ? 1 : 0;
-                const double inv = 1.0 / (double)Dn;                // :395-399
-                if (rc == NFT_SUCCESS)
-                    for (size_t i = 0; i < Dn; i++) q_new[i] *= inv;
-            }
+        const bool ok = pl.init_twiddles_only() && tmp.get(dq, Dn) && tmp.get(dX, Dn) && tmp.get(dX12, 2 * Dn)
+                        && tmp.get(dQ12, 2 * Dn) && tmp.get(dY, 2 * L) && tmp.get(dV, L) && tmp.get(dstatus, 4);
+        if (!ok) return NFT_EC_NOMEM;
+        be.h2d(dq, q, Dn * sizeof(cplx));
+        be.memset0(dstatus, 4 * sizeof(int));
+        ChirpParams C;
+        std::memset(&C, 0, sizeof(C));
+        C.poly = dq;
+        C.deg = (long long)Dn - 1;
+        C.batch = 1;
+        C.npoly = 1;
+        C.M = (long long)Dn;
+        C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = dX;
+        pl.fill_chirp_geometry(C, L);
+        C.status = dstatus;
+        C.cstype = -1;
+        C.dft_len = (long long)Dn;
+        C.dft_sign = -1;
+        int rc = pl.run_chirp(C);                               // X = DFT(q), :366-370
+        if (rc == NFT_SUCCESS) {
+            ResampleParams R;
+            std::memset(&R, 0, sizeof(R));
+            R.X = dX; R.X12 = dX12; R.Q12 = dQ12; R.qpre = nullptr;
+            R.Din = (long long)Dn; R.Dsub = (long long)Dn; R.nskip = 1;
+            R.batch = 1;
+            R.delta_over_span = delta / ((double)Dn * eps_t);    // freq[i]*delta, :383-393
+            R.status = dstatus;
+            be.template run<KBandCheck>(1, 1, R);                // :371-381
+            be.template run<KResamplePhase>((int)((Dn + 255) / 256), 1, R);
+            C.poly = dX12;
+            C.npoly = 2;
+            C.Hbuf = dQ12;
+            C.dft_sign = +1;
+            rc = pl.run_chirp(C);                               // inverse DFTs of the -delta and +delta copies
         }
-        be.free(dq); be.free(dX); be.free(dX12); be.free(dQ12); be.free(dY); be.free(dV); be.free(dstatus);
-        be.free(pl.twtab); be.free(pl.twlo);
+        if (rc == NFT_SUCCESS) {
+            int hst[4] = {0, 0, 0, 0};
+            be.d2h(hst, dstatus, sizeof(hst));
+            be.d2h(q_new, dQ12 + Dn, Dn * sizeof(cplx));        // the +delta copy
+            rc = be.sync();
+            if (warn_not_bandlimited) *warn_not_bandlimited = (hst[0] & 4) ? 1 : 0;
+            const double inv = 1.0 / (double)Dn;                // :395-399
+            if (rc == NFT_SUCCESS)
+                for (size_t i = 0; i < Dn; i++) q_new[i] *= inv;
+        }
         return rc;
     }
 

@@ -26,7 +26,6 @@ int emu_discspec_batch(size_t D, size_t K, size_t batch, int nse_disc, size_t ni
         rc = ds.read(st, ko, K_out);
         for (size_t b = 0; b < batch; b++) status[b] = st[b];
     }
-    ds.destroy();
     return rc;
 }
 

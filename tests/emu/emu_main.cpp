@@ -123,7 +123,7 @@ int emu_nsev_contspec(size_t D, const std::complex<double> *q, const double *T, 
     NftPlan<EmuBackend> pl(be, (size_t)ups * D, M, 1, akns, nft_akns_degree(akns));
     pl.set_front(D, 1, ups);
     int rc = pl.init();
-    if (rc != NFT_SUCCESS) { pl.destroy(); return rc; }
+    if (rc != NFT_SUCCESS) return rc;
     const size_t cs_len = M * (cstype == 0 ? 1 : (cstype == 1 ? 2 : 3));
     cplx *dq = (cplx *)be.alloc(D * sizeof(cplx));
     cplx *dcs = (cplx *)be.alloc(cs_len * sizeof(cplx));
@@ -141,7 +141,6 @@ int emu_nsev_contspec(size_t D, const std::complex<double> *q, const double *T, 
     if (rc == NFT_SUCCESS) be.d2h(contspec, dcs, cs_len * sizeof(cplx));
     be.free(dq);
     be.free(dcs);
-    pl.destroy();
     return rc;
 }
 
@@ -156,7 +155,7 @@ int emu_kdvv_contspec(size_t D, const std::complex<double> *u, const double *T, 
     pl.kdv = true;
     pl.want_real = real != 0;
     int rc = pl.init();
-    if (rc != NFT_SUCCESS) { pl.destroy(); return rc; }
+    if (rc != NFT_SUCCESS) return rc;
     cplx *du = (cplx *)be.alloc(D * sizeof(cplx));
     cplx *dcs = (cplx *)be.alloc(M * sizeof(cplx));
     be.h2d(du, u, D * sizeof(cplx));
@@ -168,7 +167,6 @@ int emu_kdvv_contspec(size_t D, const std::complex<double> *u, const double *T, 
     if (rc == NFT_SUCCESS) be.d2h(contspec, dcs, M * sizeof(cplx));
     be.free(du);
     be.free(dcs);
-    pl.destroy();
     return rc;
 }
 
@@ -247,7 +245,6 @@ int emu_tree_schedule(int entry, size_t D, int disc, size_t batch, int real, cha
         if (rc == NFT_SUCCESS) rc = pl.run_tree();
         if (rc == NFT_SUCCESS) pl.export_tm();
         be.free(dummy);
-        pl.destroy();
     }
     emu_schedule = nullptr;
     std::string s;
@@ -307,7 +304,6 @@ int emu_chirp_schedule(int entry, size_t n, size_t M, int disc, size_t batch, in
                 cs.T[0] = T[0]; cs.T[1] = T[1];
                 if (rc == NFT_SUCCESS) rc = pl.run_contspec_tm(dummy, cs, dummy, 3);
             }
-            pl.destroy();
         }
     } else if (entry == 4 && n > 1 && M > 0 && batch > 0 && disc >= 0) {
         const int akns = disc + 1;
@@ -319,7 +315,6 @@ int emu_chirp_schedule(int entry, size_t n, size_t M, int disc, size_t batch, in
         if (rc == NFT_SUCCESS) rc = pl.run_front(dummy, T, 1, Tsub);
         if (rc == NFT_SUCCESS) rc = pl.run_tree();
         if (rc == NFT_SUCCESS) rc = pl.run_contspec_kdv(dummy, T, XI, disc == 2);
-        pl.destroy();
     }
     be.free(dummy);
     emu_schedule = nullptr;

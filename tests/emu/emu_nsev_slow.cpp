@@ -23,7 +23,6 @@ int emu_nsev_slow(size_t D, size_t M, size_t batch, int nse_disc, int cstype, in
         rc = sp.read(st, wn);
         for (size_t b = 0; b < batch; b++) { status[b] = st[b]; warn[b] = wn[b]; }
     }
-    sp.destroy();
     return rc;
 }
 

@@ -3,16 +3,10 @@ scatterer (KBs*), without a GPU: fp64 2x2
 complex products with derivative maps are register-heavy, and a spilled register is a round trip to HBM inside every
 Newton iteration.  None may spill a VGPR or use scratch.  The figures are the code-object metadata of the built
 library, read with the ROCm LLVM tools like test_kernel_resources_cpu.py does; the test prints them."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "fnft_amd", "lib", "libfnft_amd.so")
+from kernel_notes import kernel_resources
+
 KERNELS = {
     "_Z12kernel_entryI6KDsBoxEvNT_6ParamsE": "KDsBox",
     "_Z12kernel_entryI9KDsNewtonILb0EEEvNT_6ParamsE": "KDsNewton<false>",
@@ -35,43 +29,11 @@ KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spil
         "group_segment_fixed_size")
 
 
-def _tool(name):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    for d in (os.path.join(rocm, "lib", "llvm", "bin"), os.path.join(rocm, "llvm", "bin")):
-        if os.path.exists(os.path.join(d, name)):
-            return os.path.join(d, name)
-    path = shutil.which(name)
-    assert path, "%s (ROCm LLVM tools) not found" % name
-    return path
-
-
 @pytest.fixture(scope="module")
 def resources():
     from fnft_amd import build
     build.build()
-    found = {}
-    with tempfile.TemporaryDirectory() as d:
-        shutil.copy(LIB, os.path.join(d, "lib.so"))
-        subprocess.run([_tool("llvm-objdump"), "--offloading", "lib.so"], cwd=d, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        objs = sorted(f for f in os.listdir(d) if "gfx950" in f)
-        assert objs, "no gfx950 code object in the library"
-        for co in objs:
-            notes = subprocess.run([_tool("llvm-readelf"), "--notes", os.path.join(d, co)], check=True,
-                                   stdout=subprocess.PIPE, text=True).stdout
-            cur = {}
-            for line in notes.splitlines():   # one record per kernel, opened by .agpr_count, named by .symbol
-                m = re.match(r"\s*-?\s*\.(\w+):\s*(.*)$", line)
-                if not m:
-                    continue
-                k, v = m.group(1), m.group(2).strip()
-                if k == "agpr_count":
-                    cur = {}
-                if k in KEYS and k not in cur:
-                    cur[k] = int(v)
-                elif k == "symbol" and v.endswith(".kd") and v[:-3] in KERNELS:
-                    found[KERNELS[v[:-3]]] = cur
-    return found
+    return kernel_resources(KERNELS, KEYS)
 
 
 @pytest.mark.parametrize("kernel", sorted(KERNELS.values()))

@@ -3,15 +3,11 @@ two waves per SIMD with no VGPR spilled and no scratch.  The figures are the cod
 (fnft_amd/lib/libfnft_amd.so, what `hipcc -Rpass-analysis=kernel-resource-usage` reports), read with the ROCm LLVM tools.
 A spill of these kernels is HBM traffic on the headline path (0.25 GB per cfg 2 step before they were made spill-free)."""
 import os
-import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "fnft_amd", "lib", "libfnft_amd.so")
+from kernel_notes import LIB, kernel_resources
+
 # symbol of kernel_entry<K> -> K
 KERNELS = {
     "_Z12kernel_entryI7KMidSymILb1EEEvNT_6ParamsE": "KMidSym<true>",
@@ -24,16 +20,6 @@ KERNELS = {
 KEYS = ("vgpr_count", "agpr_count", "vgpr_spill_count", "private_segment_fixed_size")
 
 
-def _tool(name):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    for d in (os.path.join(rocm, "lib", "llvm", "bin"), os.path.join(rocm, "llvm", "bin")):
-        if os.path.exists(os.path.join(d, name)):
-            return os.path.join(d, name)
-    path = shutil.which(name)
-    assert path, "%s (ROCm LLVM tools) not found" % name
-    return path
-
-
 def waves_per_simd(vgpr, agpr):
     """Waves per SIMD the registers allow on gfx950: one file of 512 registers per lane for VGPRs and AGPRs, allocated
     in granules of 8 (AGPRs start at a multiple of 4)."""
@@ -44,31 +30,7 @@ def waves_per_simd(vgpr, agpr):
 @pytest.fixture(scope="module")
 def resources():
     assert os.path.exists(LIB), "libfnft_amd.so is not built (python -m fnft_amd.build)"
-    found = {}
-    with tempfile.TemporaryDirectory() as d:
-        shutil.copy(LIB, os.path.join(d, "lib.so"))
-        subprocess.run([_tool("llvm-objdump"), "--offloading", "lib.so"], cwd=d, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        objs = sorted(f for f in os.listdir(d) if "gfx950" in f)
-        assert objs, "no gfx950 code object in the library"
-        for co in objs:
-            notes = subprocess.run([_tool("llvm-readelf"), "--notes", os.path.join(d, co)], check=True,
-                                   stdout=subprocess.PIPE, text=True).stdout
-            # one metadata record per kernel, opened by its first key (.agpr_count); .symbol names it (the argument
-            # records inside it have a .name but no .symbol)
-            cur = {}
-            for line in notes.splitlines():
-                m = re.match(r"\s*-?\s*\.(\w+):\s*(.*)$", line)
-                if not m:
-                    continue
-                k, v = m.group(1), m.group(2).strip()
-                if k == "agpr_count":
-                    cur = {}
-                if k in KEYS and k not in cur:
-                    cur[k] = int(v)
-                elif k == "symbol" and v.endswith(".kd") and v[:-3] in KERNELS:
-                    found[KERNELS[v[:-3]]] = cur
-    return found
+    return kernel_resources(KERNELS, KEYS)
 
 
 @pytest.mark.parametrize("kernel", sorted(KERNELS.values()))
