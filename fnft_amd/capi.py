@@ -108,6 +108,9 @@ EXPORTED = [
     "fnft_amd_nsev_inverse_discrete_device",
     "fnft_amd_discspec_plan_create", "fnft_amd_discspec_plan_destroy", "fnft_amd_discspec_plan_workspace_bytes",
     "fnft_amd_nsev_discspec_device", "fnft_amd_discspec_plan_finish",
+    "fnft_amd_discspec_search_plan_create", "fnft_amd_discspec_search_plan_roots",
+    "fnft_amd_nsev_discspec_search_device", "fnft_amd_discspec_plan_warnings",
+    "fnft_amd_discspec_plan_set_launch_timing", "fnft_amd_discspec_plan_launch_count", "fnft_amd_discspec_plan_launch_ms",
     "fnft_amd_slow_plan_create", "fnft_amd_slow_plan_destroy", "fnft_amd_slow_plan_workspace_bytes",
     "fnft_amd_nsev_slow_device", "fnft_amd_slow_plan_finish", "fnft_amd_slow_plan_chunks",
 ]
@@ -266,6 +269,20 @@ def load(path=None):
     L.fnft_amd_nsev_discspec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.fnft_amd_discspec_plan_finish.restype = i32
     L.fnft_amd_discspec_plan_finish.argtypes = [vp, vp, vp, vp]
+    L.fnft_amd_discspec_search_plan_create.restype = i32
+    L.fnft_amd_discspec_search_plan_create.argtypes = [C.POINTER(vp), sz, sz, sz, C.POINTER(NsevOpts), C.c_int]
+    L.fnft_amd_discspec_search_plan_roots.restype = sz
+    L.fnft_amd_discspec_search_plan_roots.argtypes = [sz, C.POINTER(NsevOpts), C.POINTER(sz)]
+    L.fnft_amd_nsev_discspec_search_device.restype = i32
+    L.fnft_amd_nsev_discspec_search_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.fnft_amd_discspec_plan_warnings.restype = i32
+    L.fnft_amd_discspec_plan_warnings.argtypes = [vp, vp]
+    L.fnft_amd_discspec_plan_set_launch_timing.restype = None
+    L.fnft_amd_discspec_plan_set_launch_timing.argtypes = [vp, C.c_int]
+    L.fnft_amd_discspec_plan_launch_count.restype = C.c_size_t
+    L.fnft_amd_discspec_plan_launch_count.argtypes = [vp]
+    L.fnft_amd_discspec_plan_launch_ms.restype = dbl
+    L.fnft_amd_discspec_plan_launch_ms.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_size_t]
     L.fnft_amd_slow_plan_create.restype = i32
     L.fnft_amd_slow_plan_create.argtypes = [C.POINTER(vp), sz, sz, sz, C.POINTER(NsevOpts), C.c_int]
     L.fnft_amd_slow_plan_destroy.restype = None
@@ -899,6 +916,58 @@ class DiscSpecPlan(_BatchPlan):
     def finish(self, stream=0):
         """Waits for `stream`: (rc, status[batch], K_out[batch])."""
         return self._finish(stream, np.uint64)
+
+    def set_launch_timing(self, on=True):
+        """Measurement: an event pair around every kernel launch of the calls that follow (clears the list)."""
+        self.L.fnft_amd_discspec_plan_set_launch_timing(self.h, 1 if on else 0)
+
+    def launches(self):
+        """[(kernel, ms)] of the launches since set_launch_timing, once the stream is done."""
+        out, buf = [], C.create_string_buffer(128)
+        for i in range(int(self.L.fnft_amd_discspec_plan_launch_count(self.h))):
+            ms = float(self.L.fnft_amd_discspec_plan_launch_ms(self.h, i, buf, len(buf)))
+            out.append((buf.value.decode(), ms))
+        return out
+
+
+def discspec_search_roots(D, opts=None):
+    """fnft_amd_discspec_search_plan_roots: (roots per signal, Dsub) of a DiscSpecSearchPlan of these sizes; (0, 0) for
+    sizes or options no plan can have.  Needs no GPU."""
+    o = None if opts is None else (opts if isinstance(opts, NsevOpts) else nsev_opts(opts))
+    ds = C.c_size_t(0)
+    n = load().fnft_amd_discspec_search_plan_roots(int(D), None if o is None else C.byref(o), C.byref(ds))
+    return int(n), int(ds.value)
+
+
+class DiscSpecSearchPlan(DiscSpecPlan):
+    """fnft_amd_discspec_plan_t made by fnft_amd_discspec_search_plan_create: the discrete spectrum of `batch` signals
+    of D samples without guesses (FAST_EIGENVALUE or SUBSAMPLE_AND_REFINE; opts None: fnft_nsev's defaults), room for K
+    bound states per signal, device-resident.  Raises RuntimeError (attribute rc) if the plan cannot be created."""
+
+    def __init__(self, D, K, batch=1, opts=None, device=0):
+        self.L = load()
+        self.D, self.K, self.batch = int(D), int(K), int(batch)
+        self.opts = None if opts is None else (opts if isinstance(opts, NsevOpts) else nsev_opts(opts))
+        self._create("fnft_amd_discspec_search_plan_create", self.D, self.K, self.batch,
+                     None if self.opts is None else C.byref(self.opts), int(device))
+
+    def roots(self):
+        """(roots per signal, subsampled length) the plan searches."""
+        return discspec_search_roots(self.D, self.opts)
+
+    def run_device(self, q_ptr, T, bs_ptr, nc_ptr, k_ptr, stream=0):
+        """Enqueue one call: q_ptr (batch*D complex128) -> bs_ptr (batch*K), nc_ptr (batch * nc_len(), or 0 to skip that
+        stage), k_ptr (batch uint64); raw device addresses (e.g. tensor.data_ptr())."""
+        return int(self.L.fnft_amd_nsev_discspec_search_device(
+            self.h, C.c_void_p(q_ptr or None), None if T is None else _d2(T), C.c_void_p(bs_ptr or None),
+            C.c_void_p(nc_ptr or None), C.c_void_p(k_ptr or None), C.c_void_p(stream)))
+
+    def warnings(self):
+        """After finish: per signal, bit 0 = truncated to K, bit 1 = root finder stopped at its sweep limit."""
+        w = np.zeros(self.batch, np.int32)
+        rc = self.L.fnft_amd_discspec_plan_warnings(self.h, _ptr(w))
+        assert rc == FNFT_SUCCESS
+        return w
 
 
 SLOW_DISCS = ("BO", "CF4_2", "CF4_3", "CF5_3", "CF6_4", "ES4", "TES4")

@@ -27,6 +27,7 @@ groups["multi3"] = ["KMulti<%d, 3>" % n for n in (128, 1024)]
 groups["multi2"] = ["KMulti<%d, 2>" % n for n in (128, 1024)]
 groups["leafmulti"] = ["KLeafMulti<%d, %d>" % (d, s) for s in (3, 2) for d in (1, 2, 4)]
 groups["discbatch"] = ["KDsBox", "KDsNewton<false>", "KDsNewton<true>", "KDsFilter", "KDsNorm<false>", "KDsNorm<true>"]
+groups["discroots"] = ["KDsGather", "KAberthBStart", "KAberthBNewton", "KAberthBSum", "KAberthBApply", "KAberthBStep", "KDsCandidates"]
 groups["slow"] = ["KSlowPrep", "KSlowScatter<0, true>", "KSlowScatter<0, false>", "KSlowScatter<1, false>", "KSlowScatter<2, false>", "KSlowReduce", "KSlowCombine"]
 groups["mid"] = ["KMidSym<true>", "KMidSym<false>"]
 groups["col"] = ["KColFwd<%d>" % n for n in N1_ALL] + ["KColInv<%d>" % n for n in N1_ALL]

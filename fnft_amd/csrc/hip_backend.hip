@@ -190,6 +190,9 @@ struct fnft_amd_inverse_plan : BatchHandle<NftInverseBatch<HipBackend>> {
 struct fnft_amd_discspec_plan : BatchHandle<NftDiscSpecBatch<HipBackend>> {
     const unsigned long long *last_K = nullptr;   // d_K_out of the last call
     std::vector<unsigned long long> kout;
+    // fnft_amd_discspec_search_plan_create: the guess-free plan in place of `core` (it owns its own NftDiscSpecBatch)
+    std::unique_ptr<NftDiscSpecSearch<HipBackend>> search;
+    std::vector<int> wn;                          // its warning bits, read by finish
 };
 struct fnft_amd_slow_plan : BatchHandle<NftSlowPlan<HipBackend>> {
     std::vector<int> wn;
@@ -265,7 +268,7 @@ static FNFT_INT batch_finish(H *plan, void *stream, FNFT_INT *status, Read read,
 {
     PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
     if (!call.ok) return FNFT_EC_OTHER;
-    const int rc = read(*plan->core);
+    const int rc = read();
     if (rc != NFT_SUCCESS || plan->be.failed) return FNFT_EC_OTHER;
     FNFT_INT first = FNFT_SUCCESS;
     for (size_t b = 0; b < plan->st.size(); b++) {
@@ -416,10 +419,11 @@ FNFT_UINT fnft_amd_plan_launch_count(const fnft_amd_plan_t *plan)
     return plan ? plan->be.launches_used : 0;
 }
 
-double fnft_amd_plan_launch_ms(const fnft_amd_plan_t *plan, FNFT_UINT i, char *name, FNFT_UINT name_cap)
+// time and kernel name of launch i of a back end's per-launch timers
+static double launch_ms_of(const HipBackend &be, FNFT_UINT i, char *name, FNFT_UINT name_cap)
 {
-    if (!plan || i >= plan->be.launches_used) return -1.0;
-    const HipBackend::LaunchRec &r = plan->be.launches[i];
+    if (i >= be.launches_used) return -1.0;
+    const HipBackend::LaunchRec &r = be.launches[i];
     if (name && name_cap) {
         // __PRETTY_FUNCTION__ of run<K>: "... [K = KMidSym<true>]"
         const char *k = strstr(r.name, "K = ");
@@ -433,6 +437,11 @@ double fnft_amd_plan_launch_ms(const fnft_amd_plan_t *plan, FNFT_UINT i, char *n
     float ms = -1.f;
     if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) return -1.0;
     return (double)ms;
+}
+
+double fnft_amd_plan_launch_ms(const fnft_amd_plan_t *plan, FNFT_UINT i, char *name, FNFT_UINT name_cap)
+{
+    return plan ? launch_ms_of(plan->be, i, name, name_cap) : -1.0;
 }
 
 FNFT_INT fnft_amd_nsev_contspec_device(fnft_amd_plan_t *plan, const void *d_q, void *d_contspec,
@@ -1104,7 +1113,7 @@ FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *strea
 {
     SEAM_CHECK(!plan, plan);
     return batch_finish(
-        plan, stream, status, [&](NftInverseBatch<HipBackend> &c) { return c.read_status(plan->st); },
+        plan, stream, status, [&] { return plan->core->read_status(plan->st); },
         [&](size_t b, int h) -> FNFT_INT {
             if (warnings) warnings[b] = ((h & 8) && !(h & 64)) ? 1 : 0;
             // the drop-in, in its order: a bound state with Im <= 0 (bit 6) fails before anything runs; then
@@ -1155,11 +1164,22 @@ FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UIN
     return batch_init(plan, batch_new<fnft_amd_discspec_plan>((size_t)D, (size_t)K, (size_t)batch, d), device);
 }
 
-void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan) { batch_destroy(plan); }
+void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
+{
+    if (!plan || !plan->search) return batch_destroy(plan);
+    {   // batch_destroy for the guess-free core: on the plan's device, after everything it enqueued
+        DeviceGuard dg(plan->device);
+        plan_quiesce(plan->last_stream);
+        plan->search.reset();
+        plan->be.destroy_events();
+    }
+    delete plan;
+}
 
 FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan)
 {
-    return plan ? plan->core->workspace_bytes() : 0;
+    if (!plan) return 0;
+    return plan->search ? plan->search->workspace_bytes() : plan->core->workspace_bytes();
 }
 
 FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
@@ -1172,6 +1192,7 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
     SEAM_CHECK(!d_guesses, guesses);
     SEAM_CHECK(!d_bound_states, bound_states);
     SEAM_CHECK(!d_K_out, K_out);
+    if (plan->search) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));   // a guess-free plan
     PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
     if (!call.ok) return FNFT_EC_OTHER;
     plan->last_K = (const unsigned long long *)d_K_out;
@@ -1186,9 +1207,13 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
     SEAM_CHECK(!plan, plan);
     return batch_finish(
         plan, stream, status,
-        [&](NftDiscSpecBatch<HipBackend> &c) { return c.read(plan->st, plan->kout, plan->last_K); },
+        [&] {
+            if (plan->search) return plan->search->read(plan->st, plan->kout, plan->wn, plan->last_K);
+            return plan->core->read(plan->st, plan->kout, plan->last_K);
+        },
         [&](size_t b, int h) -> FNFT_INT {
             if (K_out) K_out[b] = (FNFT_UINT)plan->kout[b];
+            if (h & 8) return -FNFT_EC_OTHER;   // guess-free plans: the root finder did not converge (poly_roots_fasteigen)
             // the drop-in on this signal alone, in its order: the MODAL step-size check of the transform it runs first
             // (fnft__akns_fscatter.c:122-126), an empty bounding box, a' = 0 in the refinement or the residues -- each
             // passed on as a subroutine failure (negative)
@@ -1197,6 +1222,121 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
             if (h & 2) return -FNFT_EC_DIV_BY_ZERO;
             return FNFT_SUCCESS;
         });
+}
+
+// ---- the same without guesses: FAST_EIGENVALUE and SUBSAMPLE_AND_REFINE (nft_discspec_search.h) --------------------
+static NftDsOpts search_opts(const fnft_nsev_opts_t &o)
+{
+    NftDsOpts d;
+    d.bsfilt = (int)o.bound_state_filtering; d.bsloc = (int)o.bound_state_localization; d.niter = o.niter;
+    d.Dsub = o.Dsub; d.dstype = (int)o.discspec_type; d.nse_disc = (int)o.discretization; d.richardson = 0;
+    return d;
+}
+
+FNFT_UINT fnft_amd_discspec_search_plan_roots(FNFT_UINT D, fnft_nsev_opts_t const *opts, FNFT_UINT *Dsub)
+{
+    const fnft_nsev_opts_t o = opts ? *opts : fnft_nsev_default_opts();
+    size_t ds = 0, nskip = 1, roots = 0;
+    NftDiscSpecSearch<HipBackend>::sizes((size_t)D, search_opts(o), &ds, &nskip, &roots);
+    if (Dsub) *Dsub = (FNFT_UINT)ds;
+    return (FNFT_UINT)roots;
+}
+
+FNFT_INT fnft_amd_discspec_search_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UINT D, FNFT_UINT K, FNFT_UINT batch,
+                                              fnft_nsev_opts_t const *opts, int device)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(D < 2, D);
+    SEAM_CHECK(K == 0, K);
+    SEAM_CHECK(batch == 0, batch);
+    const fnft_nsev_opts_t o = opts ? *opts : fnft_nsev_default_opts();
+    const int disc = (int)o.discretization, loc = (int)o.bound_state_localization;
+    const bool slow = disc == (int)fnft_nse_discretization_BO
+                      || (disc >= (int)fnft_nse_discretization_CF4_2 && disc <= (int)fnft_nse_discretization_TES4);
+    SEAM_CHECK(!slow && nft_nse_to_akns(disc) < 0, opts->discretization);
+    SEAM_CHECK(loc < 0 || loc > 2, opts->bound_state_localization);
+    SEAM_CHECK(loc == (int)fnft_nsev_bsloc_NEWTON, opts->bound_state_localization);   // fnft_amd_discspec_plan_create
+    SEAM_CHECK((int)o.bound_state_filtering < 0 || (int)o.bound_state_filtering > 2, opts->bound_state_filtering);
+    SEAM_CHECK((int)o.discspec_type < 0 || (int)o.discspec_type > 2, opts->discspec_type);
+    if (slow)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (discretization). GPU path covers the fast (polynomial) discretizations.");
+    if (o.richardson_extrapolation_flag != 0)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched discrete spectrum: Richardson extrapolation).");
+    if (K > NftDiscSpecBatch<HipBackend>::kMaxK || batch > NftDiscSpecBatch<HipBackend>::kMaxGroups / K)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched discrete spectrum: K > 65535 or batch*K > 2^31 - 1).");
+    const NftDsOpts d = search_opts(o);
+    size_t ds = 0, nskip = 1, roots = 0;
+    NftDiscSpecSearch<HipBackend>::sizes((size_t)D, d, &ds, &nskip, &roots);
+    if (roots > NftDiscSpecSearch<HipBackend>::kMaxRoots)
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
+                               "Not yet implemented (batched discrete spectrum: more than 16384 roots per signal).");
+    std::unique_ptr<fnft_amd_discspec_plan> h(new (std::nothrow) fnft_amd_discspec_plan());
+    if (h) h->search.reset(new (std::nothrow) NftDiscSpecSearch<HipBackend>(h->be, (size_t)D, (size_t)K, (size_t)batch, d));
+    if (!h || !h->search) return FNFT_EC_NOMEM;
+    DeviceGuard dg(device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    h->device = device;
+    const int rc = h->search->init();
+    if (rc != NFT_SUCCESS || h->be.failed) {
+        (void)h->be.sync();
+        h.reset();                // on the plan's device
+        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    }
+    *plan = h.release();
+    return FNFT_SUCCESS;
+}
+
+FNFT_INT fnft_amd_nsev_discspec_search_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
+                                              void *d_bound_states, void *d_normconsts_or_residues, void *d_K_out,
+                                              void *stream)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(!d_q, q);
+    SEAM_CHECK(T == NULL || T[0] >= T[1], T);
+    SEAM_CHECK(!d_bound_states, bound_states);
+    SEAM_CHECK(!d_K_out, K_out);
+    if (!plan->search) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));   // a guess plan
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    plan->last_K = (const unsigned long long *)d_K_out;
+    const int rc = plan->search->run((const cplx *)d_q, T, (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
+                                     (unsigned long long *)d_K_out);
+    return batch_run_result(plan->be, rc, __func__, __LINE__);
+}
+
+// per-launch timers of the plan's calls, as fnft_amd_plan_set_launch_timing and its two readers
+void fnft_amd_discspec_plan_set_launch_timing(fnft_amd_discspec_plan_t *plan, int enabled)
+{
+    if (!plan) return;
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    plan->be.launch_timing = enabled != 0;
+    plan->be.launches_used = 0;
+}
+
+FNFT_UINT fnft_amd_discspec_plan_launch_count(const fnft_amd_discspec_plan_t *plan)
+{
+    if (!plan) return 0;
+    std::lock_guard<std::mutex> lk(const_cast<fnft_amd_discspec_plan_t *>(plan)->mtx);   // a call appends to the list
+    return plan->be.launches_used;
+}
+
+double fnft_amd_discspec_plan_launch_ms(const fnft_amd_discspec_plan_t *plan, FNFT_UINT i, char *name, FNFT_UINT name_cap)
+{
+    if (!plan) return -1.0;
+    std::lock_guard<std::mutex> lk(const_cast<fnft_amd_discspec_plan_t *>(plan)->mtx);
+    return launch_ms_of(plan->be, i, name, name_cap);
+}
+
+FNFT_INT fnft_amd_discspec_plan_warnings(const fnft_amd_discspec_plan_t *plan, int *warnings)
+{
+    SEAM_CHECK(!plan, plan);
+    SEAM_CHECK(!warnings, warnings);
+    const size_t nb = plan->search ? plan->search->batch : plan->core->batch;
+    for (size_t b = 0; b < nb; b++) warnings[b] = (b < plan->wn.size()) ? plan->wn[b] : 0;
+    return FNFT_SUCCESS;
 }
 
 // ---- batched, device-resident continuous spectrum of fnft_nsev under the slow discretizations ----------------------
@@ -1268,7 +1408,7 @@ FNFT_INT fnft_amd_slow_plan_finish(fnft_amd_slow_plan_t *plan, void *stream, FNF
 {
     SEAM_CHECK(!plan, plan);
     return batch_finish(
-        plan, stream, status, [&](NftSlowPlan<HipBackend> &c) { return c.read(plan->st, plan->wn); },
+        plan, stream, status, [&] { return plan->core->read(plan->st, plan->wn); },
         [&](size_t b, int h) -> FNFT_INT {
             if (warnings) warnings[b] = (plan->wn[b] & 4) ? 1 : 0;
             // src/fnft_nsev.c:850-853 through the two callers that wrap it, as the fast plan reports it

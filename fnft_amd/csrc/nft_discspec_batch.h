@@ -67,9 +67,10 @@ public:
 
     size_t workspace_bytes() const { return mem.bytes + (front ? front->mem.bytes : 0); }
 
-    // enqueues everything; waits for nothing.  d_nc may be NULL (no norming constants / residues)
+    // enqueues everything; waits for nothing.  d_nc may be NULL (no norming constants / residues); d_nguess: live guesses
+    // per signal (the guess-free plan's candidates, nft_discspec_search.h), NULL: K each
     int run(const cplx *d_q, const double T[2], const cplx *d_guess, cplx *d_bs, cplx *d_nc,
-            unsigned long long *d_K)
+            unsigned long long *d_K, const unsigned long long *d_nguess = nullptr)
     {
         // grid and step as NftDiscSpec::prepare forms them for the full signal (Dsub = D, nskip = 1)
         const double eps_in = (T[1] - T[0]) / (double)(D - 1);
@@ -94,6 +95,7 @@ public:
         P.K = (int)K;
         P.batch = (long long)batch;
         P.guess = d_guess;
+        P.nguess = d_nguess;
         P.lam = lam;
         P.src = (o.niter > 0) ? lam : d_guess;
         P.box = box;

@@ -227,6 +227,49 @@ struct KAberthApply {
     static constexpr size_t lds_bytes() { return 0; }
     static FA_DEV void body(const Params &p) { body_aberth_apply(p); }
 };
+// batched root finder of the guess-free discrete spectrum (nft_discspec_search.h)
+struct KDsGather {
+    using Params = GatherParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_ds_gather(p); }
+};
+struct KAberthBStart {
+    using Params = AberthBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 2 * 256 * sizeof(int) + (size_t)kAbStartLds * (sizeof(double) + sizeof(int)); }
+    static FA_DEV void body(const Params &p) { body_aberthb_start(p); }
+};
+struct KAberthBNewton {
+    using Params = AberthBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 2 * 512 * (sizeof(cplx) + sizeof(double)); }
+    static FA_DEV void body(const Params &p) { body_aberthb_newton<512>(p); }
+};
+struct KAberthBSum {
+    using Params = AberthBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 256 * sizeof(cplx); }
+    static FA_DEV void body(const Params &p) { body_aberthb_sum<256>(p); }
+};
+struct KAberthBApply {
+    using Params = AberthBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_aberthb_apply(p); }
+};
+struct KAberthBStep {
+    using Params = AberthBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return 0; }
+    static FA_DEV void body(const Params &p) { body_aberthb_step(p); }
+};
+struct KDsCandidates {
+    using Params = AberthBatchParams;
+    static constexpr int THREADS = 256;
+    static constexpr size_t lds_bytes() { return (256 + 1) * sizeof(int); }
+    static FA_DEV void body(const Params &p) { body_ds_candidates(p); }
+};
 template <int DEG> struct LeafCfg {
     static constexpr int SPT = (DEG == 1) ? 8 : (DEG == 2 ? 4 : 2);
 };

@@ -2761,6 +2761,8 @@ struct DsBatchParams {
     long long batch;
     long long b0;             // body_ds_norm: first signal of this launch
     const cplx *guess;        // batch*K initial values (never written)
+    const unsigned long long *nguess;   // batch: live guesses per signal (the first nguess[b] slots), or NULL: all K.
+                              //   Slots beyond the count are neither refined nor ever returned, under any filter
     cplx *lam;                // batch*K refined values (body_ds_newton out)
     const cplx *src;          // body_ds_filter in: lam, or guess when nothing was refined
     double *box;              // batch*4: re_lo, re_hi, im_lo, im_hi
@@ -2834,6 +2836,10 @@ template <bool LDSQ> FA_DEV void body_ds_newton(const DsBatchParams &P)
     const long long w = FA_BID;               // signal * K + eigenvalue
     const long long b = w / P.K;
     const cplx *q = P.q + b * P.D;
+    if (P.nguess && (unsigned long long)(w % P.K) >= P.nguess[b]) {   // the whole workgroup: no guess in this slot
+        if (t == 0) P.lam[w] = cmake(__builtin_nan(""), __builtin_nan(""));
+        return;
+    }
     if (LDSQ) {
         for (long long i = t; i < P.D; i += kDsLanes) ql[i] = q[i];
         q = ql;
@@ -2885,15 +2891,16 @@ FA_DEV void body_ds_filter(const DsBatchParams &P)
     const long long b = (long long)FA_BID * FA_BDIM + FA_TID;
     if (b >= P.batch) return;
     const int K = P.K;
+    const int Kin = (P.nguess && P.nguess[b] < (unsigned long long)K) ? (int)P.nguess[b] : K;   // live slots
     const cplx *src = P.src + b * K;
     cplx *v = P.bs + b * K;
     int n = 0;
     if (P.bsfilt == 0) {
-        for (int i = 0; i < K; i++) v[i] = src[i];
-        n = K;
+        for (int i = 0; i < Kin; i++) v[i] = src[i];
+        n = Kin;
     } else {
         const double *box = P.box + 4 * b;
-        for (int i = 0; i < K; i++) {
+        for (int i = 0; i < Kin; i++) {
             const cplx x = src[i];
             if (!(x.x >= box[0]) || !(x.x <= box[1])) continue;
             if (!(x.y >= box[2]) || !(x.y <= box[3])) continue;
@@ -3851,15 +3858,15 @@ struct AberthParams {
 // of the error scale) per lane, with the coefficients staged through LDS in tiles that the workgroup loads
 // together.  asc(k) is the coefficient of x^k: x = z reads coef[n-k], x = 1/z (|z| > 1) reads coef[k].
 // blockIdx.y = segment of the coefficient range (AberthParams).
-template <int TILE> FA_DEV void body_aberth_newton(const AberthParams &P)
+template <int TILE> FA_DEV void aberth_newton_core(const AberthParams &P, long long bx, long long by)
 {
     constexpr int NCH = 8;
     FA_LDS_DECL
     cplx *tile = (cplx *)FA_LDS_PTR;
     double *tabs = (double *)(tile + 2 * TILE);   // |coefficient| of the same tile, both orientations
-    const long long li = (long long)FA_BID * FA_BDIM + FA_TID;
+    const long long li = bx * FA_BDIM + FA_TID;
     const long long n = P.n;
-    const long long base = (long long)FA_BID_Y * P.L;   // lowest power of this segment
+    const long long base = by * P.L;   // lowest power of this segment
     const bool act = li < P.na;
     const cplx z = act ? P.z[P.idx[li]] : cmake(0.5, 0.0);
     const bool inside = cnorm2(z) <= 1.0;
@@ -3919,11 +3926,13 @@ template <int TILE> FA_DEV void body_aberth_newton(const AberthParams &P)
         escale = fma(axp, ec[c], escale);
     }
     dp = dp + (xp[NCH - 1] * dsum) * (double)NCH;
-    const long long o = (long long)FA_BID_Y * P.na + li;
+    const long long o = by * P.na + li;
     P.pp[o] = p;
     P.pd[o] = dp;
     P.pe[o] = escale;
 }
+
+template <int TILE> FA_DEV void body_aberth_newton(const AberthParams &P) { aberth_newton_core<TILE>(P, FA_BID, FA_BID_Y); }
 
 // x^e, e >= 0, by repeated squaring (|x| <= 1: underflow to zero is the right answer)
 FA_DEV cplx c_powi(cplx x, long long e)
@@ -3953,15 +3962,15 @@ FA_DEV cplx aberth_term(cplx zk, cplx zj, bool own, bool &hit)
     return cmake(d.x * inv, -d.y * inv);
 }
 // Partial Aberth sums: blockIdx.y = segment of the estimates z_j, lane = estimate k.
-template <int TILE> FA_DEV void body_aberth_sum(const AberthParams &P)
+template <int TILE> FA_DEV void aberth_sum_core(const AberthParams &P, long long bx, long long by)
 {
     FA_LDS_DECL
     cplx *tile = (cplx *)FA_LDS_PTR;
-    const long long li = (long long)FA_BID * FA_BDIM + FA_TID;
+    const long long li = bx * FA_BDIM + FA_TID;
     const bool act = li < P.na;
     const long long k = act ? (long long)P.idx[li] : -1;
     const cplx zk = act ? P.z[k] : cmake(0.0, 0.0);
-    const long long jlo = (long long)FA_BID_Y * P.J;
+    const long long jlo = by * P.J;
     const long long jhi = (jlo + P.J < P.n) ? jlo + P.J : P.n;
     cplx s = cmake(0.0, 0.0);
     bool hit = false;   // this estimate coincides with another one
@@ -4020,16 +4029,18 @@ template <int TILE> FA_DEV void body_aberth_sum(const AberthParams &P)
         if (k >= jlo && k < jhi) s = s - cmake(1.0, 0.0);   // the own term was counted as 1/(1 + 0i)
     }
     if (act) {
-        P.ps[(long long)FA_BID_Y * P.na + li] = s;
+        P.ps[by * P.na + li] = s;
         if (hit) P.hit[k] = 1;
     }
 }
 
+template <int TILE> FA_DEV void body_aberth_sum(const AberthParams &P) { aberth_sum_core<TILE>(P, FA_BID, FA_BID_Y); }
+
 // Joins the segments: p(z), p'(z) and the error scale from the segment polynomials (Horner in x^L), the Newton
 // correction w = p/p', the Aberth sum, and the new estimate z - w/(1 - w*sum).
-FA_DEV void body_aberth_apply(const AberthParams &P)
+FA_DEV void aberth_apply_core(const AberthParams &P, long long bx)
 {
-    const long long li = (long long)FA_BID * FA_BDIM + FA_TID;
+    const long long li = bx * FA_BDIM + FA_TID;
     const long long n = P.n;
     const bool act = li < P.na;
     double rel = 0.0;
@@ -4096,6 +4107,337 @@ FA_DEV void body_aberth_apply(const AberthParams &P)
     const int slot = fa_wave_append_slot(P.cnt, moved);
     if (moved) P.idx_out[slot] = (int)k;
     fa_wave_atomic_max_f64bits(P.maxcorr, rel);
+}
+FA_DEV void body_aberth_apply(const AberthParams &P) { aberth_apply_core(P, FA_BID); }
+
+// ---------------------------------------------------------------------------------------------
+// Batched root finder of the guess-free discrete spectrum (fnft_amd_discspec_search_plan_*, nft_discspec_search.h):
+// the Ehrlich-Aberth iteration above with a signal axis, and everything the drop-in does on the host between its
+// launches (NftDiscSpec::roots) moved onto the device.  Signal and workgroup are folded into grid.x; grid.y stays the
+// segment.  Per signal the device keeps an AbState: the host enqueues a FIXED schedule of sweeps, and a workgroup
+// whose signal is not active returns after reading the state.
+//   body_ds_gather      every nskip-th sample of every signal (upsampling factor 1)
+//   body_aberthb_start  per signal: zero coefficients at either end, log|c_k|, upper convex hull, start values
+//   body_aberthb_newton / _sum / _apply   the cores of the single-signal kernels on signal b's arrays
+//   body_aberthb_step   per signal, after every sweep: what the host loop of NftDiscSpec::roots does with the two
+//                       words it reads back (stop rule, active list, buffer swap), and the start of the polish sweeps
+//   body_ds_candidates  per signal: z -> lambda, box test of the subsampled signal over all roots in parallel (ordered
+//                       compaction), in-order merge of the survivors by one lane, truncation to K
+// ---------------------------------------------------------------------------------------------
+struct GatherParams {
+    const cplx *q;       // batch * D
+    cplx *out;           // batch * Dsub
+    long long D, Dsub, nskip, batch;
+};
+FA_DEV void body_ds_gather(const GatherParams &P)
+{
+    const long long g = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (g >= P.batch * P.Dsub) return;
+    const long long b = g / P.Dsub, i = g % P.Dsub;
+    P.out[g] = P.q[b * P.D + i * P.nskip];
+}
+
+constexpr int kAbSweeps = 80;              // NftDiscSpec::kAberthMaxSweeps and its three levels
+constexpr double kAbTol = 4.0e-14, kAbFastAbove = 1.0e-3, kAbFail = 1.0e-6;
+constexpr int kAbSegCap = 16;              // most segments of a sweep (kSegCap of NftDiscSpec::roots)
+constexpr int kAbStartLds = 4096;          // body_aberthb_start: up to this many coefficients, log|c_k| and the hull in LDS
+struct AbState {
+    unsigned long long maxcorr;   // bits of the running sweep's largest relative correction
+    double mc;                    // the last finished sweep's
+    int cnt;                      // estimates the running sweep has moved
+    int na;                       // estimates of the running sweep
+    int active;                   // the sweep kernels work on this signal
+    int zin, iin;                 // buffers the running sweep reads; it writes zbuf[zout], ibuf[iin ^ 1]
+    int zout;
+    int sweeps;
+    int m, nl;                    // degree without the zero coefficients at either end; leading zeros
+    int polish;
+};
+struct AberthBatchParams {
+    const cplx *tm;      // transfer matrices, entry 11 of signal b at b*tm_stride: n+1 coefficients, highest power first
+    long long tm_stride;
+    long long n;         // roots per signal
+    long long batch;
+    int gxn;             // workgroups per signal and segment: ceil(n/256)
+    int S;               // segments (the same for every signal and sweep of a plan)
+    cplx *zbuf[2];       // batch*n each
+    int *ibuf[2];        // batch*n each
+    int *hit;            // batch*n
+    cplx *pp, *pd, *ps;  // batch*S*n
+    double *pe;
+    AbState *state;      // batch
+    double *la;          // batch*(n+1), or NULL when n+1 <= kAbStartLds
+    int *hull;           // the same
+    int stage;           // body_aberthb_step: 0 after a sweep, 1 after the last sweep, 2 after the first polish sweep
+    int *status;         // batch; bit 3: the root finder did not converge
+    int *warn;           // batch; bit 0: more than K candidates, bit 1: stopped at the sweep limit with a small correction
+    // body_ds_candidates
+    double den;          // lambda = log(z) / (i den), den = 2 eps / (deg0 ups)
+    const double *box;   // batch*4, of the signal the roots belong to
+    int bsfilt, K;
+    cplx *cand;          // batch*K
+    unsigned long long *ncand;   // batch
+};
+
+// signal b's arrays as the single-signal kernels see them.  false: nothing to do for this workgroup.  A signal whose
+// degree has dropped below 128 (exact-zero end coefficients) is not segmented, as in NftDiscSpec::roots; its segment
+// arrays keep the plan's stride
+FA_DEV bool aberthb_params(const AberthBatchParams &B, long long b, long long bx, long long by, AberthParams &A)
+{
+    const AbState *s = B.state + b;
+    if (!s->active || bx * FA_BDIM >= (long long)s->na) return false;
+    const long long m = s->m, S = (m < 128) ? 1 : B.S;
+    if (by >= S) return false;
+    A.coef = B.tm + b * B.tm_stride + s->nl;
+    A.n = m;
+    A.z = B.zbuf[s->zin] + b * B.n;
+    A.z_out = B.zbuf[s->zout] + b * B.n;
+    A.fast = (s->mc > kAbFastAbove) ? 1 : 0;
+    A.maxcorr = &B.state[b].maxcorr;
+    A.S = (int)S;
+    A.L = ((m + 1 + S - 1) / S + 7) / 8 * 8;
+    A.J = (m + S - 1) / S;
+    const long long so = b * B.S * B.n;
+    A.pp = B.pp + so; A.pd = B.pd + so; A.ps = B.ps + so; A.pe = B.pe + so;
+    A.hit = B.hit + b * B.n;
+    A.idx = B.ibuf[s->iin] + b * B.n;
+    A.idx_out = B.ibuf[s->iin ^ 1] + b * B.n;
+    A.cnt = &B.state[b].cnt;
+    A.na = s->na;
+    A.polish = s->polish;
+    return true;
+}
+template <int TILE> FA_DEV void body_aberthb_newton(const AberthBatchParams &B)
+{
+    AberthParams A;
+    const long long b = FA_BID / B.gxn, bx = FA_BID % B.gxn;
+    if (!aberthb_params(B, b, bx, FA_BID_Y, A)) return;
+    aberth_newton_core<TILE>(A, bx, FA_BID_Y);
+}
+template <int TILE> FA_DEV void body_aberthb_sum(const AberthBatchParams &B)
+{
+    AberthParams A;
+    const long long b = FA_BID / B.gxn, bx = FA_BID % B.gxn;
+    if (!aberthb_params(B, b, bx, FA_BID_Y, A) || A.polish) return;
+    aberth_sum_core<TILE>(A, bx, FA_BID_Y);
+}
+FA_DEV void body_aberthb_apply(const AberthBatchParams &B)
+{
+    AberthParams A;
+    const long long b = FA_BID / B.gxn, bx = FA_BID % B.gxn;
+    if (!aberthb_params(B, b, bx, 0, A)) return;
+    aberth_apply_core(A, bx);
+}
+
+// one workgroup per signal
+FA_DEV void body_aberthb_start(const AberthBatchParams &B)
+{
+    FA_LDS_DECL
+    int *red = (int *)FA_LDS_PTR;                       // 2 * lanes: first / last non-zero coefficient; then [0..2]: nl, m, hull points
+    double *la = (double *)(red + 2 * 256);
+    int *hull = (int *)(la + kAbStartLds);
+    const long long b = FA_BID, n = B.n;
+    const int t = FA_TID, nlanes = FA_BDIM;
+    const cplx *c = B.tm + b * B.tm_stride;
+    if (n + 1 > kAbStartLds) {
+        la = B.la + b * (n + 1);
+        hull = B.hull + b * (n + 1);
+    }
+    int first = (int)n + 1, last = -1;
+    for (long long k = t; k <= n; k += nlanes)
+        if (c[k].x != 0.0 || c[k].y != 0.0) {
+            if ((int)k < first) first = (int)k;
+            last = (int)k;
+        }
+    red[t] = first; red[nlanes + t] = last;
+    FA_SYNC();
+    if (t == 0) {
+        for (int g = 1; g < nlanes; g++) {
+            if (red[g] < first) first = red[g];
+            if (red[nlanes + g] > last) last = red[nlanes + g];
+        }
+        // NftDiscSpec::roots: leading zeros are roots at infinity, trailing ones roots at zero, the iteration runs on the rest
+        const int nl = (first < (int)n) ? first : (int)n;
+        int nt = (last < 0) ? 0 : (int)n - last;
+        if (nt > (int)n - nl) nt = (int)n - nl;
+        red[0] = nl;
+        red[1] = (int)n - nl - nt;
+    }
+    FA_SYNC();
+    const int nl = red[0], m = red[1];
+    FA_SYNC();
+    c += nl;
+    for (int k = t; k <= m; k += nlanes) {
+        const double a = hypot(c[m - k].x, c[m - k].y);   // ascending powers; no overflow of the square, as std::abs
+        la[k] = a > 0.0 ? log(a) : -1.0e300;
+    }
+    FA_SYNC();
+    if (t == 0) {   // upper convex hull of (k, log|c_k|), Andrew's chain
+        int nh = 0;
+        for (int k = 0; k <= m; k++) {
+            while (nh >= 2) {
+                const int k1 = hull[nh - 2], k2 = hull[nh - 1];
+                if ((la[k2] - la[k1]) * (double)(k - k1) <= (la[k] - la[k1]) * (double)(k2 - k1)) nh--;
+                else break;
+            }
+            hull[nh++] = k;
+        }
+        red[2] = nh;
+    }
+    FA_SYNC();
+    const int nh = red[2];
+    cplx *z0 = B.zbuf[0] + b * n, *z1 = B.zbuf[1] + b * n;
+    int *id = B.ibuf[0] + b * n, *hit = B.hit + b * n;
+    const double tau = 6.283185307179586476925286766559;
+    for (int i = t; i < (int)n; i += nlanes) {
+        cplx z;
+        if (i < m) {   // the hull segment [hull[h], hull[h+1]) that holds i: moduli from its slope, angles equispaced
+            int lo = 0, hi = nh - 1;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) / 2;
+                if (hull[mid] <= i) lo = mid; else hi = mid;
+            }
+            const int k1 = hull[lo], k2 = hull[lo + 1], mm = k2 - k1, j = i - k1;
+            double lr = (la[k1] - la[k2]) / (double)mm;
+            if (lr > 300.0) lr = 300.0;
+            if (lr < -300.0) lr = -300.0;
+            const double r = exp(lr);
+            const double ang = tau * (double)j / (double)mm + tau * (double)lo / (double)m + 0.7;
+            double sn, cs;
+            fa_sincos(ang, &sn, &cs);
+            z = cmake(r * cs, r * sn);
+        } else if (i < m + nl) z = cmake(bs_inf(), 0.0);
+        else z = cmake(0.0, 0.0);
+        z0[i] = z; z1[i] = z;
+        id[i] = i;
+        hit[i] = 0;
+    }
+    if (t == 0) {
+        AbState s;
+        s.maxcorr = 0ull;
+        s.mc = (m > 0) ? 1.0 : 0.0;
+        s.cnt = 0;
+        s.na = m;
+        s.active = (m > 0) ? 1 : 0;
+        s.zin = 0; s.zout = 1; s.iin = 0;
+        s.sweeps = 0;
+        s.m = m; s.nl = nl;
+        s.polish = 0;
+        B.state[b] = s;
+    }
+}
+
+// one workgroup per signal
+FA_DEV void body_aberthb_step(const AberthBatchParams &B)
+{
+    const long long b = FA_BID;
+    const int t = FA_TID;
+    AbState s = B.state[b];
+    FA_SYNC();
+    bool fill = false;
+    if (s.active && !s.polish) {   // a sweep of the iteration has run
+        union { double d; unsigned long long u; } cv;
+        cv.u = s.maxcorr;
+        s.mc = cv.d;
+        s.na = s.cnt;
+        s.sweeps++;
+        s.zin ^= 1; s.zout ^= 1; s.iin ^= 1;
+        if (s.mc < kAbTol || s.na == 0 || s.sweeps >= kAbSweeps) s.active = 0;
+    } else if (s.active && B.stage == 2) {   // the first polish sweep has run: the second takes what it moved, in place
+        s.na = s.cnt;
+        s.zin ^= 1;
+        s.zout = s.zin;
+        s.iin = 1;
+        if (s.na == 0) s.active = 0;
+    }
+    s.maxcorr = 0ull;
+    s.cnt = 0;
+    if (B.stage == 1) {
+        s.active = 0;
+        if (s.m > 0 && s.mc < kAbFail) {   // polish: every estimate, plain Newton steps
+            s.polish = 1;
+            s.active = 1;
+            s.na = s.m;
+            s.iin = 0;
+            s.zout = s.zin ^ 1;
+            fill = true;
+        }
+        if (t == 0 && !(s.mc < kAbTol)) {
+            if (!(s.mc < kAbFail)) B.status[b] |= 8;
+            else B.warn[b] |= 2;
+        }
+    }
+    if (fill) {
+        int *id = B.ibuf[0] + b * B.n;
+        for (int i = t; i < s.m; i += FA_BDIM) id[i] = i;
+    }
+    if (t == 0) B.state[b] = s;
+}
+
+// one workgroup per signal
+FA_DEV void body_ds_candidates(const AberthBatchParams &B)
+{
+    FA_LDS_DECL
+    int *flag = (int *)FA_LDS_PTR;    // lanes, then [lanes]: the count
+    const long long b = FA_BID, n = B.n;
+    const int t = FA_TID, nlanes = FA_BDIM;
+    const AbState *s = B.state + b;
+    const cplx *z = B.zbuf[s->zin] + b * n;
+    cplx *v = B.zbuf[s->zin ^ 1] + b * n;      // free after the last sweep: the candidates in root order
+    const double *box = B.box + 4 * b;
+    const bool failed = (B.status[b] & 8) != 0;
+    const double qn = __builtin_nan("");
+    int ns = 0;
+    for (long long i0 = 0; i0 < n && !failed; i0 += nlanes) {
+        const long long i = i0 + t;
+        bool pass = false;
+        cplx l = cmake(qn, qn);
+        if (i < n) {
+            const cplx zi = z[i];
+            const double lr = log(hypot(zi.x, zi.y));   // finite for every finite non-zero z, as std::log(z)
+            if (lr - lr == 0.0) l = cmake(atan2(zi.y, zi.x) / B.den, -lr / B.den);   // log(z) / (i den)
+            pass = true;
+            if (B.bsfilt != 0) pass = (l.x >= box[0]) && (l.x <= box[1]) && (l.y >= box[2]) && (l.y <= box[3]);
+        }
+        flag[t] = pass ? 1 : 0;
+        FA_SYNC();
+        int before = 0, all = 0;
+        for (int g = 0; g < nlanes; g++) {
+            before += (g < t) ? flag[g] : 0;
+            all += flag[g];
+        }
+        if (pass) v[ns + before] = l;
+        ns += all;
+        FA_SYNC();
+    }
+    if (t == 0) {
+        int kept = ns;
+        bool over = false;
+        if (B.bsfilt == 0) {
+            if (kept > B.K) { kept = B.K; over = true; }
+        } else if (ns > 0) {   // NftDiscSpec::filter_merge in place, stopped once K + 1 are known to survive
+            const double tol = sqrt(2.220446049250313e-16);
+            kept = 1;
+            for (int i = 1; i < ns; i++) {
+                double dist = -1.0;
+                const cplx vi = v[i];
+                for (int j = 0; j < i; j++) {
+                    dist = sqrt(cnorm2(v[j] - vi));
+                    if (dist < tol) break;
+                }
+                if (dist < tol) continue;
+                if (kept == B.K) { over = true; break; }
+                v[kept++] = vi;
+            }
+        }
+        if (over) B.warn[b] |= 1;
+        B.ncand[b] = (unsigned long long)kept;
+        flag[nlanes] = kept;
+    }
+    FA_SYNC();
+    const int kept = flag[nlanes];
+    cplx *cand = B.cand + b * B.K;
+    for (int i = t; i < B.K; i += nlanes) cand[i] = (i < kept) ? v[i] : cmake(qn, qn);
 }
 
 // ---------------------------------------------------------------------------------------------

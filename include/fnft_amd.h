@@ -550,6 +550,51 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
 FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *stream, FNFT_INT *status,
                                        FNFT_UINT *K_out);
 
+/* The same WITHOUT guesses: for each of `batch` signals what fnft_nsev computes on it alone with
+ * bound_state_localization = FAST_EIGENVALUE or SUBSAMPLE_AND_REFINE, *K_ptr = K (the capacity per signal), contspec =
+ * NULL and kappa = +1.  opts == NULL: fnft_nsev_default_opts() unchanged (2SPLIT4B, SUBSAMPLE_AND_REFINE, FULL, niter
+ * 10, NORMING_CONSTANTS).  SUBSAMPLE_AND_REFINE: Dsub = opts->Dsub, or (size_t)sqrt(D log2(D)^2) when that is 0,
+ * rounded as the reference rounds it (nskip = round(D/Dsub), Dsub = round(D/nskip)); every nskip-th sample is
+ * gathered (the 19 schemes with upsampling factor 1) or resampled (4SPLIT4A/B), one batched product tree gives the
+ * transfer matrices of the subsampled signals, a batched Ehrlich-Aberth iteration all roots of their entry 11 (start
+ * values, sweeps, stopping rule and polish sweeps on the device: a fixed schedule of 80 sweeps is enqueued, and the
+ * workgroups of a converged signal return at once), the roots are mapped to lambda, filtered and merged in the
+ * subsampled signal's box and truncated to K, and the stages of the guess plan refine them on the full signal.
+ * FAST_EIGENVALUE: the roots of the full signal's a-polynomial, filter and merge, norming constants; no Newton stage.
+ * A signal's bound states come in the root finder's order: deterministic, but not promised equal to the drop-in's.
+ * fnft_amd_discspec_plan_destroy, _workspace_bytes and _finish serve these plans too.
+ * Create-time codes, before any HIP call: FNFT_EC_INVALID_ARGUMENT for plan == NULL, D < 2, K == 0, batch == 0, an
+ * unknown discretization, localization, filtering or discspec_type, and the localization NEWTON (that is
+ * fnft_amd_discspec_plan_create); FNFT_EC_NOT_YET_IMPLEMENTED for the slow discretizations,
+ * richardson_extrapolation_flag != 0, K > 65535 or batch*K > 2^31 - 1, and more than 16384 roots per signal (the
+ * degree of the transfer matrix: Dsub * upsampling factor * degree per sample under SUBSAMPLE_AND_REFINE, with D in
+ * place of Dsub under FAST_EIGENVALUE; the drop-in remains the path above it).  Every workspace is allocated at
+ * create; a call allocates nothing, never waits for the device and copies nothing to the host. */
+FNFT_INT fnft_amd_discspec_search_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UINT D, FNFT_UINT K,
+                                              FNFT_UINT batch, fnft_nsev_opts_t const *opts, int device);
+/* Needs no device: the number of roots per signal a plan of these sizes searches (0: sizes or options no plan can
+ * have); *Dsub (may be NULL): the subsampled length actually used (D under FAST_EIGENVALUE). */
+FNFT_UINT fnft_amd_discspec_search_plan_roots(FNFT_UINT D, fnft_nsev_opts_t const *opts, FNFT_UINT *Dsub);
+/* Arrays and layouts exactly as for fnft_amd_nsev_discspec_device, without d_guesses.  FNFT_EC_INVALID_ARGUMENT,
+ * before anything is enqueued, for a NULL plan, d_q, d_bound_states, d_K_out or T, or T[0] >= T[1];
+ * -FNFT_EC_INVALID_ARGUMENT for a plan of fnft_amd_discspec_plan_create (and from fnft_amd_nsev_discspec_device for
+ * a plan of this kind).  status[b] of fnft_amd_discspec_plan_finish: as there, the step-size check of 2SPLIT2_MODAL on
+ * the subsampled step as well as the full one, and -FNFT_EC_OTHER where the root finder's last correction is not
+ * below its failure level (1e-6). */
+FNFT_INT fnft_amd_nsev_discspec_search_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
+                                              void *d_bound_states, void *d_normconsts_or_residues, void *d_K_out,
+                                              void *stream);
+/* After fnft_amd_discspec_plan_finish: warnings[b] (batch ints) bit 0 = more bound states found than K (truncated: the
+ * drop-in's "more than *K_ptr" warning), bit 1 = the root finder stopped at its sweep limit with a small correction.
+ * All zero for a plan of fnft_amd_discspec_plan_create. */
+FNFT_INT fnft_amd_discspec_plan_warnings(const fnft_amd_discspec_plan_t *plan, int *warnings);
+/* Measurement (plans of either creator): an event pair around every kernel launch of the calls that follow, as
+ * fnft_amd_plan_set_launch_timing; enabling clears the list.  Read after the stream is done: launch i of the list, its
+ * kernel's name in `name` (may be NULL), -1 past the end.  Not for production calls: the events serialize the launches. */
+void fnft_amd_discspec_plan_set_launch_timing(fnft_amd_discspec_plan_t *plan, int enabled);
+FNFT_UINT fnft_amd_discspec_plan_launch_count(const fnft_amd_discspec_plan_t *plan);
+double fnft_amd_discspec_plan_launch_ms(const fnft_amd_discspec_plan_t *plan, FNFT_UINT i, char *name, FNFT_UINT name_cap);
+
 /* ---- slow discretizations: batched, device-resident continuous spectrum ---------------------
  * fnft_nsev's contspec of `batch` signals of D samples on one xi-grid of M points with opts->discretization one of
  * BO, CF4_2, CF4_3, CF5_3, CF6_4, ES4, TES4: the schemes without a polynomial transfer matrix, one 2x2 step matrix
