@@ -1,8 +1,10 @@
 // hip_be.h -- HIP back end of NftPlan (device memory, copies, kernel launches, event timers) and the
-// kernel entry template.  The library is built from several translation units so that the ~200 kernel
+// kernel entry template.  The library is built from 23 kernel translation units so that the 258 kernel
 // instantiations compile in parallel: HipBackend::run<K> is only DECLARED for the host logic
-// (hip_backend.hip); each hip_kernels_*.hip defines FA_HIP_RUN_IMPL, sees the definition, and
-// instantiates run<K> -- and with it kernel_entry<K> -- explicitly for its group of kernels.
+// (hip_backend.hip); each hip_kernels_<name>.hip defines FA_HIP_RUN_IMPL, sees the definition, and
+// instantiates run<K> -- and with it kernel_entry<K> -- explicitly for its group of kernels,
+// FA_UNIT_<name>(FA_INST).  nft_kernel_list.h states the groups, from the same size lists the dispatch
+// switches of nft_dispatch.h read.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,31 +1,3 @@
-// hip_kernels_chirpa.hip -- kernel instantiations of group "chirpa" (see hip_be.h); written by gen_kernel_units.py, gfx950 only.
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
-
-FA_INST(KChirpRows)
-FA_INST(KChirpColFwd<2, false>)
-FA_INST(KChirpColFwd<4, false>)
-FA_INST(KChirpColFwd<8, false>)
-FA_INST(KChirpColFwd<16, false>)
-FA_INST(KChirpColFwd<32, false>)
-FA_INST(KChirpColFwd<64, false>)
-FA_INST(KChirpColFwd<128, false>)
-FA_INST(KChirpColFwd<256, false>)
-FA_INST(KChirpColFwd<512, false>)
-FA_INST(KChirpColFwd<1024, false>)
-FA_INST(KChirpColFwd<2048, false>)
-FA_INST(KChirpColFwd<4096, false>)
-FA_INST(KChirpColFwd<8192, false>)
-FA_INST(KChirpColFwd<2, true>)
-FA_INST(KChirpColFwd<4, true>)
-FA_INST(KChirpColFwd<8, true>)
-FA_INST(KChirpColFwd<16, true>)
-FA_INST(KChirpColFwd<32, true>)
-FA_INST(KChirpColFwd<64, true>)
-FA_INST(KChirpColFwd<128, true>)
-FA_INST(KChirpColFwd<256, true>)
-FA_INST(KChirpColFwd<512, true>)
-FA_INST(KChirpColFwd<1024, true>)
-FA_INST(KChirpColFwd<2048, true>)
-FA_INST(KChirpColFwd<4096, true>)
-FA_INST(KChirpColFwd<8192, true>)
+FA_UNIT_chirpa(FA_INST)   // nft_kernel_list.h

@@ -1,43 +1,3 @@
-// hip_kernels_chirpb.hip -- kernel instantiations of group "chirpb" (see hip_be.h); written by gen_kernel_units.py, gfx950 only.
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
-
-FA_INST(KChirpColInv<2, false, false>)
-FA_INST(KChirpColInv<4, false, false>)
-FA_INST(KChirpColInv<8, false, false>)
-FA_INST(KChirpColInv<16, false, false>)
-FA_INST(KChirpColInv<32, false, false>)
-FA_INST(KChirpColInv<64, false, false>)
-FA_INST(KChirpColInv<128, false, false>)
-FA_INST(KChirpColInv<256, false, false>)
-FA_INST(KChirpColInv<512, false, false>)
-FA_INST(KChirpColInv<1024, false, false>)
-FA_INST(KChirpColInv<2048, false, false>)
-FA_INST(KChirpColInv<4096, false, false>)
-FA_INST(KChirpColInv<8192, false, false>)
-FA_INST(KChirpColInv<2, true, false>)
-FA_INST(KChirpColInv<4, true, false>)
-FA_INST(KChirpColInv<8, true, false>)
-FA_INST(KChirpColInv<16, true, false>)
-FA_INST(KChirpColInv<32, true, false>)
-FA_INST(KChirpColInv<64, true, false>)
-FA_INST(KChirpColInv<128, true, false>)
-FA_INST(KChirpColInv<256, true, false>)
-FA_INST(KChirpColInv<512, true, false>)
-FA_INST(KChirpColInv<1024, true, false>)
-FA_INST(KChirpColInv<2048, true, false>)
-FA_INST(KChirpColInv<4096, true, false>)
-FA_INST(KChirpColInv<8192, true, false>)
-FA_INST(KChirpColInv<2, false, true>)
-FA_INST(KChirpColInv<4, false, true>)
-FA_INST(KChirpColInv<8, false, true>)
-FA_INST(KChirpColInv<16, false, true>)
-FA_INST(KChirpColInv<32, false, true>)
-FA_INST(KChirpColInv<64, false, true>)
-FA_INST(KChirpColInv<128, false, true>)
-FA_INST(KChirpColInv<256, false, true>)
-FA_INST(KChirpColInv<512, false, true>)
-FA_INST(KChirpColInv<1024, false, true>)
-FA_INST(KChirpColInv<2048, false, true>)
-FA_INST(KChirpColInv<4096, false, true>)
-FA_INST(KChirpColInv<8192, false, true>)
+FA_UNIT_chirpb(FA_INST)   // nft_kernel_list.h

@@ -1,28 +1,3 @@
-// hip_kernels_col.hip -- kernel instantiations of group "col" (see hip_be.h); written by gen_kernel_units.py, gfx950 only.
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
-
-FA_INST(KColFwd<4>)
-FA_INST(KColFwd<8>)
-FA_INST(KColFwd<16>)
-FA_INST(KColFwd<32>)
-FA_INST(KColFwd<64>)
-FA_INST(KColFwd<128>)
-FA_INST(KColFwd<256>)
-FA_INST(KColFwd<512>)
-FA_INST(KColFwd<1024>)
-FA_INST(KColFwd<2048>)
-FA_INST(KColFwd<4096>)
-FA_INST(KColFwd<8192>)
-FA_INST(KColInv<4>)
-FA_INST(KColInv<8>)
-FA_INST(KColInv<16>)
-FA_INST(KColInv<32>)
-FA_INST(KColInv<64>)
-FA_INST(KColInv<128>)
-FA_INST(KColInv<256>)
-FA_INST(KColInv<512>)
-FA_INST(KColInv<1024>)
-FA_INST(KColInv<2048>)
-FA_INST(KColInv<4096>)
-FA_INST(KColInv<8192>)
+FA_UNIT_col(FA_INST)   // nft_kernel_list.h

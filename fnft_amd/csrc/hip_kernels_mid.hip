@@ -1,6 +1,3 @@
-// hip_kernels_mid.hip -- kernel instantiations of group "mid" (see hip_be.h); written by gen_kernel_units.py, gfx950 only.
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
-
-FA_INST(KMidSym<true>)
-FA_INST(KMidSym<false>)
+FA_UNIT_mid(FA_INST)   // nft_kernel_list.h

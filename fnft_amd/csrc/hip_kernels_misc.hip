@@ -1,47 +1,3 @@
-// hip_kernels_misc.hip -- kernel instantiations of group "misc" (see hip_be.h); written by gen_kernel_units.py, gfx950 only.
 #define FA_HIP_RUN_IMPL
 #include "hip_be.h"
-
-FA_INST(KCoeffs<1>)
-FA_INST(KCoeffs<2>)
-FA_INST(KCoeffs<3>)
-FA_INST(KCoeffs<4>)
-FA_INST(KCoeffsProg)
-FA_INST(KResamplePhase)
-FA_INST(KResampleCombine)
-FA_INST(KBandCheck)
-FA_INST(KBsChunk<false>)
-FA_INST(KBsChunk<true>)
-FA_INST(KBsCombine<false>)
-FA_INST(KBsCombine<true>)
-FA_INST(KBsPhi)
-FA_INST(KBsMetric)
-FA_INST(KBsPick)
-FA_INST(KBsPsi)
-FA_INST(KBsMatrix)
-FA_INST(KGridMark)
-FA_INST(KGridMarkPh)
-FA_INST(KCompactCount)
-FA_INST(KCompactScatter)
-FA_INST(KInvOp)
-FA_INST(KInvSolitons)
-FA_INST(KInvCdt)
-FA_INST(KInvDsPrep)
-FA_INST(KPeelImport)
-FA_INST(KPeelLeaf)
-FA_INST(KPeelProduct<512>)
-FA_INST(KPeelProduct<1024>)
-FA_INST(KPeelProduct<2048>)
-FA_INST(KAberthNewton)
-FA_INST(KAberthSum)
-FA_INST(KAberthApply)
-FA_INST(KFinalizeScales)
-FA_INST(KExportTm)
-FA_INST(KImportLevel0)
-FA_INST(KLeaf<1>)
-FA_INST(KLeaf<2>)
-FA_INST(KLeaf<3>)
-FA_INST(KLeaf<4>)
-FA_INST(KPairSchool<1>)
-FA_INST(KPairSchool<2>)
-FA_INST(KPairSchool<3>)
+FA_UNIT_misc(FA_INST)   // nft_kernel_list.h

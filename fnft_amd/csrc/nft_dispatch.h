@@ -4,6 +4,7 @@
 // A kernel functor K provides: Params, THREADS, lds_bytes(), body(const Params&).
 // A back end BE provides: template<class K> void run(int gx, int gy, const typename K::Params&).
 #pragma once
+#include "nft_kernel_list.h"
 #include "nft_kernels.h"
 #include "nft_real.h"
 
@@ -19,164 +20,49 @@ constexpr int kFusedMaxN = 4096;    // largest pair product done by one workgrou
 constexpr int kSchoolMaxDeg = 3;    // direct products up to this input degree
 
 // ---- simple one-lane-per-item kernels --------------------------------------------------------
-template <int DEG> struct KCoeffs {
-    using Params = CoeffParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_coeffs<DEG>(p); }
-};
-struct KCoeffsProg {
-    using Params = CoeffProgParams;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return (size_t)(24 + 16) * 64 * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_coeffs_prog(p); }
-};
-struct KResamplePhase {
-    using Params = ResampleParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_resample_phase(p); }
-};
-struct KBandCheck {
-    using Params = ResampleParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 3 * 256 * sizeof(double); }
-    static FA_DEV void body(const Params &p) { body_band_check(p); }
-};
-struct KResampleCombine {
-    using Params = ResampleParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_resample_combine(p); }
-};
-template <bool BACKWARD> struct KBsChunk {
-    using Params = BsParams;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_bs_chunk<BACKWARD>(p); }
-};
-template <bool BACKWARD> struct KBsCombine {
-    using Params = BsParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * 12 * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_bs_combine<BACKWARD>(p); }
-};
-struct KBsMatrix {
-    using Params = BsParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * 8 * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_bs_matrix(p); }
-};
-struct KBsPhi {
-    using Params = BsParams;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_bs_phi(p); }
-};
-struct KBsMetric {
-    using Params = BsParams;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_bs_metric(p); }
-};
-struct KBsPick {
-    using Params = BsParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * (sizeof(double) + sizeof(int)); }
-    static FA_DEV void body(const Params &p) { body_bs_pick(p); }
-};
-struct KBsPsi {
-    using Params = BsParams;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_bs_psi(p); }
-};
+// a functor that only forwards to one body function: name, Params, THREADS, LDS bytes, body
+#define FA_FUNCTOR(NAME, PARAMS, NTHREADS, LDS, BODY)                    \
+    struct NAME {                                                       \
+        using Params = PARAMS;                                          \
+        static constexpr int THREADS = NTHREADS;                        \
+        static constexpr size_t lds_bytes() { return LDS; }             \
+        static FA_DEV void body(const Params &p) { BODY(p); }           \
+    }
+template <int DEG> FA_FUNCTOR(KCoeffs, CoeffParams, 256, 0, body_coeffs<DEG>);
+FA_FUNCTOR(KCoeffsProg, CoeffProgParams, 64, (size_t)(24 + 16) * 64 * sizeof(cplx), body_coeffs_prog);
+FA_FUNCTOR(KResamplePhase, ResampleParams, 256, 0, body_resample_phase);
+FA_FUNCTOR(KBandCheck, ResampleParams, 256, 3 * 256 * sizeof(double), body_band_check);
+FA_FUNCTOR(KResampleCombine, ResampleParams, 256, 0, body_resample_combine);
+template <bool BACKWARD> FA_FUNCTOR(KBsChunk, BsParams, 64, 0, body_bs_chunk<BACKWARD>);
+template <bool BACKWARD> FA_FUNCTOR(KBsCombine, BsParams, 256, 256 * 12 * sizeof(cplx), body_bs_combine<BACKWARD>);
+FA_FUNCTOR(KBsMatrix, BsParams, 256, 256 * 8 * sizeof(cplx), body_bs_matrix);
+FA_FUNCTOR(KBsPhi, BsParams, 64, 0, body_bs_phi);
+FA_FUNCTOR(KBsMetric, BsParams, 64, 0, body_bs_metric);
+FA_FUNCTOR(KBsPick, BsParams, 256, 256 * (sizeof(double) + sizeof(int)), body_bs_pick);
+FA_FUNCTOR(KBsPsi, BsParams, 64, 0, body_bs_psi);
 // batched discrete spectrum (nft_discspec_batch.h); LDSQ adds the staged signal to the workgroup's LDS
-struct KDsBox {
-    using Params = DsBatchParams;
-    static constexpr int THREADS = kDsLanes;
-    static constexpr size_t lds_bytes() { return kDsLanes * sizeof(double); }
-    static FA_DEV void body(const Params &p) { body_ds_box(p); }
-};
-template <bool LDSQ> struct KDsNewton {
-    using Params = DsBatchParams;
-    static constexpr int THREADS = kDsLanes;
-    static constexpr size_t lds_bytes() { return ((size_t)kDsLanes * 8 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_ds_newton<LDSQ>(p); }
-};
-struct KDsFilter {
-    using Params = DsBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_ds_filter(p); }
-};
-template <bool LDSQ> struct KDsNorm {
-    using Params = DsBatchParams;
-    static constexpr int THREADS = kDsLanes;
-    static constexpr size_t lds_bytes() { return ((size_t)kDsLanes * 10 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_ds_norm<LDSQ>(p); }
-};
+FA_FUNCTOR(KDsBox, DsBatchParams, kDsLanes, kDsLanes * sizeof(double), body_ds_box);
+template <bool LDSQ> FA_FUNCTOR(KDsNewton, DsBatchParams, kDsLanes,
+                               ((size_t)kDsLanes * 8 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx), body_ds_newton<LDSQ>);
+FA_FUNCTOR(KDsFilter, DsBatchParams, 256, 0, body_ds_filter);
+template <bool LDSQ> FA_FUNCTOR(KDsNorm, DsBatchParams, kDsLanes,
+                               ((size_t)kDsLanes * 10 + 2 + (LDSQ ? kDsLdsSamples : 0)) * sizeof(cplx), body_ds_norm<LDSQ>);
 // slow discretizations (nft_nsev_slow.h): FAM 0 CF family (REALK: real ks), 1 ES4, 2 TES4
-struct KSlowPrep {
-    using Params = SlowParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_slow_prep(p); }
-};
+FA_FUNCTOR(KSlowPrep, SlowParams, 256, 0, body_slow_prep);
 template <int FAM, bool REALK> struct KSlowScatter {
     using Params = SlowParams;
     static constexpr int THREADS = kSlowLanes;
     static constexpr size_t lds_bytes() { return 0; }
     static FA_DEV void body(const Params &p) { body_slow_scatter<FAM, REALK>(p); }
 };
-struct KSlowReduce {
-    using Params = SlowParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_slow_reduce(p); }
-};
-struct KSlowCombine {
-    using Params = SlowParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_slow_combine(p); }
-};
-struct KGridMark {
-    using Params = GridSearchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_gridsearch_mark(p); }
-};
-struct KGridMarkPh {
-    using Params = GridSearchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_gridsearch_mark_ph(p); }
-};
-struct KCompactCount {
-    using Params = GridSearchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * sizeof(int); }
-    static FA_DEV void body(const Params &p) { body_compact_count(p); }
-};
-struct KCompactScatter {
-    using Params = GridSearchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * sizeof(int); }
-    static FA_DEV void body(const Params &p) { body_compact_scatter(p); }
-};
-struct KInvOp {
-    using Params = InvOpParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * sizeof(double); }
-    static FA_DEV void body(const Params &p) { body_inv_op(p); }
-};
-struct KPeelImport {
-    using Params = PeelIoParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_peel_import(p); }
-};
+FA_FUNCTOR(KSlowReduce, SlowParams, 256, 0, body_slow_reduce);
+FA_FUNCTOR(KSlowCombine, SlowParams, 256, 0, body_slow_combine);
+FA_FUNCTOR(KGridMark, GridSearchParams, 256, 0, body_gridsearch_mark);
+FA_FUNCTOR(KGridMarkPh, GridSearchParams, 256, 0, body_gridsearch_mark_ph);
+FA_FUNCTOR(KCompactCount, GridSearchParams, 256, 256 * sizeof(int), body_compact_count);
+FA_FUNCTOR(KCompactScatter, GridSearchParams, 256, 256 * sizeof(int), body_compact_scatter);
+FA_FUNCTOR(KInvOp, InvOpParams, 256, 256 * sizeof(double), body_inv_op);
+FA_FUNCTOR(KPeelImport, PeelIoParams, 256, 0, body_peel_import);
 template <int N> struct KPeelProduct {
     using Params = PeelProdParams;
     static constexpr int R = 8;
@@ -185,91 +71,22 @@ template <int N> struct KPeelProduct {
     static constexpr size_t lds_bytes() { return (size_t)4 * N * sizeof(cplx); }
     static FA_DEV void body(const Params &p) { body_peel_product<N, R>(p); }
 };
-struct KPeelLeaf {
-    using Params = PeelLeafParams;
-    static constexpr int THREADS = 192;
-    static constexpr size_t lds_bytes() { return 256 * sizeof(cplx) + 64; }
-    static FA_DEV void body(const Params &p) { body_peel_leaf(p); }
-};
-struct KInvSolitons {
-    using Params = InvDsParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_inv_solitons(p); }
-};
-struct KInvCdt {
-    using Params = InvDsParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_inv_cdt(p); }
-};
-struct KInvDsPrep {
-    using Params = InvDsPrepParams;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_inv_ds_prep(p); }
-};
-struct KAberthNewton {
-    using Params = AberthParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 2 * 512 * (sizeof(cplx) + sizeof(double)); }
-    static FA_DEV void body(const Params &p) { body_aberth_newton<512>(p); }
-};
-struct KAberthSum {
-    using Params = AberthParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_aberth_sum<256>(p); }
-};
-struct KAberthApply {
-    using Params = AberthParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_aberth_apply(p); }
-};
+FA_FUNCTOR(KPeelLeaf, PeelLeafParams, 192, 256 * sizeof(cplx) + 64, body_peel_leaf);
+FA_FUNCTOR(KInvSolitons, InvDsParams, 256, 0, body_inv_solitons);
+FA_FUNCTOR(KInvCdt, InvDsParams, 256, 0, body_inv_cdt);
+FA_FUNCTOR(KInvDsPrep, InvDsPrepParams, 64, 0, body_inv_ds_prep);
+FA_FUNCTOR(KAberthNewton, AberthParams, 256, 2 * 512 * (sizeof(cplx) + sizeof(double)), body_aberth_newton<512>);
+FA_FUNCTOR(KAberthSum, AberthParams, 256, 256 * sizeof(cplx), body_aberth_sum<256>);
+FA_FUNCTOR(KAberthApply, AberthParams, 256, 0, body_aberth_apply);
 // batched root finder of the guess-free discrete spectrum (nft_discspec_search.h)
-struct KDsGather {
-    using Params = GatherParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_ds_gather(p); }
-};
-struct KAberthBStart {
-    using Params = AberthBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 2 * 256 * sizeof(int) + (size_t)kAbStartLds * (sizeof(double) + sizeof(int)); }
-    static FA_DEV void body(const Params &p) { body_aberthb_start(p); }
-};
-struct KAberthBNewton {
-    using Params = AberthBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 2 * 512 * (sizeof(cplx) + sizeof(double)); }
-    static FA_DEV void body(const Params &p) { body_aberthb_newton<512>(p); }
-};
-struct KAberthBSum {
-    using Params = AberthBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 256 * sizeof(cplx); }
-    static FA_DEV void body(const Params &p) { body_aberthb_sum<256>(p); }
-};
-struct KAberthBApply {
-    using Params = AberthBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_aberthb_apply(p); }
-};
-struct KAberthBStep {
-    using Params = AberthBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_aberthb_step(p); }
-};
-struct KDsCandidates {
-    using Params = AberthBatchParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return (256 + 1) * sizeof(int); }
-    static FA_DEV void body(const Params &p) { body_ds_candidates(p); }
-};
+FA_FUNCTOR(KDsGather, GatherParams, 256, 0, body_ds_gather);
+FA_FUNCTOR(KAberthBStart, AberthBatchParams, 256, 2 * 256 * sizeof(int) + (size_t)kAbStartLds * (sizeof(double) + sizeof(int)),
+          body_aberthb_start);
+FA_FUNCTOR(KAberthBNewton, AberthBatchParams, 256, 2 * 512 * (sizeof(cplx) + sizeof(double)), body_aberthb_newton<512>);
+FA_FUNCTOR(KAberthBSum, AberthBatchParams, 256, 256 * sizeof(cplx), body_aberthb_sum<256>);
+FA_FUNCTOR(KAberthBApply, AberthBatchParams, 256, 0, body_aberthb_apply);
+FA_FUNCTOR(KAberthBStep, AberthBatchParams, 256, 0, body_aberthb_step);
+FA_FUNCTOR(KDsCandidates, AberthBatchParams, 256, (256 + 1) * sizeof(int), body_ds_candidates);
 template <int DEG> struct LeafCfg {
     static constexpr int SPT = (DEG == 1) ? 8 : (DEG == 2 ? 4 : 2);
 };
@@ -279,30 +96,10 @@ template <int DEG> struct KLeaf {
     static constexpr size_t lds_bytes() { return (size_t)THREADS * DEG * LeafCfg<DEG>::SPT * sizeof(cplx); }
     static FA_DEV void body(const Params &p) { body_leaf<DEG, LeafCfg<DEG>::SPT>(p); }
 };
-template <int DEG> struct KPairSchool {
-    using Params = TreeLevel;
-    static constexpr int THREADS = 128;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_pair_school<DEG>(p); }
-};
-struct KFinalizeScales {
-    using Params = TreeLevel;
-    static constexpr int THREADS = 64;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_finalize_scales(p); }
-};
-struct KImportLevel0 {
-    using Params = ImportParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_import_level0(p); }
-};
-struct KExportTm {
-    using Params = ExportParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_export_tm(p); }
-};
+template <int DEG> FA_FUNCTOR(KPairSchool, TreeLevel, 128, 0, body_pair_school<DEG>);
+FA_FUNCTOR(KFinalizeScales, TreeLevel, 64, 0, body_finalize_scales);
+FA_FUNCTOR(KImportLevel0, ImportParams, 256, 0, body_import_level0);
+FA_FUNCTOR(KExportTm, ExportParams, 256, 0, body_export_tm);
 
 // ---- fused pair product ----------------------------------------------------------------------
 #ifndef FA_PAIR_R_SYM
@@ -435,10 +232,9 @@ template <class BE> bool dispatch_coeffs(BE &be, const CoeffParams &p)
     const long long n = (long long)p.batch * p.Dpad;
     const int g = (int)((n + 255) / 256);
     switch (p.deg) {
-    case 1: be.template run<KCoeffs<1>>(g, 1, p); return true;
-    case 2: be.template run<KCoeffs<2>>(g, 1, p); return true;
-    case 3: be.template run<KCoeffs<3>>(g, 1, p); return true;
-    case 4: be.template run<KCoeffs<4>>(g, 1, p); return true;
+#define X(dg, ...) case dg: be.template run<KCoeffs<dg>>(g, 1, p); return true;
+        FA_LIST_COEFFS_DEG(X, _)
+#undef X
     default: return false;
     }
 }
@@ -447,10 +243,9 @@ template <class BE> bool dispatch_coeffs(BE &be, const CoeffParams &p)
 inline int leaf_spt(int deg)
 {
     switch (deg) {
-    case 1: return LeafCfg<1>::SPT;
-    case 2: return LeafCfg<2>::SPT;
-    case 3: return LeafCfg<3>::SPT;
-    case 4: return LeafCfg<4>::SPT;
+#define X(dg, ...) case dg: return LeafCfg<dg>::SPT;
+        FA_LIST_LEAF_DEG(X, _)
+#undef X
     default: return 0;
     }
 }
@@ -459,10 +254,9 @@ template <class BE> bool dispatch_leaf(BE &be, const LeafParams &p)
     const long long n = (long long)p.c.batch * (p.c.Dpad / p.spt);
     const int g = (int)((n + 127) / 128);
     switch (p.c.deg) {
-    case 1: be.template run<KLeaf<1>>(g, 1, p); return true;
-    case 2: be.template run<KLeaf<2>>(g, 1, p); return true;
-    case 3: be.template run<KLeaf<3>>(g, 1, p); return true;
-    case 4: be.template run<KLeaf<4>>(g, 1, p); return true;
+#define X(dg, ...) case dg: be.template run<KLeaf<dg>>(g, 1, p); return true;
+        FA_LIST_LEAF_DEG(X, _)
+#undef X
     default: return false;
     }
 }
@@ -472,31 +266,13 @@ template <class BE> bool dispatch_pair_school(BE &be, const TreeLevel &L)
     const int pairs = L.n_in / 2;
     const int g = (pairs + 127) / 128;
     switch (L.d) {
-    case 1: be.template run<KPairSchool<1>>(g, 1, L); return true;
-    case 2: be.template run<KPairSchool<2>>(g, 1, L); return true;
-    case 3: be.template run<KPairSchool<3>>(g, 1, L); return true;
+#define X(dg, ...) case dg: be.template run<KPairSchool<dg>>(g, 1, L); return true;
+        FA_LIST_SCHOOL_DEG(X, _)
+#undef X
     default: return false;
     }
 }
 
-// the general form fuses pair products up to N = 2048 (NftPlan::fused_max_len); the symmetric form starts at degree
-// >= 6 (leaf kernel or coefficient program), so at N >= 16
-template <class BE, int N> bool run_pair_fft(BE &be, const TreeLevel &L)
-{
-    const int pairs = L.n_in / 2;
-    if (L.ne == 4) {
-        if constexpr (N <= 2048) {
-            constexpr int B = PairCfg<N, 4>::B;
-            be.template run<KPairFft<N, 4>>((pairs + B - 1) / B, 1, L);
-            return true;
-        }
-    } else if constexpr (N >= 16) {
-        constexpr int B = PairCfg<N, 2>::B;
-        be.template run<KPairFft<N, 2>>((pairs + B - 1) / B, 1, L);
-        return true;
-    }
-    return false;
-}
 // STAGES levels in one launch (symmetric form): T = 256 lanes (512 when the last stage is 4096 long)
 template <int N0, int STAGES> struct MultiCfg {
     static constexpr int R = 8;
@@ -549,17 +325,16 @@ template <int DEG, int STAGES> struct KLeafMulti {
 template <class BE> bool dispatch_leaf_multi(BE &be, const LeafMultiParams &Q, int stages)
 {
     const int deg = Q.lp.c.deg;
-#define X(dg, st) if (deg == dg && stages == st && 2 * dg * LeafCfg<dg>::SPT == 16) { be.template run<KLeafMulti<dg, st>>((Q.L.n_in + MultiCfg<16, st>::THREADS - 1) / MultiCfg<16, st>::THREADS, 1, Q); return true; }
-    X(1, 3) X(2, 3) X(4, 3) X(1, 2) X(2, 2) X(4, 2)
+#define X(dg, st, ...) if (deg == dg && stages == st && 2 * dg * LeafCfg<dg>::SPT == 16) { be.template run<KLeafMulti<dg, st>>((Q.L.n_in + MultiCfg<16, st>::THREADS - 1) / MultiCfg<16, st>::THREADS, 1, Q); return true; }
+    FA_LIST_LEAF_MULTI(X, _)
 #undef X
     return false;
 }
-// N: transform length of the first of the `stages` levels.  The leaf kernel fused into the first launch
-// (KLeafMulti) takes the levels from N = 16, so the launches that follow start at N = 128 and 1024
+// N: transform length of the first of the `stages` levels
 template <class BE> bool dispatch_multi(BE &be, const TreeLevel &L, int N, int stages)
 {
-#define X(n0, st) if (N == n0 && stages == st) { be.template run<KMulti<n0, st>>((L.n_in + 2 * MultiCfg<n0, st>::P0 - 1) / (2 * MultiCfg<n0, st>::P0), 1, L); return true; }
-    X(128, 3) X(1024, 3) X(128, 2) X(1024, 2)
+#define X(n0, st, ...) if (N == n0 && stages == st) { be.template run<KMulti<n0, st>>((L.n_in + 2 * MultiCfg<n0, st>::P0 - 1) / (2 * MultiCfg<n0, st>::P0), 1, L); return true; }
+    FA_LIST_MULTI(X, _)
 #undef X
     return false;
 }
@@ -580,33 +355,30 @@ template <class BE> void run_mid(BE &be, const BigLevel &G)
     else if (G.y_direct) be.template run<KMidSym<true>>(g, 1, G);
     else be.template run<KMidSym<false>>(g, 1, G);
 }
+// general form (L.ne == 4) or symmetric form, each over its own lengths
 template <class BE> bool dispatch_pair_fft(BE &be, const TreeLevel &L, int N)
 {
+    const int pairs = L.n_in / 2;
+#define X(n, NE, ...) case n: be.template run<KPairFft<n, NE>>((pairs + PairCfg<n, NE>::B - 1) / PairCfg<n, NE>::B, 1, L); return true;
+    if (L.ne == 4) {
+        switch (N) {
+            FA_LIST_PAIR_GEN(X, 4)
+        default: return false;
+        }
+    }
     switch (N) {
-    case 8: return run_pair_fft<BE, 8>(be, L);
-    case 16: return run_pair_fft<BE, 16>(be, L);
-    case 32: return run_pair_fft<BE, 32>(be, L);
-    case 64: return run_pair_fft<BE, 64>(be, L);
-    case 128: return run_pair_fft<BE, 128>(be, L);
-    case 256: return run_pair_fft<BE, 256>(be, L);
-    case 512: return run_pair_fft<BE, 512>(be, L);
-    case 1024: return run_pair_fft<BE, 1024>(be, L);
-    case 2048: return run_pair_fft<BE, 2048>(be, L);
-    case 4096: return run_pair_fft<BE, 4096>(be, L);
+        FA_LIST_PAIR_SYM(X, 2)
     default: return false;
     }
+#undef X
 }
-
-// N1 = 2 would be a product of length 2*N2 <= 4096, which is fused (kFusedMaxN)
-#define FA_FOR_EACH_N1(X) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
-#define FA_FOR_EACH_CHIRP_N1(X) X(2) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
 
 template <class BE> bool dispatch_col_fwd(BE &be, const BigLevel &G)
 {
     const int polys = G.L.ne * G.L.n_in;
     switch (G.N1) {
-#define X(n1) case n1: be.template run<KColFwd<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_N1(X)
+#define X(n1, ...) case n1: be.template run<KColFwd<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
+        FA_LIST_COL_N1(X, _)
 #undef X
     default: return false;
     }
@@ -615,19 +387,18 @@ template <class BE> bool dispatch_col_inv(BE &be, const BigLevel &G)
 {
     const int polys = G.L.ne * (G.L.n_in / 2);
     switch (G.N1) {
-#define X(n1) case n1: be.template run<KColInv<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_N1(X)
+#define X(n1, ...) case n1: be.template run<KColInv<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
+        FA_LIST_COL_N1(X, _)
 #undef X
     default: return false;
     }
 }
-#define FA_FOR_EACH_BRIDGE_N1(X) X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512)
 template <class BE> bool dispatch_col_bridge2(BE &be, const BigLevel &G)
 {
     const int polys = G.L.ne * (G.L.n_in / 2);
     switch (G.N1) {
-#define X(n1) case n1: be.template run<KColBridge2<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_BRIDGE_N1(X) X(1024) X(2048) X(4096)   // doubling transforms N1 points, not 2*N1
+#define X(n1, ...) case n1: be.template run<KColBridge2<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
+        FA_LIST_BRIDGE2_N1(X, _)
 #undef X
     default: return false;
     }
@@ -636,8 +407,8 @@ template <class BE> bool dispatch_chirp_col_fwd(BE &be, const ChirpParams &C)
 {
     const int jobs = C.batch * C.npoly + (C.v_mode == 2 ? 0 : 1);   // the filter job is skipped when its spectrum is cached
     switch (C.N1) {
-#define X(n1) case n1: if (C.dft_len > 0) be.template run<KChirpColFwd<n1, true>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); else be.template run<KChirpColFwd<n1>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); return true;
-        FA_FOR_EACH_CHIRP_N1(X)
+#define X(n1, ...) case n1: if (C.dft_len > 0) be.template run<KChirpColFwd<n1, true>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); else be.template run<KChirpColFwd<n1>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); return true;
+        FA_LIST_CHIRP_N1(X, _)
 #undef X
     default: return false;
     }
@@ -645,8 +416,8 @@ template <class BE> bool dispatch_chirp_col_fwd(BE &be, const ChirpParams &C)
 template <class BE> bool dispatch_chirp_col_inv(BE &be, const ChirpParams &C)
 {
     switch (C.N1) {
-#define X(n1) case n1: if (C.dft_len > 0) be.template run<KChirpColInv<n1, true>>(C.N2 / ChirpColCfg<n1>::BC, C.batch, C); else if (C.cstype == 10) be.template run<KChirpColInv<n1, false, true>>(C.N2 / ChirpColCfg<n1>::BC, C.batch, C); else be.template run<KChirpColInv<n1>>(C.N2 / ChirpColCfg<n1>::BC, C.batch, C); return true;
-        FA_FOR_EACH_CHIRP_N1(X)
+#define X(n1, ...) case n1: if (C.dft_len > 0) be.template run<KChirpColInv<n1, true>>(C.N2 / ChirpColCfg<n1>::BC, C.batch, C); else if (C.cstype == 10) be.template run<KChirpColInv<n1, false, true>>(C.N2 / ChirpColCfg<n1>::BC, C.batch, C); else be.template run<KChirpColInv<n1>>(C.N2 / ChirpColCfg<n1>::BC, C.batch, C); return true;
+        FA_LIST_CHIRP_N1(X, _)
 #undef X
     default: return false;
     }
@@ -654,12 +425,7 @@ template <class BE> bool dispatch_chirp_col_inv(BE &be, const ChirpParams &C)
 
 // ---- real-coefficient path (nft_real.h) -----------------------------------------------------------
 constexpr int kRealFusedMaxM = 2048;   // largest folded transform done by one workgroup
-template <int DEG> struct KRPairSchool {
-    using Params = TreeLevel;
-    static constexpr int THREADS = 128;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_rpair_school<DEG>(p); }
-};
+template <int DEG> FA_FUNCTOR(KRPairSchool, TreeLevel, 128, 0, body_rpair_school<DEG>);
 #ifndef FA_RPAIR_T
 #define FA_RPAIR_T 256   // lanes of a workgroup that holds several pairs (knob: 64 = one wave, barriers within the wave)
 #endif
@@ -737,34 +503,31 @@ template <class BE> bool dispatch_rpair_school(BE &be, const TreeLevel &L)
 {
     const int g = (L.n_in / 2 + 127) / 128;
     switch (L.d) {
-    case 1: be.template run<KRPairSchool<1>>(g, 1, L); return true;
-    case 2: be.template run<KRPairSchool<2>>(g, 1, L); return true;
-    default: return false;   // no d = 3: the leaf kernel starts a tree of degree-3 factors at d = 6
-    }
-}
-// the first FFT level of the real path has M >= 8; KRPair4 takes M = 32 ... 512
-template <class BE> bool dispatch_rpair(BE &be, const TreeLevel &L, int M)
-{
-    const int pairs = L.n_in / 2;
-    switch (M) {
-#define X(m) case m: be.template run<KRPair4<m>>((pairs + RPair4Cfg<m>::BP - 1) / RPair4Cfg<m>::BP, 1, L); return true;
-        X(32) X(64) X(128) X(256) X(512)
-#undef X
-#define X(m) case m: be.template run<KRPair<m>>((pairs + RPairCfg<m>::B - 1) / RPairCfg<m>::B, 1, L); return true;
-        X(8) X(16) X(1024) X(2048)
+#define X(dg, ...) case dg: be.template run<KRPairSchool<dg>>(g, 1, L); return true;
+        FA_LIST_RSCHOOL_DEG(X, _)
 #undef X
     default: return false;
     }
 }
-// a forward column step of the real path runs on the first split level, whose length is the first above the fused
-// limit (N1 = 4), and after a level without a bridge, which only the bridge limit kRBridgeMaxN1 causes (KRColInv<2048>,
-// then KRColFwd<4096>)
+template <class BE> bool dispatch_rpair(BE &be, const TreeLevel &L, int M)
+{
+    const int pairs = L.n_in / 2;
+    switch (M) {
+#define X(m, ...) case m: be.template run<KRPair4<m>>((pairs + RPair4Cfg<m>::BP - 1) / RPair4Cfg<m>::BP, 1, L); return true;
+        FA_LIST_RPAIR4_M(X, _)
+#undef X
+#define X(m, ...) case m: be.template run<KRPair<m>>((pairs + RPairCfg<m>::B - 1) / RPairCfg<m>::B, 1, L); return true;
+        FA_LIST_RPAIR_M(X, _)
+#undef X
+    default: return false;
+    }
+}
 template <class BE> bool dispatch_rcol_fwd(BE &be, const BigLevel &G)
 {
     const int polys = 4 * G.L.n_in;
     switch (G.N1) {
-#define X(n1) case n1: be.template run<KRColFwd<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        X(4) X(4096)
+#define X(n1, ...) case n1: be.template run<KRColFwd<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
+        FA_LIST_RCOL_FWD_N1(X, _)
 #undef X
     default: return false;
     }
@@ -773,8 +536,8 @@ template <class BE> bool dispatch_rcol_inv(BE &be, const BigLevel &G)
 {
     const int polys = 4 * (G.L.n_in / 2);
     switch (G.N1) {
-#define X(n1) case n1: be.template run<KRColInv<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
-        X(4) X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
+#define X(n1, ...) case n1: be.template run<KRColInv<n1>>(G.N2 / ColCfg<n1>::BC, polys, G); return true;
+        FA_LIST_RCOL_INV_N1(X, _)
 #undef X
     default: return false;
     }
@@ -783,34 +546,27 @@ template <class BE> bool dispatch_rbridge(BE &be, const BigLevel &G)
 {
     const int polys = 4 * (G.L.n_in / 2);
     switch (G.N1) {
-#define X(n1) case n1: be.template run<KRBridge<n1>>(G.N2 / RBridgeCfg<n1>::BC, polys, G); return true;
-        FA_FOR_EACH_BRIDGE_N1(X) X(1024)
+#define X(n1, ...) case n1: be.template run<KRBridge<n1>>(G.N2 / RBridgeCfg<n1>::BC, polys, G); return true;
+        FA_LIST_RBRIDGE_N1(X, _)
 #undef X
     default: return false;
     }
 }
-struct KRealCheck {
-    using Params = RealCheckParams;
-    static constexpr int THREADS = 256;
-    static constexpr size_t lds_bytes() { return 0; }
-    static FA_DEV void body(const Params &p) { body_real_check(p); }
-};
+FA_FUNCTOR(KRealCheck, RealCheckParams, 256, 0, body_real_check);
 template <int ORDER, bool BFIRST> struct KRCoeffsStrang {
     using Params = CoeffParams;
     static constexpr int THREADS = 64;
     static constexpr size_t lds_bytes() { return (size_t)64 * RStrangCfg<ORDER, BFIRST>::DEG * sizeof(double); }
     static FA_DEV void body(const Params &p) { body_rcoeffs_strang<ORDER, BFIRST>(p); }
 };
-// akns_disc 13 (2SPLIT6A), 14 (6B), 17 (8A), 18 (8B)
 template <class BE> bool dispatch_rcoeffs_strang(BE &be, const CoeffParams &p)
 {
     const long long n = (long long)p.batch * p.Dpad;
     const int g = (int)((n + 63) / 64);
     switch (p.disc) {
-    case 13: be.template run<KRCoeffsStrang<6, false>>(g, 1, p); return true;
-    case 14: be.template run<KRCoeffsStrang<6, true>>(g, 1, p); return true;
-    case 17: be.template run<KRCoeffsStrang<8, false>>(g, 1, p); return true;
-    case 18: be.template run<KRCoeffsStrang<8, true>>(g, 1, p); return true;
+#define X(disc, order, bfirst, ...) case disc: be.template run<KRCoeffsStrang<order, bfirst>>(g, 1, p); return true;
+        FA_LIST_RSTRANG(X, _)
+#undef X
     default: return false;
     }
 }
@@ -885,13 +641,12 @@ template <int K> struct KR3Bridge {
 };
 constexpr int kR3MaxK = 512;         // column length up to 1536
 constexpr int kR3BridgeMaxK = 256;   // bridges up to 768 -> 1536
-#define FA_FOR_EACH_R3_K(X) X(1) X(2) X(4) X(8) X(16) X(32) X(64) X(128) X(256)
 template <class BE> bool dispatch_r3col_fwd(BE &be, const BigLevel &G)
 {
     const int polys = 4 * G.L.n_in;
     switch (G.N1 / 3) {
-#define X(k) case k: be.template run<KR3ColFwd<k>>(G.N2 / R3ColCfg<k>::BC, polys, G); return true;
-        X(1)   // only the first split level (K = 1): a level without a bridge (K = 512) is the last
+#define X(k, ...) case k: be.template run<KR3ColFwd<k>>(G.N2 / R3ColCfg<k>::BC, polys, G); return true;
+        FA_LIST_R3_FWD_K(X, _)
 #undef X
     default: return false;
     }
@@ -900,8 +655,8 @@ template <class BE> bool dispatch_r3col_inv(BE &be, const BigLevel &G)
 {
     const int polys = 4 * (G.L.n_in / 2);
     switch (G.N1 / 3) {
-#define X(k) case k: be.template run<KR3ColInv<k>>(G.N2 / R3ColCfg<k>::BC, polys, G); return true;
-        FA_FOR_EACH_R3_K(X) X(512)
+#define X(k, ...) case k: be.template run<KR3ColInv<k>>(G.N2 / R3ColCfg<k>::BC, polys, G); return true;
+        FA_LIST_R3_INV_K(X, _)
 #undef X
     default: return false;
     }
@@ -910,8 +665,8 @@ template <class BE> bool dispatch_r3bridge(BE &be, const BigLevel &G)
 {
     const int polys = 4 * (G.L.n_in / 2);
     switch (G.N1 / 3) {
-#define X(k) case k: be.template run<KR3Bridge<k>>(G.N2 / R3Cfg<k>::BC, polys, G); return true;
-        FA_FOR_EACH_R3_K(X)
+#define X(k, ...) case k: be.template run<KR3Bridge<k>>(G.N2 / R3Cfg<k>::BC, polys, G); return true;
+        FA_LIST_R3_BRIDGE_K(X, _)
 #undef X
     default: return false;
     }
@@ -938,10 +693,9 @@ template <int ORDER, bool BFIRST> struct KRLeafStrang {
 inline int rleaf_strang_samples(int akns_disc)
 {
     switch (akns_disc) {
-    case 13: return rleaf_dl<6, false>() / RStrangCfg<6, false>::DEG;
-    case 14: return rleaf_dl<6, true>() / RStrangCfg<6, true>::DEG;
-    case 17: return rleaf_dl<8, false>() / RStrangCfg<8, false>::DEG;
-    case 18: return rleaf_dl<8, true>() / RStrangCfg<8, true>::DEG;
+#define X(disc, order, bfirst, ...) case disc: return rleaf_dl<order, bfirst>() / RStrangCfg<order, bfirst>::DEG;
+        FA_LIST_RSTRANG(X, _)
+#undef X
     default: return 0;
     }
 }
@@ -951,21 +705,18 @@ template <class BE> bool dispatch_rleaf_strang(BE &be, const LeafParams &lp)
     const long long n = (long long)p.batch * (p.Dpad / lp.spt);
     const int g = (int)((2 * n + 127) / 128);
     switch (p.disc) {
-    case 13: be.template run<KRLeafStrang<6, false>>(g, 1, lp); return true;
-    case 14: be.template run<KRLeafStrang<6, true>>(g, 1, lp); return true;
-    case 17: be.template run<KRLeafStrang<8, false>>(g, 1, lp); return true;
-    case 18: be.template run<KRLeafStrang<8, true>>(g, 1, lp); return true;
+#define X(disc, order, bfirst, ...) case disc: be.template run<KRLeafStrang<order, bfirst>>(g, 1, lp); return true;
+        FA_LIST_RSTRANG(X, _)
+#undef X
     default: return false;
     }
 }
 
-// fam: 0 CF family, 1 ES4, 2 TES4; realk: the CF family's real-ks variant
+// fam: 0 CF family, 1 ES4, 2 TES4; realk: the CF family's real-ks variant (NftSlowPlan sets it for that family only)
 template <class BE> bool dispatch_slow_scatter(BE &be, int g, const SlowParams &P, int fam, bool realk)
 {
-    if (fam == 0 && realk) be.template run<KSlowScatter<0, true>>(g, 1, P);
-    else if (fam == 0) be.template run<KSlowScatter<0, false>>(g, 1, P);
-    else if (fam == 1) be.template run<KSlowScatter<1, false>>(g, 1, P);
-    else if (fam == 2) be.template run<KSlowScatter<2, false>>(g, 1, P);
-    else return false;
-    return true;
+#define X(f, rk, ...) if (fam == f && realk == rk) { be.template run<KSlowScatter<f, rk>>(g, 1, P); return true; }
+    FA_LIST_SLOW_SCATTER(X, _)
+#undef X
+    return false;
 }

@@ -591,12 +591,57 @@ public:
         return NFT_SUCCESS;
     }
 
+    // what one level of the tree hands on to the next
+    struct TreeWalk {
+        bool y_from_bridge = false;   // the previous level bridged: Y holds this level's forward column step
+        bool in_pending = false;      // the previous level was split: its rescale is still pending
+        int zcur = 0, mcur = 0;       // which of Z / Z2 and of the max2 pair the level reads
+    };
+    // the level of n matrices of degree d, all signals; the branch that runs it adds its twiddle tables
+    TreeLevel tree_level(const TreeWalk &w, size_t n, size_t d, int ne_level, int dbg) const
+    {
+        TreeLevel L;
+        L.body_in = body[cur]; L.tail_in = tail[cur]; L.scale_in = scale[cur];
+        L.body_out = body[cur ^ 1]; L.tail_out = tail[cur ^ 1]; L.scale_out = scale[cur ^ 1];
+        L.max2_out = max2[w.mcur ^ 1];
+        L.max2_in = max2[w.mcur];
+        L.in_pending = w.in_pending ? 1 : 0;
+        L.wexp_in = wexp[cur];
+        L.wexp_out = wexp[cur ^ 1];
+        L.plane = plane;
+        L.n_in = (int)n;
+        L.d = (int)d;
+        L.pairs_per_signal = (int)(n / 2 / batch);
+        L.ne = ne_level;
+        L.kappa = kappa_run;
+        L.dbg = dbg;
+        return L;
+    }
+    // the launches of a split level G: the forward column step unless the previous level bridged into Y (or the row
+    // kernel does it on the fly, y_direct), the rows, then the bridge straight into the next level's column step when
+    // that level is split too (next_split), else the inverse column step
+    typedef bool (*ColStep)(BE &, const BigLevel &);
+    bool run_split_level(TreeWalk &w, const BigLevel &G, ColStep fwd, ColStep bridge, ColStep inv, bool next_split)
+    {
+        bool ok = true;
+        if (!w.y_from_bridge && !G.y_direct) ok = fwd(be, G);
+        if (ok) run_mid(be, G);
+        if (ok) ok = next_split ? bridge(be, G) : inv(be, G);
+        w.zcur ^= 1;
+        w.y_from_bridge = ok && next_split;
+        // the consumer of the next level finalizes this one; the last level needs a kernel
+        const bool last_level = G.L.pairs_per_signal <= 1;
+        if (ok && last_level) defer_final(G.L, (size_t)G.L.n_in / 2);
+        w.in_pending = !last_level;
+        w.mcur ^= 1;
+        return ok;
+    }
+
     // the same tree on real coefficients (nft_real.h): folded transforms of length M = nft_real_len(d)
     int run_tree_real()
     {
         size_t n = start_n, d = start_d;
-        bool y_from_bridge = false, in_pending = false;
-        int zcur = 0, mcur = 0;
+        TreeWalk w;
         // degrees 3*2^a: the split levels take columns of 3*K rows of kRowGen points -- transform length M = d exactly
         // (nft_real.h) -- when the last level's column length is instantiated
         bool r3 = false;
@@ -607,21 +652,7 @@ public:
             r3 = (odd == 3) && dtop % (size_t)kRowGen == 0 && dtop / (size_t)kRowGen <= (size_t)3 * kR3MaxK;
         }
         while (n / batch > 1) {
-            TreeLevel L;
-            L.body_in = body[cur]; L.tail_in = tail[cur]; L.scale_in = scale[cur];
-            L.body_out = body[cur ^ 1]; L.tail_out = tail[cur ^ 1]; L.scale_out = scale[cur ^ 1];
-            L.max2_out = max2[mcur ^ 1];
-            L.max2_in = max2[mcur];
-            L.in_pending = in_pending ? 1 : 0;
-            L.wexp_in = wexp[cur];
-            L.wexp_out = wexp[cur ^ 1];
-            L.plane = plane;
-            L.n_in = (int)n;
-            L.d = (int)d;
-            L.pairs_per_signal = (int)(n / 2 / batch);
-            L.ne = 4;
-            L.kappa = kappa_run;
-            L.dbg = 0;
+            TreeLevel L = tree_level(w, n, d, 4, 0);
             const size_t M = nft_real_len(d);
             bool ok;
             if (d <= (size_t)kSchoolMaxDeg) {
@@ -631,7 +662,7 @@ public:
                 std::memset(&G, 0, sizeof(G));
                 G.L = L;
                 G.Y = Y;
-                G.Z = zcur ? Z2 : Z;
+                G.Z = w.zcur ? Z2 : Z;
                 G.N2 = kRowGen;
                 G.N1 = (int)(d / (size_t)kRowGen);   // 3*K
                 const size_t K = (size_t)G.N1 / 3;
@@ -645,18 +676,10 @@ public:
                 G.tw3x2 = tw3_table((size_t)2 * G.N1);
                 G.twq = tw3_table((size_t)4 * G.N1);
                 G.twq2 = ((size_t)8 * G.N1 <= ((size_t)3 << kTw3MaxLog)) ? tw3_table((size_t)8 * G.N1) : nullptr;
-                G.y_unscaled = y_from_bridge ? 1 : 0;
-                ok = true;
-                if (!y_from_bridge) ok = dispatch_r3col_fwd(be, G);
-                if (ok) run_mid(be, G);
+                G.y_unscaled = w.y_from_bridge ? 1 : 0;
                 const bool next_split = (n / 2 / batch > 1) && K <= (size_t)kR3BridgeMaxK;
-                if (ok) ok = next_split ? dispatch_r3bridge(be, G) : dispatch_r3col_inv(be, G);
-                zcur ^= 1;
-                y_from_bridge = ok && next_split;
-                const bool last_level = (n / 2 / batch <= 1);
-                if (ok && last_level) defer_final(L, n / 2);
-                in_pending = !last_level;
-                mcur ^= 1;
+                ok = run_split_level(w, G, dispatch_r3col_fwd<BE>, dispatch_r3bridge<BE>, dispatch_r3col_inv<BE>,
+                                     next_split);
             } else if (M <= (size_t)kRealFusedMaxM) {
                 L.tw = tw_table(M);
                 L.twx = tw_table(4 * M);
@@ -666,7 +689,7 @@ public:
                 std::memset(&G, 0, sizeof(G));
                 G.L = L;
                 G.Y = Y;
-                G.Z = zcur ? Z2 : Z;
+                G.Z = w.zcur ? Z2 : Z;
                 G.N2 = row_len_gen(M);
                 G.N1 = (int)(M / (size_t)G.N2);
                 if (4 * (size_t)G.N1 > (size_t)kMaxTwTable) return NFT_EC_NOT_YET_IMPLEMENTED;
@@ -677,19 +700,11 @@ public:
                 G.tw1x2 = tw_table((size_t)2 * G.N1);
                 G.twq = tw_table((size_t)4 * G.N1);
                 G.twq2 = (8 * (size_t)G.N1 <= (size_t)kMaxTwTable) ? tw_table((size_t)8 * G.N1) : nullptr;
-                G.y_unscaled = y_from_bridge ? 1 : 0;
-                ok = true;
-                if (!y_from_bridge) ok = dispatch_rcol_fwd(be, G);
-                if (ok) run_mid(be, G);
+                G.y_unscaled = w.y_from_bridge ? 1 : 0;
                 const bool next_split = (n / 2 / batch > 1) && G.N1 <= kRBridgeMaxN1
                                         && row_len_gen(2 * M) == G.N2;
-                if (ok) ok = next_split ? dispatch_rbridge(be, G) : dispatch_rcol_inv(be, G);
-                zcur ^= 1;
-                y_from_bridge = ok && next_split;
-                const bool last_level = (n / 2 / batch <= 1);
-                if (ok && last_level) defer_final(L, n / 2);
-                in_pending = !last_level;
-                mcur ^= 1;
+                ok = run_split_level(w, G, dispatch_rcol_fwd<BE>, dispatch_rbridge<BE>, dispatch_rcol_inv<BE>,
+                                     next_split);
             }
             if (!ok) return NFT_EC_NOT_YET_IMPLEMENTED;
             cur ^= 1;
@@ -707,27 +722,10 @@ public:
         if (real_run) return run_tree_real();
         size_t n = start_n;     // matrices at the current level, all signals
         size_t d = start_d;
-        bool y_from_bridge = false;
-        int zcur = 0;
-        bool in_pending = false;   // previous level was split: its rescale is still pending
-        int mcur = 0;
+        TreeWalk w;
         int split_idx = 0;
         while (n / batch > 1) {
-            TreeLevel L;
-            L.body_in = body[cur]; L.tail_in = tail[cur]; L.scale_in = scale[cur];
-            L.body_out = body[cur ^ 1]; L.tail_out = tail[cur ^ 1]; L.scale_out = scale[cur ^ 1];
-            L.max2_out = max2[mcur ^ 1];
-            L.max2_in = max2[mcur];
-            L.in_pending = in_pending ? 1 : 0;
-            L.wexp_in = wexp[cur];
-            L.wexp_out = wexp[cur ^ 1];
-            L.plane = plane;
-            L.n_in = (int)n;
-            L.d = (int)d;
-            L.pairs_per_signal = (int)(n / 2 / batch);
-            L.ne = ne;
-            L.kappa = kappa_run;
-            L.dbg = dbg_flags;
+            TreeLevel L = tree_level(w, n, d, ne, dbg_flags);
             const size_t N = nft_product_len(d);
             L.tw = (N <= (size_t)kMaxTwTable) ? tw_table(N) : nullptr;
             bool ok;
@@ -765,9 +763,9 @@ public:
                 BigLevel G;
                 G.L = L;
                 G.Y = Y;
-                G.Z = zcur ? Z2 : Z;
-                G.Zprev = zcur ? Z : Z2;
-                G.y_split = y_from_bridge ? 1 : 0;   // every bridge doubles: Y holds the odd rows only
+                G.Z = w.zcur ? Z2 : Z;
+                G.Zprev = w.zcur ? Z : Z2;
+                G.y_split = w.y_from_bridge ? 1 : 0;   // every bridge doubles: Y holds the odd rows only
                 G.N2 = (ne == 4) ? row_len_gen(N) : kRowTree;
                 G.N1 = (int)(N / (size_t)G.N2);
                 G.btw = big_tw(N);
@@ -775,28 +773,18 @@ public:
                 G.tw2 = tw_table((size_t)G.N2);
                 G.tw1x2 = tw_table((size_t)2 * G.N1);
                 G.btw2 = big_tw(2 * N);
-                G.y_unscaled = y_from_bridge ? 1 : 0;
+                G.y_unscaled = w.y_from_bridge ? 1 : 0;
                 // first split level of the symmetric form: a length-4 column transform of two non-zero rows is done
                 // by the row kernel on the fly (saves the column launch and its 32 + 64 MB)
-                G.y_direct = (!y_from_bridge && G.N1 == 4 && N == 2 * d && dbg_flags == 0 && ne == 2) ? 1 : 0;
+                G.y_direct = (!w.y_from_bridge && G.N1 == 4 && N == 2 * d && dbg_flags == 0 && ne == 2) ? 1 : 0;
                 G.stagger = (n / 2 * (size_t)G.N1 == 512) ? tune_stagger : 0;   // exactly one round of workgroups
                 G.stamps = (dbg_stamps && split_idx == stamp_level) ? dbg_stamps : nullptr;
                 split_idx++;
-                ok = true;
-                if (!y_from_bridge && !G.y_direct) ok = dispatch_col_fwd(be, G);
-                if (ok) run_mid(be, G);
-                // bridge straight into the next level's column step when that level is split too, with spectral
-                // doubling (body_col_bridge2; N = 2d and N > 2d alike)
+                // the bridge doubles the spectrum (body_col_bridge2; N = 2d and N > 2d alike)
                 const bool next_split = (n / 2 / batch > 1) && G.N1 <= 4096 && nft_product_len(2 * d) == 2 * N
                                         && ((ne == 4) ? row_len_gen(2 * N) : kRowTree) == G.N2;
-                if (ok) ok = next_split ? dispatch_col_bridge2(be, G) : dispatch_col_inv(be, G);
-                zcur ^= 1;
-                y_from_bridge = ok && next_split;
-                // the consumer of the next level finalizes this one; the last level needs a kernel
-                const bool last_level = (n / 2 / batch <= 1);
-                if (ok && last_level) defer_final(L, n / 2);
-                in_pending = !last_level;
-                mcur ^= 1;
+                ok = run_split_level(w, G, dispatch_col_fwd<BE>, dispatch_col_bridge2<BE>, dispatch_col_inv<BE>,
+                                     next_split);
             }
             if (!ok) return NFT_EC_NOT_YET_IMPLEMENTED;
             cur ^= 1;

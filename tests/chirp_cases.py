@@ -115,14 +115,6 @@ CASES = [
     _c("kdv_2A_real_N8192", "kdv", 8192, disc="2SPLIT2A", D=1000, M=20000001, real=1, K=4),
 ]
 
-# Every chirp kernel instantiation (FA_INST lines of hip_kernels_chirpa.hip / hip_kernels_chirpb.hip)
-N1S = [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
-CHIRP_INSTANTIATIONS = (
-    ["KChirpRows"]
-    + ["KChirpColFwd<%d,%s>" % (n, d) for d in ("false", "true") for n in N1S]
-    + ["KChirpColInv<%d,%s,%s>" % (n, d, k) for d, k in (("false", "false"), ("true", "false"), ("false", "true"))
-       for n in N1S])
-
 EXCLUDED = {}
 
 # degree per step of the schemes used above (nft_akns_degree)

@@ -325,4 +325,19 @@ int emu_chirp_schedule(int entry, size_t n, size_t M, int disc, size_t batch, in
     return rc;
 }
 
+// Every kernel instantiation of the library (the units of fnft_amd/csrc/nft_kernel_list.h, which the hip_kernels_*.hip
+// files instantiate and the dispatch switches read), named as the schedules above name them, '\n'-separated, into
+// out[cap].  Returns the number of names, or -1 if out is too small.
+int emu_kernel_list(char *out, size_t cap)
+{
+    std::string s;
+    int n = 0;
+#define FA_EMU_NAME(...) s += emu_kernel_name<__VA_ARGS__>() + "\n"; n++;
+    FA_ALL_UNITS(FA_EMU_NAME)
+#undef FA_EMU_NAME
+    if (s.size() + 1 > cap) return -1;
+    std::memcpy(out, s.c_str(), s.size() + 1);
+    return n;
+}
+
 }  // extern "C"

@@ -2,7 +2,6 @@
 schedule-only mode: kernel names from the product's own host code, nothing executed), coverage of the chirp
 instantiations, self-tests of the extended-precision reference tests/chirp_ref.py, and the metric's sensitivity."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -10,9 +9,8 @@ import pytest
 
 import chirp_cases as CC
 import chirp_ref as R
-from test_emu_kernels import emu  # noqa: F401  (module fixture: builds and loads tests/emu/libfnft_emu.so)
+from test_emu_kernels import emu, kernel_list  # noqa: F401  (module fixture: builds and loads tests/emu/libfnft_emu.so)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLD = np.clongdouble
 
 
@@ -43,18 +41,18 @@ def test_case_schedule(schedules, case):
     assert not unwanted, (unwanted, names)
 
 
-def test_chirp_instantiation_list():
-    """CHIRP_INSTANTIATIONS is exactly the FA_INST(KChirp...) lines of the chirp kernel units."""
-    found = []
-    for f in ("hip_kernels_chirpa.hip", "hip_kernels_chirpb.hip"):
-        with open(os.path.join(ROOT, "fnft_amd", "csrc", f)) as fh:
-            found += [m.replace(" ", "") for m in re.findall(r"^FA_INST\((KChirp[^)]*)\)", fh.read(), re.M)]
-    assert len(CC.CHIRP_INSTANTIATIONS) == 66 == len(set(CC.CHIRP_INSTANTIATIONS))
-    assert sorted(found) == sorted(CC.CHIRP_INSTANTIATIONS), (sorted(set(found) ^ set(CC.CHIRP_INSTANTIATIONS)))
+@pytest.fixture(scope="module")
+def chirp_instantiations(emu):  # noqa: F811
+    """The chirp kernels of the library's instantiation list: what the units compile and the dispatch switches launch."""
+    return [n for n in kernel_list(emu) if n.startswith("KChirp")]
 
 
-def test_chirp_instantiation_coverage(schedules):
-    inst = set(CC.CHIRP_INSTANTIATIONS)
+def test_chirp_instantiation_list(chirp_instantiations):
+    assert len(chirp_instantiations) == 66 == len(set(chirp_instantiations))
+
+
+def test_chirp_instantiation_coverage(schedules, chirp_instantiations):
+    inst = set(chirp_instantiations)
     assert set(CC.EXCLUDED) <= inst, sorted(set(CC.EXCLUDED) - inst)
     used = set().union(*schedules.values()) & inst
     # every instantiation is launched by some case, or excluded with a reason; an exclusion that a case reaches is stale

@@ -32,7 +32,7 @@ def _P(a):
 def emu():
     deps = [os.path.join(EMU_DIR, f) for f in ("emu_main.cpp", "emu_backend.h")]
     deps += [os.path.join(CSRC, f) for f in ("dev_compat.h", "fft_dev.h", "nft_kernels.h", "nft_real.h", "nft_dispatch.h",
-                                             "nft_plan.h", "nft_api.h", "nft_discspec.h")]
+                                             "nft_kernel_list.h", "nft_plan.h", "nft_api.h", "nft_discspec.h")]
     if not os.path.exists(EMU_LIB) or max(map(os.path.getmtime, deps)) > os.path.getmtime(EMU_LIB):
         subprocess.check_call(["g++", "-std=c++20", "-O2", "-fPIC", "-shared", "-pthread",
                                "-Wno-unknown-pragmas", "-o", EMU_LIB,
@@ -50,6 +50,23 @@ def emu():
     L.emu_nsev_discspec.argtypes = [C.c_size_t, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
                                     C.c_int, C.POINTER(C.c_size_t), vp, vp]
     return L
+
+
+def kernel_list(emu):
+    """Every kernel instantiation of the library (the units of fnft_amd/csrc/nft_kernel_list.h), named as the emulator's
+    schedules name them, spaces removed."""
+    emu.emu_kernel_list.argtypes = [C.c_char_p, C.c_size_t]
+    buf = C.create_string_buffer(1 << 16)
+    n = emu.emu_kernel_list(buf, len(buf))
+    names = [k.replace(" ", "") for k in buf.value.decode().split("\n") if k]
+    assert n == len(names), (n, len(names))
+    return names
+
+
+def test_kernel_list_count(emu):
+    """The 23 units instantiate 258 distinct kernels."""
+    names = kernel_list(emu)
+    assert len(names) == 258 == len(set(names))
 
 
 @pytest.mark.parametrize("kind,N", [("pair", n) for n in (8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096)]

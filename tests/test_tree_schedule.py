@@ -9,7 +9,7 @@ import pytest
 import signals as S
 import tree_cases as TC
 import tree_ref as R
-from test_emu_kernels import emu  # noqa: F401  (module fixture: builds and loads tests/emu/libfnft_emu.so)
+from test_emu_kernels import emu, kernel_list  # noqa: F401  (module fixture: builds and loads tests/emu/libfnft_emu.so)
 
 
 def schedule(emu, case):
@@ -32,16 +32,25 @@ def test_case_schedule(schedules, case):
     assert not missing, (missing, names)
 
 
-def test_tree_instantiation_coverage(schedules):
-    inst = set(TC.TREE_INSTANTIATIONS)
-    assert len(inst) == len(TC.TREE_INSTANTIATIONS)
+@pytest.fixture(scope="module")
+def tree_instantiations(emu):  # noqa: F811
+    """The tree kernels of the library's instantiation list: what the units compile and the dispatch switches launch."""
+    return [n for n in kernel_list(emu) if n.startswith(TC.TREE_PREFIXES)]
+
+
+def test_tree_instantiation_list(tree_instantiations):
+    assert len(tree_instantiations) == 131 == len(set(tree_instantiations))
+
+
+def test_tree_instantiation_coverage(schedules, tree_instantiations):
+    inst = set(tree_instantiations)
+    assert len(inst) == len(tree_instantiations)
     assert set(TC.EXCLUDED) <= inst, sorted(set(TC.EXCLUDED) - inst)
     used = set().union(*schedules.values()) & inst
     # every instantiation is launched by some case, or excluded with a reason; an exclusion that a case reaches is stale
     assert used == inst - set(TC.EXCLUDED), (sorted(inst - set(TC.EXCLUDED) - used), sorted(used & set(TC.EXCLUDED)))
-    # every tree kernel a case launches is in the list (a new instantiation has to be added to it)
-    tree_like = ("KPair", "KMulti", "KLeaf", "KCol", "KMid", "KRPair", "KRCol", "KRBridge", "KR3", "KRLeaf")
-    extra = {n for s in schedules.values() for n in s if n.startswith(tree_like)} - inst
+    # every tree kernel a case launches is in the list
+    extra = {n for s in schedules.values() for n in s if n.startswith(TC.TREE_PREFIXES)} - inst
     assert not extra, sorted(extra)
 
 

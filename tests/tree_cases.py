@@ -121,28 +121,9 @@ CASES = [
 ]
 
 
-# Every instantiation of a product-tree kernel in the dispatch switches of nft_dispatch.h (dispatch_leaf, _pair_school,
-# _pair_fft, _multi, _leaf_multi, run_mid, _col_fwd, _col_inv, _col_bridge2, _rpair_school, _rpair,
-# _rcol_fwd, _rcol_inv, _rbridge, _r3col_fwd, _r3col_inv, _r3bridge, _rleaf_strang).
-def _l(fmt, xs):
-    return [fmt % x for x in xs]
-
-
-N1 = [4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
-N1BR = [4, 8, 16, 32, 64, 128, 256, 512]
-K3 = [1, 2, 4, 8, 16, 32, 64, 128, 256]
-TREE_INSTANTIATIONS = (
-    _l("KLeaf<%d>", [1, 2, 3, 4]) + _l("KPairSchool<%d>", [1, 2, 3])
-    + _l("KPairFft<%d,4>", P2) + _l("KPairFft<%d,2>", P2[1:] + [4096])
-    + _l("KMulti<%d,3>", [128, 1024]) + _l("KMulti<%d,2>", [128, 1024])
-    + ["KLeafMulti<%d,%d>" % (d, s) for s in (3, 2) for d in (1, 2, 4)]
-    + ["KMidSym<true>", "KMidSym<false>", "KMidGen<1024>", "KMidGen<2048>"]
-    + _l("KColFwd<%d>", N1) + _l("KColInv<%d>", N1) + _l("KColBridge2<%d>", N1BR + [1024, 2048, 4096])
-    + _l("KRPairSchool<%d>", [1, 2]) + _l("KRPair<%d>", [8, 16, 1024, 2048])
-    + _l("KRPair4<%d>", [32, 64, 128, 256, 512])
-    + _l("KRColFwd<%d>", [4, 4096]) + _l("KRColInv<%d>", N1[:-1]) + _l("KRBridge<%d>", N1BR + [1024])
-    + _l("KR3ColFwd<%d>", [1]) + _l("KR3ColInv<%d>", K3 + [512]) + _l("KR3Bridge<%d>", K3)
-    + ["KRLeafStrang<%d,%s>" % (o, b) for o in (6, 8) for b in ("false", "true")])
+# Kernels of the product tree: the names of the library's instantiation list (emu_kernel_list) that begin with one of
+# these are the set the cases have to cover (tests/test_tree_schedule.py)
+TREE_PREFIXES = ("KPair", "KMulti", "KLeaf", "KCol", "KMid", "KRPair", "KRCol", "KRBridge", "KR3", "KRLeaf")
 
 EXCLUDED = {}
 _BIG = "reachable, but only by a tree of transform length 2^24 (1 GB of coefficients per side plus the reference " \
