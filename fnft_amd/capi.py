@@ -211,6 +211,8 @@ def load(path=None):
     L.fnft__misc_resample.argtypes = [sz, dbl, vp, dbl, vp]
     L.fnft__poly_roots_fasteigen.restype = i32
     L.fnft__poly_roots_fasteigen.argtypes = [sz, vp, vp]
+    L.fnft_amd__aberthb_roots.restype = i32
+    L.fnft_amd__aberthb_roots.argtypes = [sz, sz, vp, vp, vp, vp, vp, vp, vp]
     L.fnft__nse_scatter_bound_states.restype = i32
     L.fnft__nse_scatter_bound_states.argtypes = [sz, vp, vp, vp, sz, vp, vp, vp, vp, C.c_int, sz]
     L.fnft__poly_fmult_numel.restype = sz
@@ -568,6 +570,19 @@ def poly_roots_fasteigen(p):
     roots = np.zeros(max(p.size - 1, 1), np.complex128)
     rc = L.fnft__poly_roots_fasteigen(p.size - 1, _ptr(p), _ptr(roots))
     return int(rc), roots[: p.size - 1]
+
+
+def aberthb_roots(p):
+    """fnft_amd__aberthb_roots, a test seam: the batched root finder of DiscSpecSearchPlan alone.  p[batch, n + 1], highest
+    power first -> (rc, roots[batch, n], mdeg[batch], status[batch], warnings[batch], sweeps[batch], segments S)."""
+    L = load()
+    p = np.ascontiguousarray(p, np.complex128)
+    B, n = p.shape[0], p.shape[1] - 1
+    z = np.zeros((B, n), np.complex128)
+    mdeg, st, wn, sw = (np.zeros(B, np.int32) for _ in range(4))
+    sizes = np.zeros(1, np.uint64)
+    rc = L.fnft_amd__aberthb_roots(n, B, _ptr(p), _ptr(z), _ptr(mdeg), _ptr(st), _ptr(wn), _ptr(sw), _ptr(sizes))
+    return int(rc), z, mdeg, st, wn, sw, int(sizes[0])
 
 
 def nse_scatter_bound_states(q, T, lam, skip_b=False, discretization="BO"):

@@ -1479,6 +1479,57 @@ FNFT_INT fnft__poly_roots_fasteigen(const FNFT_UINT deg, FNFT_COMPLEX const *con
     return FNFT_SUCCESS;
 }
 
+// TEST SEAM ("Test seams"; not declared in include/fnft_amd.h): the batched root finder of the guess-free
+// discrete spectrum alone, NftDiscSpecSearch::roots, on caller-supplied polynomials -- what emu_aberthb_roots of
+// tests/emu/emu_discspec_search.cpp is over the emulator.  Every array in host memory.  coef: batch polynomials of
+// degree n, n + 1 coefficients each, highest power first; each becomes entry 11 of a 4*(n + 1) block, as roots(tm)
+// expects.  z: batch*n roots; per signal: mdeg, the degree the iteration ran on (without zero end coefficients), the
+// status word (bit 3: not converged), the warning word (bit 1: sweep limit) and the sweeps of its AbState; sizes (may
+// be NULL): {segments of the plan}
+FNFT_INT fnft_amd__aberthb_roots(FNFT_UINT n, FNFT_UINT batch, FNFT_COMPLEX const *coef, FNFT_COMPLEX *z, int *mdeg,
+                                 int *status, int *warn, int *sweeps, FNFT_UINT *sizes)
+{
+    if (n < 2 || batch == 0 || !coef || !z || !mdeg || !status || !warn || !sweeps) return FNFT_EC_INVALID_ARGUMENT;
+    const int dev = current_device();
+    if (dev < 0) return FNFT_EC_OTHER;
+    std::lock_guard<std::mutex> host_lk(host_call_mutex());
+    HipBackend be;
+    NftDsOpts o;
+    o.bsfilt = 2; o.bsloc = 0; o.niter = 0; o.Dsub = 0; o.dstype = 0; o.nse_disc = 4; o.richardson = 0;   // 2SPLIT2A: n = D
+    NftDiscSpecSearch<HipBackend> ds(be, n, 1, batch, o);
+    int rc = ds.init();
+    if (rc == NFT_SUCCESS && be.failed) rc = NFT_EC_NOMEM;
+    DevArena<HipBackend> tmp(be);
+    cplx *tm = nullptr;
+    const size_t stride = 4 * (n + 1);
+    if (rc == NFT_SUCCESS && !tmp.get(tm, batch * stride)) rc = NFT_EC_NOMEM;
+    if (rc == NFT_SUCCESS) {
+        std::vector<cplx> h(batch * stride, cmake(0.0, 0.0));
+        for (size_t b = 0; b < batch; b++) std::memcpy(h.data() + b * stride, coef + b * (n + 1), (n + 1) * sizeof(cplx));
+        be.h2d(tm, h.data(), h.size() * sizeof(cplx));
+        be.memset0(ds.sstatus, batch * sizeof(int));
+        be.memset0(ds.warn, batch * sizeof(int));
+        ds.roots(tm);
+        std::vector<AbState> st(batch);
+        std::vector<cplx> zb[2] = {std::vector<cplx>(batch * n), std::vector<cplx>(batch * n)};
+        be.d2h(st.data(), ds.A.state, batch * sizeof(AbState));
+        be.d2h(zb[0].data(), ds.A.zbuf[0], batch * n * sizeof(cplx));
+        be.d2h(zb[1].data(), ds.A.zbuf[1], batch * n * sizeof(cplx));
+        be.d2h(status, ds.sstatus, batch * sizeof(int));
+        be.d2h(warn, ds.warn, batch * sizeof(int));
+        rc = be.sync();
+        for (size_t b = 0; b < batch && rc == NFT_SUCCESS; b++) {
+            std::memcpy(z + b * n, zb[st[b].zin & 1].data() + b * n, n * sizeof(cplx));
+            mdeg[b] = st[b].m;
+            sweeps[b] = st[b].sweeps;
+        }
+        if (sizes) sizes[0] = (FNFT_UINT)ds.S;
+    }
+    (void)be.sync();   // the arenas hand their blocks back: nothing enqueued may still be using them
+    if (be.failed) return FNFT_EC_OTHER;
+    return rc;
+}
+
 // include/private/fnft__nse_scatter.h:76-80 (src/private/fnft__nse_scatter_bound_states.c:29-667) for the
 // Boffetta-Osborne scheme (the one fnft_nsev uses for Newton refinement and norming constants of every
 // 2SPLIT discretization): a, a' and b = phi/psi at K points lambda; q holds the D samples, r is not read

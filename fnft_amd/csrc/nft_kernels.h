@@ -3898,8 +3898,8 @@ template <int TILE> FA_DEV void aberth_newton_core(const AberthParams &P, long l
             const cplx cb = (kk <= n) ? P.coef[kk] : cmake(0.0, 0.0);
             tile[2 * t] = ca;
             tile[2 * t + 1] = cb;
-            tabs[2 * t] = sqrt(cnorm2(ca));
-            tabs[2 * t + 1] = sqrt(cnorm2(cb));
+            tabs[2 * t] = hypot(ca.x, ca.y);       // not sqrt(cnorm2): the square of a coefficient above 1.3e154 overflows,
+            tabs[2 * t + 1] = hypot(cb.x, cb.y);   // the error scale becomes inf and every estimate counts as converged
         }
         FA_SYNC();
         const int off = inside ? 0 : 1;
@@ -4071,7 +4071,9 @@ FA_DEV void aberth_apply_core(const AberthParams &P, long long bx)
         // an ill-conditioned polynomial keep receiving corrections of the size of the noise and never "converge"
         const double noise = P.polish ? 0.0 : 2.220446049250313e-16 * (2.0 * sqrt((double)n) + 2.0) * escale;
         cplx w;
-        if (cnorm2(p) <= noise * noise) {
+        // compared without squares: |p|^2 underflows below 1.5e-154 (a polynomial whose terms are all that small at its
+        // roots, e.g. coefficients 2^-k), and the estimate would freeze wherever it stands
+        if (hypot(p.x, p.y) <= noise) {
             w = cmake(0.0, 0.0);
         } else if (inside) {
             w = c_div(p, dp);

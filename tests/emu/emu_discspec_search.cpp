@@ -49,9 +49,11 @@ int emu_discspec_search(size_t D, size_t K, size_t batch, int nse_disc, int bslo
 }
 
 // the root finder alone on caller-supplied polynomials: entry 11 of signal b (n + 1 coefficients, highest power first)
-// at tm + b*4*(n + 1).  z: batch*n roots; mdeg: the degree each iteration ran on (without zero end coefficients);
-// sizes (may be NULL): {sweeps of signal 0, segments of the plan}
-int emu_aberthb_roots(size_t n, size_t batch, const cplx *tm, cplx *z, int *mdeg, int *status, size_t *sizes)
+// at tm + b*4*(n + 1).  z: batch*n roots; per signal, as fnft_amd__aberthb_roots of hip_backend.hip reports them: mdeg,
+// the degree the iteration ran on (without zero end coefficients), the status word (bit 3: not converged), the warning
+// word (bit 1: sweep limit) and the sweeps of its AbState; sizes (may be NULL): {segments of the plan}
+int emu_aberthb_roots(size_t n, size_t batch, const cplx *tm, cplx *z, int *mdeg, int *status, int *warn, int *sweeps,
+                      size_t *sizes)
 {
     EmuBackend be;
     NftDsOpts o;
@@ -59,14 +61,18 @@ int emu_aberthb_roots(size_t n, size_t batch, const cplx *tm, cplx *z, int *mdeg
     NftDiscSpecSearch<EmuBackend> ds(be, n, 1, batch, o);
     int rc = ds.init();
     if (rc != NFT_SUCCESS) return rc;
+    be.memset0(ds.sstatus, batch * sizeof(int));
+    be.memset0(ds.warn, batch * sizeof(int));
     ds.roots(tm);
     for (size_t b = 0; b < batch; b++) {
         const AbState &s = ds.A.state[b];
         std::memcpy(z + b * n, ds.A.zbuf[s.zin] + b * n, n * sizeof(cplx));
         mdeg[b] = s.m;
         status[b] = ds.sstatus[b];
+        warn[b] = ds.warn[b];
+        sweeps[b] = s.sweeps;
     }
-    if (sizes) { sizes[0] = (size_t)ds.A.state[0].sweeps; sizes[1] = (size_t)ds.S; }
+    if (sizes) sizes[0] = (size_t)ds.S;
     return rc;
 }
 

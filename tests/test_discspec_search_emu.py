@@ -44,7 +44,7 @@ def emu():
     L = C.CDLL(EMU_LIB)
     L.emu_discspec_search.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
                                       C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.emu_aberthb_roots.argtypes = [C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]
+    L.emu_aberthb_roots.argtypes = [C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.emu_discspec_search_lds_bytes.argtypes = [C.c_int]
     L.emu_discspec_search_lds_bytes.restype = C.c_size_t
     return L
@@ -163,12 +163,12 @@ def test_zero_end_coefficients(emu):
     tm0 = tm.copy()
     z = np.zeros((len(shapes), n), np.complex128)
     mdeg = np.zeros(len(shapes), np.int32)
-    st = np.zeros(len(shapes), np.int32)
-    sz = np.zeros(2, np.uint64)
-    assert emu.emu_aberthb_roots(n, len(shapes), _P(tm), _P(z), _P(mdeg), _P(st), _P(sz)) == 0
-    assert np.array_equal(tm, tm0) and not st.any()
-    print("sweeps of signal 0", sz[0], "segments of the plan", sz[1])
-    assert sz[1] > 1
+    st, wn, sw = (np.zeros(len(shapes), np.int32) for _ in range(3))
+    sz = np.zeros(1, np.uint64)
+    assert emu.emu_aberthb_roots(n, len(shapes), _P(tm), _P(z), _P(mdeg), _P(st), _P(wn), _P(sw), _P(sz)) == 0
+    assert np.array_equal(tm, tm0) and not st.any() and not wn.any()
+    print("sweeps", sw, "segments of the plan", sz[0])
+    assert sz[0] > 1
     for b, (nl, m, nt) in enumerate(shapes):
         assert mdeg[b] == m
         assert np.isinf(z[b, m:m + nl].real).all() and (z[b, m + nl:] == 0).all()

@@ -9,6 +9,7 @@ from the exact answer at those sizes.
 import numpy as np
 import pytest
 
+import roots_ref
 import signals as S
 
 pytestmark = pytest.mark.gpu
@@ -868,6 +869,10 @@ def test_poly_roots_fasteigen_golden(capi, fixtures):
     rc, r = capi.poly_roots_fasteigen(S.l2c(f["p"]))
     assert rc == 0, capi.last_error()
     assert _hausdorff(r, S.l2c(f["roots_exact"])) <= f["tol_hausdorff"]
+    # the two well-conditioned cases also pass the extended-precision certificate of roots_ref.py (disjoint inclusion
+    # discs, backward error <= 2 n u); the clustered and double-root cases below stay Hausdorff-only: the discs of a
+    # cluster overlap by design
+    roots_ref.certify("reference cubic", S.l2c(f["p"]), r)
     rng = np.random.default_rng(5)
     known = np.concatenate([0.9 * np.exp(2j * np.pi * rng.random(50)), 1.3 * np.exp(2j * np.pi * rng.random(50))])
     rc, r = capi.poly_roots_fasteigen(np.poly(known))
@@ -882,6 +887,7 @@ def test_poly_roots_fasteigen_golden(capi, fixtures):
     c[0], c[n], c[2 * n] = 1.0, -(a + b), a * b
     rc, r = capi.poly_roots_fasteigen(c)
     assert rc == 0 and _hausdorff(r, known) < 1e-12
+    roots_ref.certify("two circles of 300", c, r)
     clustered = np.array([0.5 + 0.5j, 0.5 + 0.5j + 1e-4, 0.5 + 0.5j - 1e-4j, -0.3j, 2.0])
     rc, r = capi.poly_roots_fasteigen(np.poly(clustered))
     # three roots 1e-4 apart: sensitivity eps/sep^2 ~ 2e-8 (numpy.roots, backward stable: 2.6e-8).  The sweeps' worst-case
