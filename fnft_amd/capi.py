@@ -788,6 +788,13 @@ class Plan(_TreePlan):
                                                              C.c_void_p(stream))
         return int(rc), int(deg.value), int(W.value)
 
+    def set_root_handover(self, on=True):
+        """A/B switch for tests and measurements (NftPlan::tune_fuse_root): off, the tree runs its last inverse column
+        pass itself instead of leaving it to the chirp transform's first kernel."""
+        fn = self.L.fnft_amd_debug_root_handover
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+        return int(fn(self.h, 1 if on else 0))
+
     @property
     def device(self):
         return int(self.L.fnft_amd_plan_device(self.h))

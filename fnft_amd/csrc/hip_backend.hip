@@ -358,6 +358,16 @@ double fnft_amd_discspec_stage_ms(FNFT_UINT i, char *name, FNFT_UINT name_cap)
     return v[i].ms;
 }
 
+// measurement and tests only (not declared in include/fnft_amd.h): 0 makes the tree of this plan run its last inverse
+// column pass itself instead of leaving it to the chirp transform's first kernel (NftPlan::tune_fuse_root)
+extern "C" int fnft_amd_debug_root_handover(fnft_amd_plan_t *plan, int enabled)
+{
+    if (!plan) return -1;
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    plan->pl->tune_fuse_root = enabled ? 1 : 0;
+    return 0;
+}
+
 #ifdef FNFT_AMD_TUNING
 // diagnostic builds only: tuning parameters of a plan (which: 0 = row-kernel stagger)
 extern "C" int fnft_amd_debug_tune(fnft_amd_plan_t *plan, int which, int value)

@@ -406,8 +406,10 @@ template <class BE> bool dispatch_col_bridge2(BE &be, const BigLevel &G)
 template <class BE> bool dispatch_chirp_col_fwd(BE &be, const ChirpParams &C)
 {
     const int jobs = C.batch * C.npoly + (C.v_mode == 2 ? 0 : 1);   // the filter job is skipped when its spectrum is cached
+    // root_fused (ChirpParams): a polynomial job's workgroups own columns of the tree, half as many as the filter job's
+    const int n2 = (C.root_fused && C.v_mode == 2) ? C.root_N2 : C.N2;
     switch (C.N1) {
-#define X(n1, ...) case n1: if (C.dft_len > 0) be.template run<KChirpColFwd<n1, true>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); else be.template run<KChirpColFwd<n1>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); return true;
+#define X(n1, ...) case n1: if (C.dft_len > 0) be.template run<KChirpColFwd<n1, true>>(C.N2 / ChirpColCfg<n1>::BC, jobs, C); else be.template run<KChirpColFwd<n1>>(n2 / ChirpColCfg<n1>::BC, jobs, C); return true;
         FA_LIST_CHIRP_N1(X, _)
 #undef X
     default: return false;

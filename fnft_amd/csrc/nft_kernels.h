@@ -1945,6 +1945,14 @@ struct ChirpParams {
     const unsigned *fin_max2;
     double *fin_scale;
     int *fin_wexp;
+    // != 0 (workgroup-uniform; NftPlan::run_contspec_impl decides): the tree did not run the inverse column pass of its
+    // last split level.  body_chirp_col_fwd does it on the way (chirp_col_fwd_root: rows of root_Z in, root_L's tail,
+    // maxima and un-aliasing as body_col_inv, Ybuf out UNSCALED); body_chirp_rows then turns the maxima (fin_max2) into
+    // the scale it applies on load, and one of its workgroups per signal stores fin_scale / fin_wexp
+    int root_fused;
+    int root_N2;         // row length of the tree's split transform: N2 = 2 * root_N2
+    const cplx *root_Z;  // [plane * batch + signal][N1][root_N2], the row kernel's output
+    TreeLevel root_L;
 };
 
 // exp((xr + i*xi)) with a real multiplier folded in: returns exp(t*lr) * cis(t*li)
@@ -2006,6 +2014,121 @@ template <bool DFT> FA_DEV cplx chirp_poly_coef(const ChirpParams &C, int b, int
 // (Measured and dropped in round 3: one workgroup per signal that forms the chirp factor once for both polynomials --
 //  35 -> 39.5 us at cfg 2, half the workgroups; and a 30-instruction sincos for |x| < 2^17 in place of the library's --
 //  no change: the column kernels are not bound by their transcendentals.)
+//
+// ChirpParams::root_fused: the polynomial jobs take chirp_col_fwd_root below, the filter job is as ever.
+//
+// The root of a tree whose last level is split (N = N1 * Nt coefficients 0 .. N-1 plus the tail, Nt = root_N2, with the
+// SAME column length N1 as the chirp transform of length 2N = N1 * 2Nt) is handed over without going to HBM as
+// coefficients.  Chirp element n = n1 * 2Nt + n2 is coefficient kk = N - n (the tail for n = 0, nothing for n > N); with
+// n2 = h Nt + r, h in {0, 1}:
+//     r > 0:  kk = Nt (N1 - 1 - h - 2 n1) + (Nt - r)   -- tree column Nt - r, row N1 - 1 - h - 2 n1
+//     r = 0:  kk = Nt (N1 - h - 2 n1)                  -- tree column 0, row N1 - h - 2 n1 (row N1: the tail, n = 0)
+// so one inverse column transform of tree column t yields the non-zero rows of the chirp columns n2 = (Nt - t) mod Nt
+// and n2 + Nt: its odd rows in reversed order for the first, its even rows for the second.  A workgroup owns the BC tree
+// columns t = (BC bid + c + 1) mod Nt -- shifted by one so that the chirp columns it writes, Nt - 1 - (BC bid + c) and
+// that plus Nt, are whole aligned runs of BC -- of one stored plane of one signal: inverse transform, what
+// body_col_inv does to the coefficients (1/N1, tail product, un-aliasing of coefficient 0, maximum, tail_out), the
+// row permutation (through LDS, or in registers where a lane holds the whole column), chirp factors, two forward
+// transforms.  The maximum of the whole root is only known after this launch: Ybuf is written unscaled.
+// where chirp_col_fwd_root keeps row `row` of its columns in LDS: the lanes of a wave read rows two apart, so the rows of
+// one parity lie next to each other (consecutive lanes then read consecutive 16 * BC bytes)
+template <int N1> FA_HD int root_lds_row(int row) { return (row >> 1) + (row & 1) * (N1 / 2); }
+constexpr int kRootFusedMaxN1 = 8192;   // column lengths below this have the mode (8192: 16 points per lane, no registers left)
+template <int N1, int R, int BC, bool DB> FA_DEV void chirp_col_fwd_root(const ChirpParams &C, cplx *lds)
+{
+    const TreeLevel &L = C.root_L;
+    const int Nt = C.root_N2;
+    if (FA_BID * BC >= Nt) return;   // the grid may be the filter job's: 2 Nt / BC
+    const int tid = FA_TID;
+    const int c = tid % BC, v = tid / BC;
+    const int job = FA_BID_Y;
+    const int b = job / C.npoly, e = C.entry[job % C.npoly];   // signal = output matrix of the level, stored plane
+    const int n_out = L.n_in / 2;                               // = batch
+    const int n2a = Nt - 1 - (FA_BID * BC + c);                 // chirp columns n2a and n2a + Nt
+    const int t = (n2a == 0) ? 0 : Nt - n2a;                    // tree column
+    const bool r0 = (n2a == 0);
+    const long long N = (long long)N1 * Nt;
+    const cplx *src = C.root_Z + ((size_t)e * n_out + b) * (size_t)N;
+    const double sA = level_in_scale(L, 2 * b), sB = level_in_scale(L, 2 * b + 1);   // wave-uniform
+    cplx x[R];
+#pragma unroll
+    for (int i = 0; i < R; i++) x[i] = src[yz_index(N1, Nt, v + (N1 / R) * i, t)];
+    int parity = 0;
+    fft_wg<N1, R, BC, +1, DB, true>(x, lds, v, c, C.tw1, parity);
+    const double inv = 1.0 / (double)N1;
+    double m2 = 0.0;
+    cplx tp = cmake(0.0, 0.0);
+    if (r0 && v == 0) {   // the lane that holds coefficient 0; it is also the one that forms chirp element n = 0
+        tp = split_tail_product(L, b, e, sA, sB);
+        L.tail_out[(size_t)e * n_out + b] = tp;
+        m2 = cnorm2(tp);
+    }
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+        cplx val = x[i] * inv;
+        if (r0 && v + (N1 / R) * i == 0) val = val - tp;   // N = 2d: un-alias coefficient 2d folded onto 0
+        m2 = fmax(m2, cnorm2(val));
+        x[i] = val;
+    }
+    fa_wave_atomic_max_hi32(&L.max2_out[(size_t)b * kMax2Slots + max2_slot()], m2);   // b is uniform in the workgroup
+    if constexpr (N1 > R) {
+        FA_SYNC_LDS();   // the transform's last exchange has been read
+#pragma unroll
+        for (int i = 0; i < R; i++) lds[(size_t)root_lds_row<N1>(v + (N1 / R) * i) * BC + c] = x[i];
+        FA_SYNC_LDS();
+    }
+    // Rows n1 >= N1/2 of a chirp column are zero (n > N) but for one element: n = N, coefficient 0, which is row N1/2 of
+    // chirp column 0.  So a lane has R/2 non-zero elements per column, i < R/2 (there row >= 0 always), and the transform
+    // starts from registers that are zero at compile time; the odd element's share, cv (-1)^k1, is added afterwards.
+    constexpr int H = R / 2;
+    const long long Lc = 2 * N;
+    cplx *dst = C.Ybuf + (size_t)job * Lc;
+    // coefficient of row n1 = v + (N1/R) i, i < H, of chirp column n2a + h Nt
+    auto coef_of = [&](int h, int i) -> cplx {
+        const int row = N1 - 2 * (v + (N1 / R) * i) - h - (r0 ? 0 : 1);
+        cplx coef;
+        if constexpr (N1 > R) {
+            coef = lds[(size_t)root_lds_row<N1>(row < N1 ? row : 0) * BC + c];
+        } else {   // v = 0: both candidates are registers known at compile time
+            constexpr int kLast = N1 - 1;
+            const int ra = N1 - 2 * i - h - 1, rb = N1 - 2 * i - h;
+            coef = r0 ? x[rb > kLast ? kLast : rb] : x[ra];
+        }
+        return (row == N1) ? tp : coef;   // row N1: n = 0, the tail
+    };
+    // :68-69  p[deg-n] * A^-n * W^(n^2/2)
+    auto chirp_of = [&](int h, int i) -> cplx {
+        const double dn = (double)((long long)(v + (N1 / R) * i) * (2 * Nt) + n2a + h * Nt);
+        return cpow_real2(C.logA, -dn, C.logW, 0.5 * dn * dn);
+    };
+    cplx y[R];
+#pragma unroll
+    for (int i = 0; i < R; i++) y[i] = (i < H) ? coef_of(0, i) * chirp_of(0, i) : cmake(0.0, 0.0);
+    cplx co1[H];   // the second column's coefficients: the first column's transform takes the LDS
+#pragma unroll
+    for (int i = 0; i < H; i++) co1[i] = coef_of(1, i);
+    cplx cv = cmake(0.0, 0.0);
+    if (r0) {   // n = N
+        cplx c0;
+        if constexpr (N1 > R) c0 = lds[c];
+        else c0 = x[0];
+        const double dn = (double)N;
+        cv = c0 * cpow_real2(C.logA, -dn, C.logW, 0.5 * dn * dn);
+    }
+    fft_wg<N1, R, BC, -1, DB, true>(y, lds, v, c, C.tw1, parity);
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+        const int k1 = v + (N1 / R) * i;
+        if (r0) y[i] = (k1 & 1) ? y[i] - cv : y[i] + cv;
+        dst[yz_index(N1, 2 * Nt, k1, n2a)] = y[i];
+    }
+#pragma unroll
+    for (int i = 0; i < R; i++) y[i] = (i < H) ? co1[i] * chirp_of(1, i) : cmake(0.0, 0.0);
+    fft_wg<N1, R, BC, -1, DB, true>(y, lds, v, c, C.tw1, parity);
+#pragma unroll
+    for (int i = 0; i < R; i++) dst[yz_index(N1, 2 * Nt, v + (N1 / R) * i, n2a + Nt)] = y[i];
+}
+
 template <int N1, int R, int BC, bool DB, bool DFT> FA_DEV void body_chirp_col_fwd(const ChirpParams &C)
 {
     FA_LDS_DECL
@@ -2015,6 +2138,12 @@ template <int N1, int R, int BC, bool DB, bool DFT> FA_DEV void body_chirp_col_f
     const int n2 = FA_BID * BC + c;
     const int job = FA_BID_Y;
     const int njobs = C.batch * C.npoly;
+    if constexpr (!DFT && N1 < kRootFusedMaxN1) {
+        if (C.root_fused && job < njobs) {
+            chirp_col_fwd_root<N1, R, BC, DB>(C, lds);
+            return;
+        }
+    }
     const long long Lc = (long long)N1 * C.N2;
     const long long Np = C.deg + 1;
     // pending scale of this job's signal: stored, or (root not finalized yet) from the 64 unreduced maxima -- every
@@ -2073,6 +2202,16 @@ template <int N2, int R, bool DB> FA_DEV void body_chirp_rows(const ChirpParams 
     const int k1 = FA_BID;
     const long long Lc = (long long)C.N1 * N2;
     int parity = 0;
+    const int njobs = C.batch * C.npoly;
+    const int job0 = FA_BID_Y * C.jobs_per_group;
+    const int job1 = (job0 + C.jobs_per_group < njobs) ? job0 + C.jobs_per_group : njobs;
+    // root_fused (see the job loop): the maxima of the first job's signal are asked for before anything else, so that
+    // they have arrived when the first row is loaded; exponent 0 (scale 1) otherwise
+    int fin_b = -1, fin_a = 0;
+    if (C.root_fused) {
+        fin_b = job0 / C.npoly;
+        fin_a = exponent_of_max2(fa_slots_max_u32(C.fin_max2 + (size_t)fin_b * kMax2Slots));
+    }
     // w_L^{k1 n2} for n2 = v + (N2/R) i: per-lane base times workgroup-uniform factors
     const cplx base = big_twiddle(C.btw, (unsigned)k1 * (unsigned)v);
     cplx tw[R];
@@ -2094,15 +2233,24 @@ template <int N2, int R, bool DB> FA_DEV void body_chirp_rows(const ChirpParams 
             for (int i = 0; i < R; i++) vd[v + (N2 / R) * i] = vv[i];
         }
     }
-    const int njobs = C.batch * C.npoly;
     const double inv = 1.0 / (double)N2;
-    const int job0 = FA_BID_Y * C.jobs_per_group;
-    const int job1 = (job0 + C.jobs_per_group < njobs) ? job0 + C.jobs_per_group : njobs;
     for (int job = job0; job < job1; job++) {
         cplx *ys = C.Ybuf + (size_t)job * Lc;
         cplx y[R];
+        // root_fused: Ybuf is unscaled and the root not finalized -- the pending scale from the 64 maxima of the job's
+        // signal, applied with the load twiddle (a power of two: exact); the workgroup of row 0 that has the signal's
+        // first polynomial stores scale and exponent
+        if (C.root_fused && job / C.npoly != fin_b) {   // every lane of every wave is active here
+            fin_b = job / C.npoly;
+            fin_a = exponent_of_max2(fa_slots_max_u32(C.fin_max2 + (size_t)fin_b * kMax2Slots));
+        }
+        const double sc = pow2i(-fin_a);
+        if (C.root_fused && k1 == 0 && job % C.npoly == 0 && v == 0) {
+            C.fin_scale[fin_b] = sc;
+            C.fin_wexp[fin_b] = C.fin_wexp[fin_b] + fin_a;
+        }
 #pragma unroll
-        for (int i = 0; i < R; i++) y[i] = ys[yz_index(C.N1, N2, k1, v + (N2 / R) * i)] * tw[i];
+        for (int i = 0; i < R; i++) y[i] = ys[yz_index(C.N1, N2, k1, v + (N2 / R) * i)] * (tw[i] * sc);
         fft_wg<N2, R, 1, -1, DB, true>(y, lds, v, 0, C.tw2, parity);
 #pragma unroll
         for (int i = 0; i < R; i++) y[i] = y[i] * vv[i];

@@ -164,20 +164,39 @@ public:
     size_t Lc = 0;           // chirp transform length
     int cur = 0;             // index of the body/tail/scale set holding the current level
     bool tree_valid = false;
-    // The last split level leaves its maxima unreduced (64 slots per matrix): turning them into the pending scale and
-    // the final exponent is a one-wave job (KFinalizeScales, 6 us as a launch of its own between the tree and the
-    // evaluation).  The chirp transform's first kernel does it on the way (every workgroup reduces the slots of its
-    // signal for itself, one of them stores scale and exponent: ChirpParams::fin_*); every other consumer of the root
-    // (export, discrete spectrum, block matrices) calls ensure_final() first.
+    // The last split level leaves two things undone.
+    // (1) Its maxima stay unreduced (64 slots per matrix): turning them into the pending scale and the final exponent is
+    // a one-wave job (KFinalizeScales, 6 us as a launch of its own between the tree and the evaluation) that a kernel of
+    // the chirp transform does on the way (ChirpParams::fin_*: every workgroup reduces the slots of its signal for
+    // itself, one of them stores scale and exponent).  final_pending says that this is still to be done.
+    // (2) Where the chirp transform can take the root straight from the row kernel's output (root_fusable), the level's
+    // inverse column pass is not launched either: the chirp transform's first kernel does it in registers
+    // (ChirpParams::root_fused, hand_final_to), and the root's coefficients -- body[cur], tail[cur] -- do not exist in
+    // HBM.  root_pending says so; root_G and root_inv are the pass as the tree would have launched it.  Z is scratch of
+    // the tree run that produced it, so a new run_tree drops a pending root.
+    // Every reader of the root other than the fused chirp kernel (export, and through it the discrete spectrum, the
+    // block matrices and the inverse plans' trees; the chirp transform on a shape that is not eligible) calls
+    // ensure_root() first: the kept pass, then the finalize unless a chirp kernel has done it already.
     bool final_pending = false;
     TreeLevel final_L;
     size_t final_n = 0;
+    bool root_pending = false;
+    BigLevel root_G;
+    bool (*root_inv)(BE &, const BigLevel &) = nullptr;
     void defer_final(const TreeLevel &L, size_t n_out) { final_L = L; final_n = n_out; final_pending = true; }
     void ensure_final()
     {
         if (!final_pending) return;
         be.template run<KFinalizeScales>((int)final_n, 1, final_L);
         final_pending = false;
+    }
+    void ensure_root()
+    {
+        if (root_pending) {
+            root_pending = false;
+            root_inv(be, root_G);   // dispatched once already when the level was run: the length is instantiated
+        }
+        ensure_final();
     }
     size_t res_deg = 0;      // degree of the transfer matrix of the last tree run
     size_t start_n = 0, start_d = 0;  // matrices (all signals) / degree the tree run starts from
@@ -189,6 +208,7 @@ public:
     int stamp_level = -1;                        // split level (0 = first) whose row kernel is stamped
     int last_warn = 0;       // bit 0: the resampler found the signal not band-limited (set by read_status)
     int tune_stagger = 0;    // row kernel start delay of the second half of a one-round grid (BigLevel::stagger)
+    int tune_fuse_root = 1;  // 0: the tree always runs its last inverse column pass itself (A/B runs of ChirpParams::root_fused)
     int dbg_flags = 0;       // timing ablation: only builds with -DFNFT_AMD_ABLATION ever set it (hip_backend.hip)
 
     NftPlan(BE &be_, size_t D_, size_t M_, size_t batch_, int akns_disc_, int deg0_)
@@ -626,15 +646,37 @@ public:
         bool ok = true;
         if (!w.y_from_bridge && !G.y_direct) ok = fwd(be, G);
         if (ok) run_mid(be, G);
-        if (ok) ok = next_split ? bridge(be, G) : inv(be, G);
+        const bool last_level = G.L.pairs_per_signal <= 1;
+        if (ok && !next_split && last_level && root_fusable(G)) {
+            root_G = G;
+            root_inv = inv;
+            root_pending = true;
+        } else if (ok) {
+            ok = next_split ? bridge(be, G) : inv(be, G);
+        }
         w.zcur ^= 1;
         w.y_from_bridge = ok && next_split;
         // the consumer of the next level finalizes this one; the last level needs a kernel
-        const bool last_level = G.L.pairs_per_signal <= 1;
         if (ok && last_level) defer_final(G.L, (size_t)G.L.n_in / 2);
         w.in_pending = !last_level;
         w.mcur ^= 1;
         return ok;
+    }
+    // The chirp transform of this plan can take the root of the last split level G from the row kernel's output
+    // (chirp_col_fwd_root, nft_kernels.h): complex symmetric form, one matrix per signal, no padding (deg = deg_tot = N,
+    // so N = 2d and coefficient kk is chirp element N - kk), and a chirp of length 2N -- M <= D*deg0 -- whose rows are
+    // twice the tree's, so that both have the same column length.  Plans of fewer than kRootFusedMinM spectral points keep
+    // the root's last pass inside the tree: a conservative cut -- those are the plans that are made for their transfer
+    // matrix (a few points to check, then the export; tests/test_gpu_tree_paths.py pins KColInv<N1> in the transform of
+    // its M = 64 plans), and the saving does not depend on M.
+    static constexpr size_t kRootFusedMinM = 512;
+    bool root_fusable(const BigLevel &G) const
+    {
+        if (kRowChirp != 2 * kRowTree) return false;
+        const size_t N = (size_t)G.N1 * (size_t)G.N2;
+        return tune_fuse_root != 0 && dbg_flags == 0 && !real_run && ne == 2 && G.L.ne == 2 && M >= kRootFusedMinM && chY != nullptr
+               && G.N1 < kRootFusedMaxN1 && G.N2 == kRowTree && Lc == 2 * N && N == 2 * (size_t)G.L.d && D == Dpad && N == D * (size_t)deg0
+               && (size_t)(G.L.n_in / 2) == batch;
     }
 
     // the same tree on real coefficients (nft_real.h): folded transforms of length M = nft_real_len(d)
@@ -719,6 +761,7 @@ public:
     int run_tree()
     {
         final_pending = false;   // an unconsumed root of an earlier run is dropped
+        root_pending = false;
         if (real_run) return run_tree_real();
         size_t n = start_n;     // matrices at the current level, all signals
         size_t d = start_d;
@@ -801,7 +844,7 @@ public:
     // bstride: distance between the signals of a batch in dst
     void export_tm(cplx *dst = nullptr, size_t stride = 0, bool unscale = false, size_t bstride = 0)
     {
-        ensure_final();
+        ensure_root();
         ExportParams E;
         E.body = body[cur]; E.tail = tail[cur]; E.scale = scale[cur];
         E.out = dst ? dst : tm_out;
@@ -943,9 +986,29 @@ public:
         return run_chirp_cached(C);
     }
 
-    // the root's pending finalize rides on the chirp transform's column kernel (one matrix per signal at the root)
+    // the root's pending finalize rides on a kernel of the chirp transform (one matrix per signal at the root): on the row
+    // kernel, with the root's last inverse column pass on the first column kernel, when that pass is still pending
+    // (root_fusable said that this plan's chirp transform can take it; the checks here are about THIS transform); on the
+    // first column kernel otherwise
     void hand_final_to(ChirpParams &C)
     {
+        if (root_pending && final_pending && final_n == batch && C.poly == nullptr && !C.real_layout && C.ne == 2
+            && C.npoly == 2 && C.dft_len == 0 && C.N1 == root_G.N1 && C.N2 == 2 * root_G.N2 && C.deg == C.deg_tot
+            && C.deg == (long long)root_G.N1 * root_G.N2) {
+            C.root_fused = 1;
+            C.root_N2 = root_G.N2;
+            C.root_Z = root_G.Z;
+            C.root_L = root_G.L;
+            C.fin_max2 = final_L.max2_out;
+            C.fin_scale = final_L.scale_out;
+            C.fin_wexp = final_L.wexp_out;
+            final_pending = false;   // the coefficients stay pending: ensure_root() makes them for whoever asks
+            return;
+        }
+        if (root_pending) {
+            root_pending = false;
+            root_inv(be, root_G);
+        }
         if (!final_pending) return;
         if (final_n != batch) { ensure_final(); return; }
         C.fin_max2 = final_L.max2_out;
