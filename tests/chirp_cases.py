@@ -117,8 +117,8 @@ CASES = [
 
 EXCLUDED = {}
 
-# degree per step of the schemes used above (nft_akns_degree)
-DEG0 = {"2SPLIT2_MODAL": 1, "2SPLIT1A": 1, "2SPLIT2A": 1, "2SPLIT3A": 3, "2SPLIT4B": 2}
+# degree per step of the schemes used above and in tests/handover_cases.py (nft_akns_degree)
+DEG0 = {"2SPLIT2_MODAL": 1, "2SPLIT1A": 1, "2SPLIT2A": 1, "2SPLIT3A": 3, "2SPLIT3S": 2, "2SPLIT4A": 4, "2SPLIT4B": 2}
 
 
 def case_ids():
