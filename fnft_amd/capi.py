@@ -87,7 +87,8 @@ PRINTF_T = C.CFUNCTYPE(C.c_int32, C.c_char_p)  # variadic in C; used only to sil
 EXPORTED = [
     "fnft_nsev", "fnft_nsev_default_opts", "fnft_nsev_max_K", "fnft_errwarn_setprintf",
     "fnft_errwarn_getprintf", "fnft__poly_fmult2x2_numel", "fnft__poly_fmult2x2",
-    "fnft_amd_poly_chirpz", "fnft__poly_chirpz", "fnft__akns_fscatter_numel", "fnft__akns_fscatter",
+    "fnft_amd_poly_chirpz", "fnft__poly_chirpz", "fnft__poly_eval", "fnft__poly_evalderiv", "fnft_amd_poly_eval_device",
+    "fnft_amd_nsev_eval_device", "fnft__akns_fscatter_numel", "fnft__akns_fscatter",
     "fnft__nse_fscatter_numel", "fnft__nse_fscatter", "fnft_amd_device_count",
     "fnft_amd_last_error", "fnft_amd_plan_create", "fnft_amd_plan_create_sub", "fnft_amd_plan_destroy",
     "fnft_amd_plan_workspace_bytes", "fnft_amd_nsev_contspec_device", "fnft_amd_plan_finish",
@@ -152,6 +153,14 @@ def load(path=None):
     L.fnft__poly_fmult2x2.argtypes = [C.POINTER(sz), sz, vp, vp, C.POINTER(i32)]
     L.fnft_amd_poly_chirpz.restype = i32
     L.fnft_amd_poly_chirpz.argtypes = [sz, vp, C.POINTER(dbl), C.POINTER(dbl), sz, vp]
+    L.fnft__poly_eval.restype = i32
+    L.fnft__poly_eval.argtypes = [sz, vp, sz, vp]
+    L.fnft__poly_evalderiv.restype = i32
+    L.fnft__poly_evalderiv.argtypes = [sz, vp, sz, vp, vp]
+    L.fnft_amd_poly_eval_device.restype = i32
+    L.fnft_amd_poly_eval_device.argtypes = [sz, sz, sz, vp, sz, sz, sz, vp, sz, vp, vp, vp]
+    L.fnft_amd_nsev_eval_device.restype = i32
+    L.fnft_amd_nsev_eval_device.argtypes = [vp, C.POINTER(dbl), vp, sz, sz, i32, vp, vp]
     L.fnft__akns_fscatter_numel.restype = sz
     L.fnft__akns_fscatter_numel.argtypes = [sz, C.c_int]
     L.fnft__akns_fscatter.restype = i32
@@ -624,6 +633,32 @@ def poly_chirpz(p, A, W, M):
     return int(rc), out
 
 
+def poly_eval(p, z):
+    """fnft__poly_eval: (rc, p(z)) for the coefficients p (highest power first) at the points z (not modified)."""
+    L = load()
+    p, v = _c128(p), _c128(z).copy()
+    rc = L.fnft__poly_eval(p.size - 1, _ptr(p), v.size, _ptr(v))
+    return int(rc), v
+
+
+def poly_evalderiv(p, z):
+    """fnft__poly_evalderiv: (rc, p(z), p'(z))."""
+    L = load()
+    p, v = _c128(p), _c128(z).copy()
+    d = np.zeros(v.size, np.complex128)
+    rc = L.fnft__poly_evalderiv(p.size - 1, _ptr(p), v.size, _ptr(v), _ptr(d))
+    return int(rc), v, d
+
+
+def poly_eval_device(deg, npoly, batch, p_ptr, pstride, bstride, nz, z_ptr, zstride, val_ptr, deriv_ptr=0, stream=0):
+    """fnft_amd_poly_eval_device on raw device addresses (e.g. tensor.data_ptr()); deriv_ptr 0: values only.  The outputs
+    are [batch][npoly][nz]; zstride 0 shares one point list among the signals.  Waits for the stream once."""
+    return int(load().fnft_amd_poly_eval_device(int(deg), int(npoly), int(batch), C.c_void_p(p_ptr), int(pstride),
+                                                int(bstride), int(nz), C.c_void_p(z_ptr), int(zstride),
+                                                C.c_void_p(val_ptr), C.c_void_p(deriv_ptr) if deriv_ptr else None,
+                                                C.c_void_p(stream)))
+
+
 def akns_fscatter(q, r, eps_t, discretization, normalize=True):
     L = load()
     q, r = _c128(q), _c128(r)
@@ -779,6 +814,18 @@ class Plan(_TreePlan):
         c = CSTYPE[contspec_type] if isinstance(contspec_type, str) else int(contspec_type)
         return int(self.L.fnft_amd_nsev_contspec_from_tm_device(self.h, C.c_void_p(tm_ptr), int(W), C.c_void_p(out_ptr),
                                                                 _d2(T), _d2(XI), c, C.c_void_p(stream)))
+
+    def eval_len(self, n, derivative=False):
+        """complex128 per signal that eval_device writes: [a(n) | b(n)], with derivative [a | b | a' | b']."""
+        return (4 if derivative else 2) * int(n)
+
+    def eval_device(self, lam_ptr, n, out_ptr, T, derivative=False, per_signal=False, stream=0):
+        """fnft_amd_nsev_eval_device: a(lambda), b(lambda) of the last contspec_device call's transfer matrix at n complex
+        points per signal (raw device addresses; per_signal: batch lists of n points instead of one shared list), T the
+        interval passed to contspec_device.  Enqueues; finish() waits."""
+        return int(self.L.fnft_amd_nsev_eval_device(self.h, _d2(T), C.c_void_p(lam_ptr), int(n),
+                                                    int(n) if per_signal else 0, 1 if derivative else 0,
+                                                    C.c_void_p(out_ptr), C.c_void_p(stream)))
 
     def transfer_matrix_device(self, out_ptr, b=0, stream=0):
         """Transfer matrix of signal b into a device buffer of 4*(deg+1) complex128; returns (rc, deg, W)."""

@@ -513,6 +513,27 @@ FNFT_INT fnft_amd_nsev_contspec_from_tm_device(fnft_amd_plan_t *plan, const void
     return rc;
 }
 
+// a(lambda), b(lambda) of the plan's last tree run at n arbitrary complex lambda per signal (Plan::run_eval)
+FNFT_INT fnft_amd_nsev_eval_device(fnft_amd_plan_t *plan, const FNFT_REAL *T, const void *d_lambda, FNFT_UINT n,
+                                   FNFT_UINT lambda_stride, FNFT_INT derivative_flag, void *d_out, void *stream)
+{
+    if (!plan || !T || !d_lambda || !d_out || !(T[0] < T[1]) || (lambda_stride != 0 && lambda_stride < n))
+        return FNFT_EC_INVALID_ARGUMENT;
+    if (plan->kdv_disc >= 0 || !plan->pl->tree_valid) return -FNFT_EC_INVALID_ARGUMENT;
+    if (plan->pl->nskip > 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
+    if (n == 0) return FNFT_SUCCESS;
+    std::lock_guard<std::mutex> lk(plan->mtx);
+    DeviceGuard dg(plan->device);
+    if (!dg.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->pl;
+    plan->be.stream = (hipStream_t)stream;
+    plan->be.failed = false;
+    const int rc = pl.run_eval(T, plan->nse_disc, (const cplx *)d_lambda, n, lambda_stride, derivative_flag != 0,
+                               (cplx *)d_out);
+    if (plan->be.failed) return FNFT_EC_OTHER;
+    return rc;
+}
+
 // ---- KdV ----------------------------------------------------------------------------------------
 FNFT_INT fnft_amd_kdvv_plan_create(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
                                    fnft_kdv_discretization_t discretization, int device)
@@ -1444,6 +1465,68 @@ FNFT_INT fnft__poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, con
 {
     const double a[2] = {A.real(), A.imag()}, w[2] = {W.real(), W.imag()};
     return fnft_amd_poly_chirpz(deg, p, a, w, M, result);
+}
+
+// include/private/fnft__poly_eval.h:43-44, :66-68 (src/private/fnft__poly_eval.c:25-53, :55-91): p at the nz points z, in
+// place; the derivative goes to deriv.  KPolyEval / KPolyJoin on the current device.
+static FNFT_INT poly_eval_host(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z,
+                               FNFT_COMPLEX *const deriv)
+{
+    if (current_device() < 0) return FNFT_EC_OTHER;
+    std::lock_guard<std::mutex> host_lk(host_call_mutex());
+    HipBackend be;
+    DevArena<HipBackend> tmp(be);
+    cplx *dp = nullptr, *dz = nullptr, *dv = nullptr, *dd = nullptr;
+    if (!tmp.get(dp, deg + 1) || !tmp.get(dz, nz) || !tmp.get(dv, nz) || (deriv && !tmp.get(dd, nz))) return FNFT_EC_NOMEM;
+    be.h2d(dp, p, (deg + 1) * sizeof(cplx));
+    be.h2d(dz, z, nz * sizeof(cplx));
+    int rc = polyeval_device(be, deg, 1, 1, dp, deg + 1, deg + 1, nz, dz, 0, dv, dd);
+    if (rc == NFT_SUCCESS) {
+        be.d2h(z, dv, nz * sizeof(cplx));
+        if (deriv) be.d2h(deriv, dd, nz * sizeof(cplx));
+        rc = be.sync();
+    }
+    if (be.failed) return FNFT_EC_OTHER;
+    return rc;
+}
+
+FNFT_INT fnft__poly_eval(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z)
+{
+    SEAM_CHECK(!p, p);   // :32-35
+    SEAM_CHECK(!z, z);
+    if (nz == 0) return FNFT_SUCCESS;
+    return poly_eval_host(deg, p, nz, z, nullptr);
+}
+
+FNFT_INT fnft__poly_evalderiv(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z,
+                              FNFT_COMPLEX *const deriv)
+{
+    SEAM_CHECK(!p, p);   // :63-66
+    SEAM_CHECK(!z, z);
+    if (nz == 0) return FNFT_SUCCESS;
+    SEAM_CHECK(!deriv, deriv);   // the reference would write through it
+    return poly_eval_host(deg, p, nz, z, deriv);
+}
+
+// The same on device arrays, batched: npoly polynomials per signal (d_p + b*bstride + j*pstride, deg+1 coefficients,
+// highest power first) at nz points per signal (d_z + b*zstride; zstride 0: one list for all signals); d_val and d_deriv
+// (may be NULL) are [batch][npoly][nz].  On `stream` of the current device; waits for it once (pooled scratch).
+FNFT_INT fnft_amd_poly_eval_device(FNFT_UINT deg, FNFT_UINT npoly, FNFT_UINT batch, const void *d_p, FNFT_UINT pstride,
+                                   FNFT_UINT bstride, FNFT_UINT nz, const void *d_z, FNFT_UINT zstride, void *d_val,
+                                   void *d_deriv, void *stream)
+{
+    if (!d_p || !d_z || !d_val || npoly == 0 || batch == 0 || pstride < deg + 1 || (zstride != 0 && zstride < nz))
+        return FNFT_EC_INVALID_ARGUMENT;
+    if (batch > 1 && bstride < deg + 1) return FNFT_EC_INVALID_ARGUMENT;
+    if (nz == 0) return FNFT_SUCCESS;
+    if (current_device() < 0) return FNFT_EC_OTHER;
+    std::lock_guard<std::mutex> host_lk(host_call_mutex());
+    HipBackend be;
+    be.stream = (hipStream_t)stream;
+    const int rc = polyeval_device(be, deg, npoly, batch, (const cplx *)d_p, pstride, bstride, nz, (const cplx *)d_z, zstride,
+                                   (cplx *)d_val, (cplx *)d_deriv);
+    if (be.failed) return FNFT_EC_OTHER;
+    return rc;
 }
 
 // include/private/fnft__misc.h:241-242 (src/private/fnft__misc.c:326-407): band-limited shift by delta

@@ -1,6 +1,6 @@
 // hip_be.h -- HIP back end of NftPlan (device memory, copies, kernel launches, event timers) and the
-// kernel entry template.  The library is built from 23 kernel translation units so that the 258 kernel
-// instantiations compile in parallel: HipBackend::run<K> is only DECLARED for the host logic
+// kernel entry template.  The library is built from 24 kernel translation units so that the 261 kernel
+// instantiations (FA_ALL_UNITS: 258 in 23 units, FA_EXT_UNITS: 3 in one) compile in parallel: HipBackend::run<K> is only DECLARED for the host logic
 // (hip_backend.hip); each hip_kernels_<name>.hip defines FA_HIP_RUN_IMPL, sees the definition, and
 // instantiates run<K> -- and with it kernel_entry<K> -- explicitly for its group of kernels,
 // FA_UNIT_<name>(FA_INST).  nft_kernel_list.h states the groups, from the same size lists the dispatch

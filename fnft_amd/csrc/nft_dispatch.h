@@ -87,6 +87,12 @@ FA_FUNCTOR(KAberthBSum, AberthBatchParams, 256, 256 * sizeof(cplx), body_aberthb
 FA_FUNCTOR(KAberthBApply, AberthBatchParams, 256, 0, body_aberthb_apply);
 FA_FUNCTOR(KAberthBStep, AberthBatchParams, 256, 0, body_aberthb_step);
 FA_FUNCTOR(KDsCandidates, AberthBatchParams, 256, (256 + 1) * sizeof(int), body_ds_candidates);
+// polynomials at arbitrary points (fnft__poly_eval, fnft_amd_nsev_eval_device): tiles of kPolyEvalTile coefficients, both
+// orientations
+constexpr int kPolyEvalTile = 512;
+template <bool DERIV> FA_FUNCTOR(KPolyEval, PolyEvalParams, 256, 2 * kPolyEvalTile * sizeof(cplx),
+                                (body_polyeval<kPolyEvalTile, DERIV>));
+FA_FUNCTOR(KPolyJoin, PolyEvalParams, 256, 0, body_polyjoin);
 template <int DEG> struct LeafCfg {
     static constexpr int SPT = (DEG == 1) ? 8 : (DEG == 2 ? 4 : 2);
 };

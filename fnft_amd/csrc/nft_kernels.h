@@ -4944,3 +4944,283 @@ FA_DEV void body_slow_combine(const SlowParams &P)
     }
     if (zero) fa_atomic_or_i32(P.status + b, 1);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Polynomials at arbitrary points (include/private/fnft__poly_eval.h, src/private/fnft__poly_eval.c:25-91): `npoly`
+// polynomials per signal, `nz` complex points per signal, value and optionally derivative; and on top of it the NSE
+// spectrum a(lambda), b(lambda) of a plan's transfer matrix at arbitrary lambda (fnft_amd_nsev_eval_device).
+//   body_polyeval<DERIV>  lane = point, blockIdx.y = segment of the coefficient range: P_s(x) and P_s'(x), the powers
+//                         [s*L, (s+1)*L) of x = z (|z| <= 1) or of the reversed polynomial in x = 1/z (|z| > 1)
+//   body_polyjoin         lane = point: p = sum_s x^(sL) P_s, p' likewise, the power z^deg outside the unit circle
+//                         (:48, :86-87), and in NSE mode the epilogue 2^W exp(i lambda pf) with the chain rule
+// What is carried in two doubles.  The chains advance by w = x^8 and the join by y = x^L: a relative error delta of w
+// turns term k of the polynomial by k*delta/8, and these errors are coherent -- they add up to delta |x p'(x)| / 8, of
+// order sqrt(deg) u of the scale sum |c_k| |x|^k where plain Horner in z (the reference) errs by a few u.  The same
+// holds for x = 1/z itself, which exp(i theta) of a real lambda needs on every other point (|z| = 1 + u).  So 1/z, the
+// powers x^0..x^8, x^(L-1), x^L and z^deg are kept as unevaluated sums hi + lo (error ~1e-32), and a Horner step is
+// acc*w_hi + (acc*w_lo + c): the low part only has to be good to a few digits, but it has to be there.
+// The error-free transformations below are exact only operation by operation: nothing in them may be contracted (a
+// product fused into the sum that is meant to measure its rounding error counts that error twice, and z^deg is back to
+// deg u / 2), so each of them switches contraction off and states its FMAs itself.
+// ---------------------------------------------------------------------------------------------
+struct dd2 {
+    double h, l;
+};
+FA_DEV dd2 dd_make(double a) { return dd2{a, 0.0}; }
+FA_DEV dd2 dd_fast_two_sum(double a, double b)   // |a| >= |b|
+{
+#pragma clang fp contract(off)
+    const double s = a + b;
+    return dd2{s, b - (s - a)};
+}
+FA_DEV dd2 dd_two_sum(double a, double b)
+{
+#pragma clang fp contract(off)
+    const double s = a + b, bb = s - a;
+    return dd2{s, (a - (s - bb)) + (b - bb)};
+}
+FA_DEV dd2 dd_add(dd2 a, dd2 b)
+{
+#pragma clang fp contract(off)
+    dd2 s = dd_two_sum(a.h, b.h);
+    const dd2 t = dd_two_sum(a.l, b.l);
+    s = dd_fast_two_sum(s.h, s.l + t.h);
+    return dd_fast_two_sum(s.h, s.l + t.l);
+}
+FA_DEV dd2 dd_neg(dd2 a) { return dd2{-a.h, -a.l}; }
+FA_DEV dd2 dd_mul(dd2 a, dd2 b)
+{
+#pragma clang fp contract(off)
+    const double p = a.h * b.h;
+    const double e = fma(a.h, b.h, -p) + fma(a.h, b.l, a.l * b.h);
+    return dd_fast_two_sum(p, e);
+}
+struct cdd {
+    dd2 re, im;
+};
+FA_DEV cdd cdd_make(cplx a) { return cdd{dd_make(a.x), dd_make(a.y)}; }
+FA_DEV cplx cdd_hi(cdd a) { return cmake(a.re.h, a.im.h); }
+FA_DEV cplx cdd_lo(cdd a) { return cmake(a.re.l, a.im.l); }
+FA_DEV cdd cdd_mul(cdd a, cdd b)
+{
+    return cdd{dd_add(dd_mul(a.re, b.re), dd_neg(dd_mul(a.im, b.im))), dd_add(dd_mul(a.re, b.im), dd_mul(a.im, b.re))};
+}
+// x^e, e >= 0, by repeated squaring like c_powi
+FA_DEV cdd cdd_powi(cdd x, long long e)
+{
+    cdd r = cdd_make(cmake(1.0, 0.0));
+    while (e > 0) {
+        if (e & 1) r = cdd_mul(r, x);
+        e >>= 1;
+        if (e > 0) x = cdd_mul(x, x);
+    }
+    return r;
+}
+// 1/z: Smith's quotient, then one Newton correction from the residual 1 - z*x formed in two doubles
+FA_DEV cdd cdd_recip(cplx z)
+{
+#pragma clang fp contract(off)
+    const cplx xh = c_div(cmake(1.0, 0.0), z);
+    const cdd zx = cdd_mul(cdd_make(z), cdd_make(xh));
+    const dd2 rre = dd_add(dd_make(1.0), dd_neg(zx.re));
+    const cplx r = cmake(rre.h + rre.l, -(zx.im.h + zx.im.l));   // 1 - z*xh, of order u
+    const cplx xl = cmake(xh.x * r.x - xh.y * r.y, xh.x * r.y + xh.y * r.x);   // 1/z = xh / (1 - r) = xh + xh*r + O(u^2)
+    cdd x;
+    x.re = dd_fast_two_sum(xh.x, xl.x);
+    x.im = dd_fast_two_sum(xh.y, xl.y);
+    return x;
+}
+// |z| <= 1, the branch of src/private/fnft__poly_eval.c:39.  KPolyEval and KPolyJoin decide it separately for the same
+// point and must agree (a forward partial joined as a reversed one is garbage): the norm is stated operation by
+// operation, one product and one FMA, so that no compiler choice can round it differently in the two kernels.  The same
+// holds for polyeval_point below: products and quotients only, and the library's sincos and exp.
+FA_DEV bool polyeval_inside(cplx z) { return fma(z.x, z.x, z.y * z.y) <= 1.0; }
+// acc * (w_hi + w_lo) + c
+FA_DEV cplx polyeval_step(cplx acc, cplx wh, cplx wl, cplx c)
+{
+    const double tx = fma(acc.x, wl.x, fma(-acc.y, wl.y, c.x));
+    const double ty = fma(acc.x, wl.y, fma(acc.y, wl.x, c.y));
+    return cmake(fma(acc.x, wh.x, fma(-acc.y, wh.y, tx)), fma(acc.x, wh.y, fma(acc.y, wh.x, ty)));
+}
+// sum a*b of a complex double and a two-double complex number, to double
+FA_DEV cplx polyeval_scale(cplx a, cdd b) { return polyeval_step(a, cdd_hi(b), cdd_lo(b), cmake(0.0, 0.0)); }
+
+struct PolyEvalParams {
+    const cplx *coef;        // polynomial j of signal b: coef + b*bstride + j*pstride, deg+1 coefficients, highest power first
+    long long pstride, bstride;
+    long long deg;
+    int npoly, batch;
+    const cplx *z;           // points of signal b: z + b*zstride (zstride 0: one list for all signals); NSE mode: lambda
+    long long zstride;
+    long long nz;
+    cplx *val, *der;         // [batch][npoly][nz]; der may be NULL (then the DERIV = false kernel runs)
+    int S;                   // segments of the coefficient range (grid.y of body_polyeval)
+    long long L;             // powers per segment, a multiple of the chain count
+    cplx *pp, *pd;           // [S][batch*npoly*nz]: P_s(x) and P_s'(x) (pd is not touched without derivative)
+    // NSE mode (fnft_amd_nsev_eval_device): z = exp(2i lambda eps_t / deg1) (fnft__akns_discretization.c:217), outputs per
+    // signal [a(nz) | b(nz)] or [a | b | a' | b'] in val (der only says that the derivative is wanted), a = H11(z) 2^W
+    // exp(i lambda pf[0]), b = H21(z) 2^W exp(i lambda pf[1])
+    int nse;
+    double eps_t, deg1;
+    const int *W;            // per signal
+    double pf[2];
+};
+FA_DEV cplx polyeval_point(const PolyEvalParams &P, long long b, long long i)
+{
+    const cplx v = P.z[b * P.zstride + i];
+    if (!P.nse) return v;
+    // CEXP(2*I*lambda*eps_t/deg1) in the reference's operation order
+    const double tr = 2.0 * v.x * P.eps_t / P.deg1, ti = 2.0 * v.y * P.eps_t / P.deg1;
+    double s, c;
+    fa_sincos(tr, &s, &c);
+    const double m = exp(-ti);
+    return cmake(m * c, m * s);
+}
+
+// p(x) = sum_r x^r P_r(x^NCH): NCH independent Horner chains per lane (and their derivatives), the coefficients staged
+// through LDS in tiles that the workgroup loads together, both orientations interleaved because both regimes occur
+// inside one wave.  grid.x = (signal, polynomial, block of THREADS points), grid.y = segment.
+template <int TILE, bool DERIV> FA_DEV void body_polyeval(const PolyEvalParams &P)
+{
+    constexpr int NCH = 8;
+    FA_LDS_DECL
+    cplx *tile = (cplx *)FA_LDS_PTR;
+    const long long nblk = (P.nz + FA_BDIM - 1) / FA_BDIM;
+    const long long job = (long long)FA_BID / nblk, blk = (long long)FA_BID % nblk;   // job = b*npoly + j
+    const long long b = job / P.npoly;
+    const cplx *coef = P.coef + b * P.bstride + (job % P.npoly) * P.pstride;
+    const long long i = blk * FA_BDIM + FA_TID;
+    const bool act = i < P.nz;
+    const bool wave_act = blk * FA_BDIM + (FA_TID & ~63) < P.nz;   // uniform over the wave
+    const long long n = P.deg;
+    const long long base = (long long)FA_BID_Y * P.L;   // lowest power of this segment
+    const cplx z = act ? polyeval_point(P, b, i) : cmake(0.5, 0.0);
+    const bool inside = polyeval_inside(z);
+    const cdd x = inside ? cdd_make(z) : cdd_recip(z);
+    cplx wh, wl;
+    {
+        const cdd x2 = cdd_mul(x, x), x4 = cdd_mul(x2, x2), w = cdd_mul(x4, x4);   // x^NCH
+        wh = cdd_hi(w);
+        wl = cdd_lo(w);
+    }
+    cplx pc[NCH], dc[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) { pc[c] = cmake(0.0, 0.0); dc[c] = cmake(0.0, 0.0); }
+    // local powers run from the top block (m = Mtop) down to m = 0; block m holds powers NCH*m .. NCH*m + NCH-1
+    const long long Mtop = P.L / NCH - 1;
+    for (long long mhi = Mtop; mhi >= 0; mhi -= TILE / NCH) {
+        const long long mlo = (mhi - TILE / NCH + 1 > 0) ? mhi - TILE / NCH + 1 : 0;
+        const long long kbase = base + NCH * mlo;     // lowest (global) power held by this tile
+        if (kbase > n) continue;                      // the whole tile lies above the leading coefficient (uniform)
+        FA_SYNC();
+        for (int t = FA_TID; t < TILE; t += FA_BDIM) {
+            const long long kk = kbase + t;
+            tile[2 * t] = (kk <= n) ? coef[n - kk] : cmake(0.0, 0.0);   // coefficient of z^kk
+            tile[2 * t + 1] = (kk <= n) ? coef[kk] : cmake(0.0, 0.0);   // coefficient of (1/z)^kk of the reversed polynomial
+        }
+        FA_SYNC();
+        if (!wave_act) continue;   // a wave without a point (the last block's tail) only helps to load the tiles
+        const int off = inside ? 0 : 1;
+        for (long long m = mhi; m >= mlo; m--) {
+            const int t = (int)(NCH * (m - mlo));
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                if (DERIV) dc[c] = polyeval_step(dc[c], wh, wl, pc[c]);
+                pc[c] = polyeval_step(pc[c], wh, wl, tile[2 * (t + c) + off]);
+            }
+        }
+    }
+    if (!act) return;
+    // p = sum_c x^c P_c;  p' = sum_c c x^(c-1) P_c + NCH x^(NCH-1) sum_c x^c P_c'
+    cdd xc = cdd_make(cmake(1.0, 0.0));   // x^(c-1)
+    cplx p = pc[0], dsum = dc[0], dp = cmake(0.0, 0.0);
+#pragma unroll
+    for (int c = 1; c < NCH; c++) {
+        if (DERIV) dp = dp + polyeval_scale(pc[c], xc) * (double)c;
+        xc = cdd_mul(xc, x);
+        p = p + polyeval_scale(pc[c], xc);
+        if (DERIV) dsum = dsum + polyeval_scale(dc[c], xc);
+    }
+    const long long o = ((long long)FA_BID_Y * P.batch * P.npoly + job) * P.nz + i;
+    P.pp[o] = p;
+    if (DERIV) P.pd[o] = dp + polyeval_scale(dsum, xc) * (double)NCH;
+}
+
+// Joins the segments of one point: Q(y) = sum_s P_s y^s at y = x^L (Horner in y), p = Q, dp/dx = sum_s y^s P_s' +
+// L x^(L-1) Q'(y); then the way back from x to z, and the NSE epilogue.  grid.x = (signal, polynomial, block of points).
+FA_DEV void body_polyjoin(const PolyEvalParams &P)
+{
+    const long long nblk = (P.nz + FA_BDIM - 1) / FA_BDIM;
+    const long long job = (long long)FA_BID / nblk, blk = (long long)FA_BID % nblk;
+    const long long b = job / P.npoly, j = job % P.npoly;
+    const long long i = blk * FA_BDIM + FA_TID;
+    if (i >= P.nz) return;
+    const bool deriv = P.der != nullptr;
+    const cplx z = polyeval_point(P, b, i);
+    const bool inside = polyeval_inside(z);
+    const cdd x = inside ? cdd_make(z) : cdd_recip(z);
+    const long long tot = (long long)P.batch * P.npoly * P.nz;
+    const long long o = job * P.nz + i;
+    cplx q = P.pp[o], d = deriv ? P.pd[o] : cmake(0.0, 0.0);
+    if (P.S > 1) {
+        const cdd xL1 = cdd_powi(x, P.L - 1), y = cdd_mul(xL1, x);
+        const cplx yh = cdd_hi(y), yl = cdd_lo(y);
+        cplx dq = cmake(0.0, 0.0);
+        q = cmake(0.0, 0.0);
+        d = cmake(0.0, 0.0);
+        // the partials of NJ segments are loaded together: taken one by one, every step of the chain waits for a load
+        // from HBM (a call with 8 points and 1024 segments spent three quarters of its time here)
+        constexpr int NJ = 8;
+        for (int g0 = P.S - 1; g0 >= 0; g0 -= NJ) {
+            cplx vp[NJ], vd[NJ];
+#pragma unroll
+            for (int u = 0; u < NJ; u++) {
+                const long long og = (long long)(g0 - u >= 0 ? g0 - u : 0) * tot + o;
+                vp[u] = P.pp[og];
+                vd[u] = deriv ? P.pd[og] : cmake(0.0, 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < NJ; u++) {
+                if (g0 - u < 0) break;
+                if (deriv) {
+                    dq = polyeval_step(dq, yh, yl, q);
+                    d = polyeval_step(d, yh, yl, vd[u]);
+                }
+                q = polyeval_step(q, yh, yl, vp[u]);
+            }
+        }
+        if (deriv) d = d + polyeval_scale(dq, xL1) * (double)P.L;
+    }
+    cplx val = q, der = d;
+    if (!inside) {
+        // p(z) = z^n q(x), p'(z) = z^(n-1) (n q(x) - x q'(x)), src/private/fnft__poly_eval.c:48, :86-87
+        const cdd zd = cdd_make(z);
+        const cdd zn1 = cdd_powi(zd, P.deg > 0 ? P.deg - 1 : 0);
+        const cdd zn = P.deg > 0 ? cdd_mul(zn1, zd) : zn1;
+        val = polyeval_scale(q, zn);
+        if (deriv) der = polyeval_scale(q * (double)P.deg - polyeval_scale(d, x), zn1);
+    }
+    if (!P.nse) {
+        P.val[o] = val;
+        if (deriv) P.der[o] = der;
+        return;
+    }
+    // E = exp(i lambda pf):  a = 2^W p(z) E,  da/dlambda = 2^W (p'(z) dz/dlambda + i pf p(z)) E,  dz/dlambda = (2i eps_t/deg1) z
+    const cplx lam = P.z[b * P.zstride + i];
+    const double pf = P.pf[j];
+    double s, c;
+    fa_sincos(lam.x * pf, &s, &c);
+    const double m = exp(-lam.y * pf);
+    const int W = P.W[b];
+    const cplx E = cmake(m * c, m * s);   // 2^W goes onto the product: the exponent of a long signal overflows on its own
+    cplx *out = P.val + b * (deriv ? 4 : 2) * P.nz;
+    const cplx a = val * E;
+    out[j * P.nz + i] = cmake(ldexp(a.x, W), ldexp(a.y, W));
+    if (deriv) {
+        const double k = 2.0 * P.eps_t / P.deg1;
+        const cplx zp = der * z;                                  // z p'(z)
+        const cplx t = cmake(-k * zp.y - pf * val.y, k * zp.x + pf * val.x);   // i (k z p' + pf p)
+        const cplx da = t * E;
+        out[(2 + j) * P.nz + i] = cmake(ldexp(da.x, W), ldexp(da.y, W));
+    }
+}

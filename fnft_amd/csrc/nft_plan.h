@@ -115,6 +115,70 @@ constexpr size_t kMaxSplitChirp = (size_t)kRowChirp * 8192;  // chirp length up 
 // fine tables of the two master twiddle pairs: 2^12 entries exp(-2 pi i j/2^24), then 2^13 entries exp(-2 pi i j/2^26)
 constexpr size_t kTwLoEntries = ((size_t)1 << kFineLog2) + ((size_t)1 << (kFineLog2 + 1));
 
+// ---- polynomials at arbitrary points (KPolyEval, KPolyJoin) ------------------------------------------------------------
+// Segments of the coefficient range: a call with few points and a long polynomial must still fill the chip.  One
+// workgroup takes 256 points of one polynomial; with G such workgroups, S = ceil(target / G) segments give the launch
+// `target` workgroups, as long as a segment keeps kPolyEvalMinSeg powers (two tiles: below that the tile loads and the
+// join cost more than the segment saves).  L = powers per segment, a multiple of the 8 chains.  force_S > 0: the tests'
+// choice of S (the last segment may be ragged or, for deg < L, the only one that holds coefficients).
+constexpr long long kPolyEvalMinSeg = 2 * kPolyEvalTile;
+struct PolyEvalSegs {
+    int S;
+    long long L;
+    bool ok;   // the grid fits the launch limits
+};
+inline PolyEvalSegs polyeval_segments(size_t deg, size_t nz, size_t jobs, size_t target, int force_S)
+{
+    const unsigned long long G = (unsigned long long)jobs * ((nz + 255) / 256);
+    const long long np = (long long)deg + 1;
+    long long S = force_S;
+    if (S <= 0) {
+        S = (long long)(((unsigned long long)target + G - 1) / (G ? G : 1));
+        const long long smax = (np + kPolyEvalMinSeg - 1) / kPolyEvalMinSeg;
+        if (S > smax) S = smax;
+        if (S < 1) S = 1;
+    }
+    long long L = ((np + S - 1) / S + 7) / 8 * 8;
+    if (force_S <= 0) S = (np + L - 1) / L;   // no segment without a coefficient
+    return PolyEvalSegs{(int)S, L, G >= 1 && G <= 0x7fffffffull && S <= 65535};
+}
+// Partials (per array) a plan keeps for calls of up to nz points: those of the most segments a call of nz OR FEWER points
+// can get -- S grows as the points fill fewer workgroups, and is largest where they fill one per polynomial.  Monotone
+// in nz, so a later call with the same or a smaller nz fits what an earlier one allocated.
+inline size_t polyeval_partials(size_t deg, size_t nz, size_t jobs, size_t target, int force_S)
+{
+    return (size_t)polyeval_segments(deg, 1, jobs, target, force_S).S * jobs * nz;
+}
+// the two launches; P.S, P.L, P.pp, P.pd are set by the caller (polyeval_segments, S*jobs*nz partials each)
+template <class BE> void polyeval_launch(BE &be, const PolyEvalParams &P)
+{
+    const int gx = (int)((long long)P.batch * P.npoly * ((P.nz + 255) / 256));
+    if (P.der) be.template run<KPolyEval<true>>(gx, P.S, P);
+    else be.template run<KPolyEval<false>>(gx, P.S, P);
+    be.template run<KPolyJoin>(gx, 1, P);
+}
+// fnft__poly_eval / fnft__poly_evalderiv on device arrays (fnft_amd_poly_eval_device): the partials come from a
+// temporary arena, so the stream is waited for once before they go back
+template <class BE>
+int polyeval_device(BE &be, size_t deg, size_t npoly, size_t batch, const cplx *d_p, size_t pstride, size_t bstride,
+                    size_t nz, const cplx *d_z, size_t zstride, cplx *d_val, cplx *d_deriv, int force_S = 0)
+{
+    const PolyEvalSegs sg = polyeval_segments(deg, nz, batch * npoly, BE::kTargetWorkgroups, force_S);
+    if (!sg.ok || batch > 0x7fffffff || npoly > 0x7fffffff) return NFT_EC_NOT_YET_IMPLEMENTED;
+    DevArena<BE> tmp(be);
+    PolyEvalParams P;
+    std::memset(&P, 0, sizeof(P));
+    const size_t part = (size_t)sg.S * batch * npoly * nz;
+    if (!tmp.get(P.pp, part) || (d_deriv && !tmp.get(P.pd, part))) return NFT_EC_NOMEM;
+    P.coef = d_p; P.pstride = (long long)pstride; P.bstride = (long long)bstride;
+    P.deg = (long long)deg; P.npoly = (int)npoly; P.batch = (int)batch;
+    P.z = d_z; P.zstride = (long long)zstride; P.nz = (long long)nz;
+    P.val = d_val; P.der = d_deriv;
+    P.S = sg.S; P.L = sg.L;
+    polyeval_launch(be, P);
+    return be.sync();   // before tmp hands the partials back to the pool
+}
+
 template <class BE> class NftPlan {
 public:
     BE &be;
@@ -131,6 +195,11 @@ public:
     int *wexp[2] = {nullptr, nullptr};  // per matrix, ping-pong with body/tail/scale
     int *status = nullptr;
     int *wuser = nullptr;   // exponents of caller-supplied transfer matrices (run_contspec_tm)
+    // fnft_amd_nsev_eval_device (run_eval): segment partials, grown lazily like wuser, and whether tm_out already holds the
+    // matrix of the last tree run (export_tm() without a destination; run_tree clears it)
+    cplx *evpp = nullptr, *evpd = nullptr;
+    size_t evpp_n = 0, evpd_n = 0;
+    bool tm_current = false;
     // monomial program of the order 5..8 schemes (nft_schemes.h), device copies
     double *prog_bfrac = nullptr, *prog_mw = nullptr;
     int *prog_ptr = nullptr;
@@ -762,6 +831,7 @@ public:
     {
         final_pending = false;   // an unconsumed root of an earlier run is dropped
         root_pending = false;
+        tm_current = false;
         if (real_run) return run_tree_real();
         size_t n = start_n;     // matrices at the current level, all signals
         size_t d = start_d;
@@ -860,6 +930,56 @@ public:
         E.real_layout = real_run ? 1 : 0;
         const long long tot = 4 * (E.deg + 1) * E.batch;
         be.template run<KExportTm>((int)((tot + 255) / 256), 1, E);
+        if (!dst) tm_current = true;
+    }
+
+    // ---- a(lambda), b(lambda) and their derivatives at arbitrary lambda (fnft_amd_nsev_eval_device) ---------------------
+    // Entries 11 and 21 of the last tree run's matrix by KPolyEval / KPolyJoin at z = exp(2i lambda eps_t/(deg0*ups))
+    // (fnft__akns_discretization.c:204-219), times 2^W exp(i lambda pf) with the phase factors of run_contspec_impl
+    // (fnft__nse_discretization.c:240-379).  T: the interval of the plan's input samples.  d_out per signal:
+    // [a(n) | b(n)], with derivative [a | b | da/dlambda | db/dlambda].  lambda_stride 0: one list for all signals.
+    int run_eval(const double T[2], int nse_disc, const cplx *d_lambda, size_t n, size_t lambda_stride, bool derivative,
+                 cplx *d_out, int force_S = 0)
+    {
+        if (!tree_valid || kdv) return NFT_EC_INVALID_ARGUMENT;
+        const PolyEvalSegs sg = polyeval_segments(res_deg, n, batch * 2, BE::kTargetWorkgroups, force_S);
+        if (!sg.ok) return NFT_EC_NOT_YET_IMPLEMENTED;
+        const size_t part = polyeval_partials(res_deg, n, batch * 2, BE::kTargetWorkgroups, force_S);   // >= S * batch * 2 * n
+        if (part > evpp_n || (derivative && part > evpd_n)) be.sync();   // queued kernels may still use what goes back
+        if (part > evpp_n) {
+            mem.give_back(evpp);
+            evpp_n = 0;
+            if (!mem.get(evpp, part)) return NFT_EC_NOMEM;
+            evpp_n = part;
+        }
+        if (derivative && part > evpd_n) {
+            mem.give_back(evpd);
+            evpd_n = 0;
+            if (!mem.get(evpd, part)) return NFT_EC_NOMEM;
+            evpd_n = part;
+        }
+        if (!tm_current) export_tm();   // ensure_root() and the export, once per tree run
+        const double deg1 = (double)(deg0 * ups);
+        const size_t Dg = D / (size_t)ups;
+        // the interval of the kept steps as run_front hands it to run_contspec (nskip = 1 here)
+        const double T1 = (ups == 1) ? T[1] : T[0] + (double)(Dg - 1) * ((T[1] - T[0]) / (double)(Din - 1));
+        const double eps_t = (T1 - T[0]) / (double)(Dg - 1);
+        const double bc = 0.5;
+        const bool shifted = (nse_disc == 0 /*MODAL*/ || nse_disc == 4 /*2SPLIT2A*/);
+        PolyEvalParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.coef = tm_out;
+        P.pstride = (long long)(2 * (res_deg + 1));   // [r11|r12|r21|r22]: entries 11 and 21
+        P.bstride = (long long)(4 * (res_deg + 1));
+        P.deg = (long long)res_deg; P.npoly = 2; P.batch = (int)batch;
+        P.z = d_lambda; P.zstride = (long long)lambda_stride; P.nz = (long long)n;
+        P.val = d_out; P.der = derivative ? d_out : nullptr;
+        P.S = sg.S; P.L = sg.L; P.pp = evpp; P.pd = evpd;
+        P.nse = 1; P.eps_t = eps_t; P.deg1 = deg1; P.W = wexp[cur];
+        P.pf[0] = -eps_t * (double)Dg + (T1 + eps_t * bc) - (T[0] - eps_t * bc);
+        P.pf[1] = -eps_t * (double)Dg - (T1 + eps_t * bc) - (T[0] - eps_t * bc) + (shifted ? eps_t / deg1 : 0.0);
+        polyeval_launch(be, P);
+        return NFT_SUCCESS;
     }
 
     // ---- chirp z + epilogue (fnft_nsev.c:744-891) ----------------------------------------------

@@ -296,6 +296,15 @@ FNFT_INT fnft_amd_poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p,
 FNFT_INT fnft__poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_COMPLEX A,
                            const FNFT_COMPLEX W, const FNFT_UINT M, FNFT_COMPLEX *const result);
 
+/* include/private/fnft__poly_eval.h:43-44 and :66-68 (src/private/fnft__poly_eval.c:25-53, :55-91): the polynomial
+ * p[0] z^deg + ... + p[deg] at the nz points z, IN PLACE (z[i] becomes p(z[i])); fnft__poly_evalderiv also stores p'(z[i])
+ * in deriv[i].  Horner in z where |z| <= 1, Horner of the reversed polynomial in 1/z and the power z^deg where |z| > 1
+ * (:44-48, :79-87).  Host buffers, computed on the current device.  p == NULL or z == NULL: FNFT_EC_INVALID_ARGUMENT,
+ * raised with the argument's name like the reference (:32-35); nz == 0: success; both before any HIP call. */
+FNFT_INT fnft__poly_eval(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z);
+FNFT_INT fnft__poly_evalderiv(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z,
+                              FNFT_COMPLEX *const deriv);
+
 /* include/private/fnft__misc.h:241-242 (src/private/fnft__misc.c:326-407): q_new = q shifted by delta on the
  * periodically continued, band-limited grid (the 4SPLIT4A/B front end).  Host buffers of D samples, D > 2. */
 FNFT_INT fnft__misc_resample(const FNFT_UINT D, const FNFT_REAL eps_t, FNFT_COMPLEX const *const q,
@@ -388,6 +397,16 @@ FNFT_INT fnft_amd_plan_create(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT M, 
  * root's step of a sample-axis split: the block matrices arrive by RCCL and never visit the host. */
 FNFT_INT fnft_amd_poly_fmult2x2_device(FNFT_UINT deg, FNFT_UINT n, const void *d_p, void *d_result, FNFT_UINT *deg_out,
                                        FNFT_INT *W_out, void *stream);
+/* fnft__poly_eval / fnft__poly_evalderiv (src/private/fnft__poly_eval.c:25-91) on DEVICE buffers, batched: npoly
+ * polynomials of degree deg per signal -- polynomial j of signal b starts at d_p + b*bstride + j*pstride (complex128,
+ * deg+1 coefficients, highest power first; pstride >= deg+1) -- at nz complex points per signal, d_z + b*zstride;
+ * zstride = 0 means one point list shared by all signals, zstride >= nz per-signal lists.  d_val receives
+ * [batch][npoly][nz] values, d_deriv (may be NULL) the derivatives in the same layout; d_z is not modified.  Runs on
+ * `stream` of the calling thread's current device.  The segment partials are pooled scratch that must not go back to the
+ * pool while the kernels that use it are queued, so the call waits for the stream once before it returns. */
+FNFT_INT fnft_amd_poly_eval_device(FNFT_UINT deg, FNFT_UINT npoly, FNFT_UINT batch, const void *d_p, FNFT_UINT pstride,
+                                   FNFT_UINT bstride, FNFT_UINT nz, const void *d_z, FNFT_UINT zstride, void *d_val,
+                                   void *d_deriv, void *stream);
 /* same, for the second (coarse) transform of Richardson extrapolation with 4SPLIT4A/B: the
  * transform uses every nskip-th step of the D samples; the band-limited resampling of
  * fnft__nse_discretization_preprocess_signal (src/private/fnft__nse_discretization.c:474-503)
@@ -419,6 +438,27 @@ FNFT_INT fnft_amd_nsev_contspec_device(fnft_amd_plan_t *plan, const void *d_q, v
                                        fnft_nsev_cstype_t contspec_type,
                                        FNFT_INT normalization_flag, void *stream);
 FNFT_INT fnft_amd_plan_finish(fnft_amd_plan_t *plan, void *stream);
+
+/* The NSE spectrum at ARBITRARY lambda: a(lambda), b(lambda) and optionally their derivatives at n complex points per
+ * signal, from the transfer matrix of the plan's LAST tree run -- call fnft_amd_nsev_contspec_device first (with a
+ * spectrum, or with d_contspec = NULL on an M = 0 plan); T is the interval passed to it.  Entries 11 and 21 are evaluated
+ * (fnft__poly_eval semantics, src/private/fnft__poly_eval.c:25-91) at z = exp(2i lambda eps_t/(deg0*ups))
+ * (fnft__akns_discretization_lambda_to_z, src/private/fnft__akns_discretization.c:204-219):
+ *   a = H11(z) 2^W exp(i lambda pf_a),  b = H21(z) 2^W exp(i lambda pf_b)
+ * with the phase factors of the continuous spectrum (src/private/fnft__nse_discretization.c:240-379), so that on a real
+ * equispaced grid the result is the plan's contspec of type AB up to rounding.  d_lambda: complex128, signal b's points
+ * at d_lambda + b*lambda_stride (0: one list for all signals, otherwise >= n).  d_out per signal: [a(n) | b(n)], or with
+ * derivative_flag != 0 [a | b | da/dlambda | db/dlambda] (the flag of fnft__nse_scatter_matrix).  rho = b/a is left to
+ * the caller, so no status is raised.  All 21 fast schemes and both kappa.
+ * Before anything is enqueued: FNFT_EC_INVALID_ARGUMENT for a NULL plan, T, d_lambda or d_out, T[0] >= T[1] or a
+ * lambda_stride in [1, n); -FNFT_EC_INVALID_ARGUMENT for a KdV plan or a plan without a valid tree run;
+ * FNFT_EC_NOT_YET_IMPLEMENTED for a fnft_amd_plan_create_sub plan with nskip > 1; n == 0 is success.
+ * Asynchronous on `stream` like fnft_amd_nsev_contspec_device; fnft_amd_plan_finish waits.  The segment partials grow
+ * lazily in the plan's workspace, sized for the most segments a call of n or fewer points can be cut into: a later call
+ * with the same or a smaller n (and no more derivative than before) allocates nothing and stays asynchronous; a call
+ * that has to grow them waits for the stream first.  The matrix is exported at most once per tree run. */
+FNFT_INT fnft_amd_nsev_eval_device(fnft_amd_plan_t *plan, const FNFT_REAL *T, const void *d_lambda, FNFT_UINT n,
+                                   FNFT_UINT lambda_stride, FNFT_INT derivative_flag, void *d_out, void *stream);
 
 /* nsev_compute_contspec (src/fnft_nsev.c:744-891) alone: continuous spectrum from a transfer matrix the caller
  * holds in DEVICE memory -- per signal [r11|r12|r21|r22], each D*deg0+1 complex128, highest power first (the
