@@ -720,12 +720,24 @@ def kdv_fscatter(u, eps_t, discretization, normalize=True):
     return int(rc), dd, res[: 4 * (dd + 1)].reshape(4, dd + 1).copy(), int(W.value)
 
 
-class _TreePlan:
-    """What Plan and KdvvPlan share: self.h is a fnft_amd_plan_t of the library self.L."""
+class _BatchPlan:
+    """What every device-resident plan shares: self.h is the plan of the library self.L, made by _create and given
+    back by close; _DESTROY and _FINISH (the three batched plans: per-signal status words) name its entries."""
+    _DESTROY = _FINISH = None
+
+    def _create(self, fn, *args, name=None):
+        """self.h = the plan made by the entry `fn`, or RuntimeError (in the name of `name`, default fn) with the
+        entry's code in its attribute rc."""
+        self.h = C.c_void_p()
+        rc = getattr(self.L, fn)(C.byref(self.h), *args)
+        if rc != FNFT_SUCCESS:
+            err = RuntimeError("%s rc=%d (%s)" % (name or fn, rc, last_error()))
+            err.rc = int(rc)
+            raise err
 
     def close(self):
         if self.h:
-            self.L.fnft_amd_plan_destroy(self.h)
+            getattr(self.L, self._DESTROY)(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -733,6 +745,18 @@ class _TreePlan:
             self.close()
         except Exception:
             pass
+
+    def _finish(self, stream, second=np.int32):
+        """(rc, status[batch], second per-signal array[batch]) once `stream` is done."""
+        st = np.zeros(self.batch, np.int32)
+        x = np.zeros(self.batch, second)
+        rc = getattr(self.L, self._FINISH)(self.h, C.c_void_p(stream), _ptr(st), _ptr(x))
+        return int(rc), st, x
+
+
+class _TreePlan(_BatchPlan):
+    """What Plan and KdvvPlan share: self.h is a fnft_amd_plan_t of the library self.L."""
+    _DESTROY = "fnft_amd_plan_destroy"
 
     def set_timing(self, on=True):
         self.L.fnft_amd_plan_set_timing(self.h, 1 if on else 0)
@@ -763,10 +787,7 @@ class KdvvPlan(_TreePlan):
         self.L = load()
         self.D, self.M, self.batch = int(D), int(M), int(batch)
         self.disc = KDV_DISC[discretization] if isinstance(discretization, str) else int(discretization)
-        self.h = C.c_void_p()
-        rc = self.L.fnft_amd_kdvv_plan_create(C.byref(self.h), self.D, self.M, self.batch, self.disc, int(device))
-        if rc != FNFT_SUCCESS:
-            raise RuntimeError("fnft_amd_kdvv_plan_create rc=%d (%s)" % (rc, last_error()))
+        self._create("fnft_amd_kdvv_plan_create", self.D, self.M, self.batch, self.disc, int(device))
 
     def set_real_mode(self, mode):
         """-1: ask the device whether u is real (default); 1: u is real (real-coefficient tree); 0: complex tree."""
@@ -787,11 +808,8 @@ class Plan(_TreePlan):
         self.L = load()
         self.D, self.M, self.batch = int(D), int(M), int(batch)
         self.disc = NSE_DISC[discretization] if isinstance(discretization, str) else int(discretization)
-        self.h = C.c_void_p()
-        rc = self.L.fnft_amd_plan_create_sub(C.byref(self.h), self.D, self.M, self.batch, self.disc,
-                                             int(device), int(nskip))
-        if rc != FNFT_SUCCESS:
-            raise RuntimeError("fnft_amd_plan_create rc=%d (%s)" % (rc, last_error()))
+        self._create("fnft_amd_plan_create_sub", self.D, self.M, self.batch, self.disc, int(device), int(nskip),
+                     name="fnft_amd_plan_create")
 
     @property
     def workspace_bytes(self):
@@ -859,39 +877,6 @@ class Plan(_TreePlan):
         rc = self.L.fnft_amd_plan_get_transfer_matrix(self.h, b, _ptr(buf), C.byref(deg), C.byref(W))
         d = deg.value
         return int(rc), d, buf[: 4 * (d + 1)].reshape(4, d + 1).copy(), int(W.value)
-
-
-class _BatchPlan:
-    """What InversePlan, DiscSpecPlan and SlowPlan share: self.h is the plan of the library self.L, _DESTROY and
-    _FINISH name its entries."""
-    _DESTROY = _FINISH = None
-
-    def _create(self, fn, *args):
-        """self.h = the plan made by the entry `fn`, or RuntimeError with the entry's code in its attribute rc."""
-        self.h = C.c_void_p()
-        rc = getattr(self.L, fn)(C.byref(self.h), *args)
-        if rc != FNFT_SUCCESS:
-            err = RuntimeError("%s rc=%d (%s)" % (fn, rc, last_error()))
-            err.rc = int(rc)
-            raise err
-
-    def close(self):
-        if self.h:
-            getattr(self.L, self._DESTROY)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _finish(self, stream, second=np.int32):
-        """(rc, status[batch], second per-signal array[batch]) once `stream` is done."""
-        st = np.zeros(self.batch, np.int32)
-        x = np.zeros(self.batch, second)
-        rc = getattr(self.L, self._FINISH)(self.h, C.c_void_p(stream), _ptr(st), _ptr(x))
-        return int(rc), st, x
 
 
 class InversePlan(_BatchPlan):

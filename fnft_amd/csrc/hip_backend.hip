@@ -1,6 +1,12 @@
 // hip_backend.hip -- the HIP side of libfnft_amd.so: the extern "C" shim (sections 2 and 3 of
-// include/fnft_amd.h plus the internal entries the C drivers call) over NftPlan<HipBackend>.  The kernels
-// are instantiated in hip_kernels_*.hip (see hip_be.h).  gfx950 only.
+// include/fnft_amd.h plus the internal entries the C drivers call) over NftPlan<HipBackend> and the batched cores.  The
+// kernels are instantiated in hip_kernels_*.hip (see hip_be.h).  gfx950 only.
+// Every entry makes its call in one of two ways, and the rules of DESIGN.md ("The shim") hold by their construction:
+//   - on a plan (the tree plan and the three batched plans share PlanHandle): PlanCall takes the plan's lock, selects
+//     its device and sets its stream -- one call at a time per plan; batch_destroy waits for the last stream;
+//   - on host pointers: HostCall finds the current device, takes that device's lock where the entry shares state
+//     (HostState: the cached plans, the peeler) and owns the back end; the entry returns through done(), which waits
+//     for the stream on a failing branch before the entry's plans and arenas hand their blocks back to the pool.
 #include <map>
 #include <memory>
 #include <mutex>
@@ -8,6 +14,7 @@
 
 #include "hip_be.h"
 #include "nft_nsev_inverse.h"
+#include "nft_plan_cache.h"
 #include "../../include/fnft_amd.h"
 
 thread_local std::string g_last_error;
@@ -16,21 +23,6 @@ extern "C" void fnft_amd__warn(const char *msg, const char *func, int line);   /
 static const char *const kNotBandlimitedMsg =
     "Signal does not appear to be bandlimited. Interpolation step may be inaccurate. Try to reduce the step size, "
     "or switch to a discretization that does not require interpolation";
-// Host-pointer entry points share cached plans and workspaces PER DEVICE: one call at a time on a device (SURVEY 8b
-// allows an internal mutex), calls on different devices run concurrently; device-resident plans are independent
-// objects with their own lock.
-static std::mutex &host_call_mutex_of(int d)
-{
-    static std::mutex m[64];
-    return m[(unsigned)d % 64u];
-}
-static std::mutex &host_call_mutex()
-{
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess) d = 0;
-    return host_call_mutex_of(d);
-}
-
 using Plan = NftPlan<HipBackend>;
 
 // ---- cache of released device blocks (HipBackend::alloc / free) ------------------------------------------------------
@@ -104,16 +96,6 @@ void fa_pool_free(void *p)
     P.cached += key.second;
 }
 
-struct fnft_amd_plan {
-    HipBackend be;
-    std::unique_ptr<Plan> pl;   // after be: its arena hands the blocks back through be
-    int device = 0;
-    int nse_disc = 0;
-    int kdv_disc = -1;   // >= 0: plan made by fnft_amd_kdvv_plan_create
-    int real_mode = -1;  // KdV plans: -1 ask the device whether the potential is real (default), 0 complex path, 1 real path
-    std::mutex mtx;
-};
-
 // Device rule of the library (documented in include/fnft_amd.h): the host-pointer entry points
 // compute on the calling thread's CURRENT HIP device (hipGetDevice; what torch.cuda.set_device or
 // hipSetDevice selected) and never change it; device-resident plans live on the device given to
@@ -158,23 +140,12 @@ struct DeviceGuard {
     }
 };
 
-// state the host-pointer entry points keep between calls, per device (fnft_amd_release_cached gives it back)
-struct Peeler {
-    HipBackend be;
-    NftLayerPeelingDev<HipBackend> lp;
-    Peeler() : lp(be, 1.0, 1, 1) {}
-};
-static std::map<int, Peeler *> g_peelers;
-static std::mutex g_peelers_mtx;   // the map itself; a device's peeler is used under that device's host-call lock
-static std::mutex g_cache_mtx;     // the two plan caches below
-static std::map<std::tuple<int, size_t, size_t, int, size_t>, fnft_amd_plan *> g_nsev_cache;   // (dev, D, M, disc, nskip)
-static std::map<std::tuple<int, size_t, size_t, int>, fnft_amd_plan *> g_kdvv_cache;           // (dev, D, M, disc)
-
-// ---- the parts of the three batched plans' entry points that do not depend on the plan ---------------------------------
-// One handle for the three batched plans: the back end, the plan core (NftInverseBatch, NftDiscSpecBatch,
-// NftSlowPlan), the device it lives on, the stream of its last call (destroy waits for it), the status words finish
-// reads back, and the lock that makes calls on one plan take turns.  The public opaque types add their few own fields.
-template <class CoreT> struct BatchHandle {
+// ---- the parts of the plans' entry points that do not depend on the plan -----------------------------------------------
+// One handle for the tree plan and the three batched plans: the back end, the plan core (NftPlan, NftInverseBatch,
+// NftDiscSpecBatch, NftSlowPlan), the device it lives on, the stream of its last call (destroy waits for it), the status
+// words finish reads back, and the lock that makes calls on one plan take turns.  The public opaque types add their few
+// own fields.
+template <class CoreT> struct PlanHandle {
     typedef CoreT Core;
     HipBackend be;
     std::unique_ptr<Core> core;   // after be: its arenas hand the blocks back through be
@@ -183,18 +154,23 @@ template <class CoreT> struct BatchHandle {
     std::vector<int> st;
     std::mutex mtx;
 };
-struct fnft_amd_inverse_plan : BatchHandle<NftInverseBatch<HipBackend>> {
+struct fnft_amd_plan : PlanHandle<Plan> {
+    int nse_disc = 0;
+    int kdv_disc = -1;   // >= 0: plan made by fnft_amd_kdvv_plan_create
+    int real_mode = -1;  // KdV plans: -1 ask the device whether the potential is real (default), 0 complex path, 1 real path
+};
+struct fnft_amd_inverse_plan : PlanHandle<NftInverseBatch<HipBackend>> {
     int cstype = 0;
     size_t K = 0;                 // fnft_amd_inverse_plan_create_discrete: bound states per signal (>= 1)
 };
-struct fnft_amd_discspec_plan : BatchHandle<NftDiscSpecBatch<HipBackend>> {
+struct fnft_amd_discspec_plan : PlanHandle<NftDiscSpecBatch<HipBackend>> {
     const unsigned long long *last_K = nullptr;   // d_K_out of the last call
     std::vector<unsigned long long> kout;
     // fnft_amd_discspec_search_plan_create: the guess-free plan in place of `core` (it owns its own NftDiscSpecBatch)
     std::unique_ptr<NftDiscSpecSearch<HipBackend>> search;
     std::vector<int> wn;                          // its warning bits, read by finish
 };
-struct fnft_amd_slow_plan : BatchHandle<NftSlowPlan<HipBackend>> {
+struct fnft_amd_slow_plan : PlanHandle<NftSlowPlan<HipBackend>> {
     std::vector<int> wn;
 };
 
@@ -216,8 +192,8 @@ template <class H> static FNFT_INT batch_init(H **plan, std::unique_ptr<H> h, in
     if (!dg.ok) return FNFT_EC_OTHER;
     h->device = device;
     const int rc = h->core->init();
+    (void)h->be.sync();           // what init enqueued is done before a call arrives on another stream, or the core goes
     if (rc != NFT_SUCCESS || h->be.failed) {
-        (void)h->be.sync();
         h.reset();                // on the plan's device
         return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
     }
@@ -244,13 +220,14 @@ template <class H> static void batch_destroy(H *plan)
 }
 
 // one call on a plan: its lock, its device, its stream.  last_stream != NULL (the *_device entries): the stream is also
-// the one destroy waits for, and the failure flag starts clear
+// the one destroy waits for, and the failure flag starts clear.  Without a stream (a setting, or a read that belongs on
+// the stream of the call before it) the plan's stream stays what it is.
 struct PlanCall {
     std::lock_guard<std::mutex> lk;
     DeviceGuard dg;
     const bool ok;
-    PlanCall(std::mutex &m, int device, HipBackend &be, hipStream_t *last_stream, void *stream)
-        : lk(m), dg(device), ok(dg.ok)
+    PlanCall(std::mutex &m, int device) : lk(m), dg(device), ok(dg.ok) {}
+    PlanCall(std::mutex &m, int device, HipBackend &be, hipStream_t *last_stream, void *stream) : PlanCall(m, device)
     {
         if (!ok) return;
         be.stream = (hipStream_t)stream;
@@ -279,6 +256,73 @@ static FNFT_INT batch_finish(H *plan, void *stream, FNFT_INT *status, Read read,
     return first;
 }
 
+// ---- host-pointer entry points: what they keep between calls, and how they make a call ----------------------------------
+// They compute on the calling thread's current device.  What they keep there between calls is that device's alone: the
+// lock that makes the calls sharing it take turns (SURVEY 8b allows an internal mutex; calls on different devices run
+// concurrently), the plans of fnft_nsev and fnft_kdvv by size and scheme, and the resident layer peeler.  Device-resident
+// plans are the caller's, with their own lock.  fnft_amd_release_cached empties a device's state.
+struct Peeler {
+    HipBackend be;
+    NftLayerPeelingDev<HipBackend> lp;
+    Peeler() : lp(be, 1.0, 1, 1) {}
+};
+struct HostState {
+    std::mutex mtx;
+    PlanCache<std::tuple<size_t, size_t, int, size_t>, fnft_amd_plan, fnft_amd_plan_destroy> nsev;   // (D, M, disc, nskip)
+    PlanCache<std::tuple<size_t, size_t, int>, fnft_amd_plan, fnft_amd_plan_destroy> kdvv;           // (D, M, disc)
+    Peeler peeler;
+};
+static HostState &host_state(int device)
+{
+    static auto *r = new DeviceRegistry<HostState>();   // never destroyed: plans outlive static teardown, like the pool
+    return r->of(device);
+}
+
+// a call that failed may have left work queued on its stream: wait for it, so that the plans and arenas of the call hand
+// their blocks back to the pool from an idle stream.  A call that succeeded has waited already and gains nothing here.
+static FNFT_INT drained(HipBackend &be, FNFT_INT rc)
+{
+    if (rc != FNFT_SUCCESS || be.failed) (void)hipStreamSynchronize(be.stream);
+    return be.failed ? FNFT_EC_OTHER : rc;
+}
+
+// one host-pointer call: the current device (!ok: none), its lock unless the entry shares nothing (kNoLock: it builds its
+// plan, runs it and lets it go), and the back end.  Every entry returns through done(rc); its plans and arenas are
+// declared after the HostCall, so they are destroyed after the return expression has drained the stream.
+struct HostCall {
+    enum Lock { kLock, kNoLock };
+    const int dev;
+    const bool ok;
+    HostState *const hs;
+    std::unique_lock<std::mutex> lk;
+    HipBackend be;
+    explicit HostCall(Lock lock = kLock, void *stream = nullptr)
+        : dev(current_device()), ok(dev >= 0), hs(ok && lock == kLock ? &host_state(dev) : nullptr)
+    {
+        if (hs) lk = std::unique_lock<std::mutex>(hs->mtx);
+        be.stream = (hipStream_t)stream;
+    }
+    FNFT_INT done(FNFT_INT rc) { return drained(be, rc); }
+};
+
+// a cached plan's pass over host arrays: two staging blocks from the pool, the n_in values in, run(d_in, d_out), the
+// n_out values out (out NULL: none).  The caller's arrays are ordinary pageable memory: hipMemcpy moves them at the link
+// rate once their pages are resident.
+template <class Run>
+static FNFT_INT staged_run(HostCall &call, const void *in, size_t n_in, void *out, size_t n_out, Run run)
+{
+    DevArena<HipBackend> tmp(call.be);
+    cplx *d_in = nullptr, *d_out = nullptr;
+    if (!tmp.get(d_in, n_in) || !tmp.get(d_out, n_out)) return call.done(FNFT_EC_NOMEM);
+    FNFT_INT rc = FNFT_SUCCESS;
+    if (!hip_ok(hipMemcpy(d_in, in, n_in * sizeof(cplx), hipMemcpyHostToDevice), "hipMemcpy(H2D)")) rc = FNFT_EC_OTHER;
+    if (rc == FNFT_SUCCESS) rc = run(d_in, d_out);
+    if (rc == FNFT_SUCCESS && out && n_out)
+        if (!hip_ok(hipMemcpy(out, d_out, n_out * sizeof(cplx), hipMemcpyDeviceToHost), "hipMemcpy(D2H)"))
+            rc = FNFT_EC_OTHER;
+    return call.done(rc);
+}
+
 extern "C" {
 
 int fnft_amd_device_count(void)
@@ -305,44 +349,25 @@ FNFT_INT fnft_amd_plan_create_sub(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT
     const int ups = nft_nse_upsampling((int)discretization);
     if (ups == 1 && nskip != 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
     if (ups == 2 && D <= 2) return FNFT_EC_INVALID_ARGUMENT;   // fnft__misc.c:331-332
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    fnft_amd_plan *P = new (std::nothrow) fnft_amd_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->device = device;
-    P->nse_disc = (int)discretization;
     const size_t Dtree = (ups == 1) ? (size_t)D : 2 * Plan::sub_count((size_t)D, (size_t)nskip);
-    P->pl.reset(new (std::nothrow) Plan(P->be, Dtree, M, batch, akns, nft_akns_degree(akns)));
-    if (!P->pl) { delete P; return FNFT_EC_NOMEM; }
-    P->pl->set_front((size_t)D, (size_t)nskip, ups);
+    auto h = batch_new<fnft_amd_plan>(Dtree, (size_t)M, (size_t)batch, akns, nft_akns_degree(akns));
+    if (h) {
+        h->nse_disc = (int)discretization;
+        h->core->set_front((size_t)D, (size_t)nskip, ups);
 #ifdef FNFT_AMD_ABLATION   // diagnostic builds only; the product library reads no environment variable
-    if (const char *dbg = getenv("FNFT_AMD_DBG")) P->pl->dbg_flags = atoi(dbg);
+        if (const char *dbg = getenv("FNFT_AMD_DBG")) h->core->dbg_flags = atoi(dbg);
 #endif
-    const int rc = P->pl->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
     }
-    (void)P->be.sync();
-    *plan = P;
-    return FNFT_SUCCESS;
+    return batch_init(plan, std::move(h), device);
 }
 
-void fnft_amd_plan_destroy(fnft_amd_plan_t *plan)
-{
-    if (!plan) return;
-    DeviceGuard dg(plan->device);
-    (void)hipDeviceSynchronize();
-    plan->pl.reset();
-    plan->be.destroy_events();
-    delete plan;
-}
+void fnft_amd_plan_destroy(fnft_amd_plan_t *plan) { batch_destroy(plan); }
 
-FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->pl->mem.bytes : 0; }
+FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->core->mem.bytes : 0; }
 
 int fnft_amd_plan_device(const fnft_amd_plan_t *plan) { return plan ? plan->device : -1; }
 
-int fnft_amd_plan_last_warnings(const fnft_amd_plan_t *plan) { return plan ? plan->pl->last_warn : 0; }
+int fnft_amd_plan_last_warnings(const fnft_amd_plan_t *plan) { return plan ? plan->core->last_warn : 0; }
 
 // host wall-clock stages of the calling thread's last discrete-spectrum call (measurement only)
 double fnft_amd_discspec_stage_ms(FNFT_UINT i, char *name, FNFT_UINT name_cap)
@@ -363,8 +388,9 @@ double fnft_amd_discspec_stage_ms(FNFT_UINT i, char *name, FNFT_UINT name_cap)
 extern "C" int fnft_amd_debug_root_handover(fnft_amd_plan_t *plan, int enabled)
 {
     if (!plan) return -1;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    plan->pl->tune_fuse_root = enabled ? 1 : 0;
+    PlanCall call(plan->mtx, plan->device);
+    if (!call.ok) return FNFT_EC_OTHER;
+    plan->core->tune_fuse_root = enabled ? 1 : 0;
     return 0;
 }
 
@@ -373,7 +399,7 @@ extern "C" int fnft_amd_debug_root_handover(fnft_amd_plan_t *plan, int enabled)
 extern "C" int fnft_amd_debug_tune(fnft_amd_plan_t *plan, int which, int value)
 {
     if (!plan) return -1;
-    if (which == 0) plan->pl->tune_stagger = value;
+    if (which == 0) plan->core->tune_stagger = value;
     return 0;
 }
 #endif
@@ -385,7 +411,7 @@ extern "C" int fnft_amd_debug_stamps(fnft_amd_plan_t *plan, int level, unsigned 
 {
     if (!plan) return -1;
     DeviceGuard dg(plan->device);
-    Plan &pl = *plan->pl;
+    Plan &pl = *plan->core;
     if (!pl.dbg_stamps) {
         if (!pl.mem.get(pl.dbg_stamps, (size_t)4096 * 16)) return -1;
         (void)hipMemset(pl.dbg_stamps, 0, (size_t)4096 * 16 * 8);
@@ -464,12 +490,9 @@ FNFT_INT fnft_amd_nsev_contspec_device(fnft_amd_plan_t *plan, const void *d_q, v
     if (kappa != 1 && kappa != -1) return FNFT_EC_INVALID_ARGUMENT;
     const int cst = (int)contspec_type;
     if (cst < 0 || cst > 2) return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    Plan &pl = *plan->pl;
-    plan->be.stream = (hipStream_t)stream;
-    plan->be.failed = false;
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
     plan->be.mark(0);
     double Tsub[2];
     int rc = pl.run_front(d_q, T, kappa, Tsub);
@@ -496,13 +519,10 @@ FNFT_INT fnft_amd_nsev_contspec_from_tm_device(fnft_amd_plan_t *plan, const void
     if (!plan || plan->kdv_disc >= 0 || !d_tm || !d_contspec || !T || !(T[0] < T[1]) || !XI || !(XI[0] < XI[1]))
         return FNFT_EC_INVALID_ARGUMENT;
     const int cst = (int)contspec_type;
-    if (cst < 0 || cst > 2 || plan->pl->M == 0) return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    Plan &pl = *plan->pl;
-    plan->be.stream = (hipStream_t)stream;
-    plan->be.failed = false;
+    if (cst < 0 || cst > 2 || plan->core->M == 0) return FNFT_EC_INVALID_ARGUMENT;
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
     Plan::Contspec cs;
     cs.T[0] = T[0]; cs.T[1] = T[1]; cs.XI[0] = XI[0]; cs.XI[1] = XI[1];
     cs.nse_disc = plan->nse_disc;
@@ -519,15 +539,12 @@ FNFT_INT fnft_amd_nsev_eval_device(fnft_amd_plan_t *plan, const FNFT_REAL *T, co
 {
     if (!plan || !T || !d_lambda || !d_out || !(T[0] < T[1]) || (lambda_stride != 0 && lambda_stride < n))
         return FNFT_EC_INVALID_ARGUMENT;
-    if (plan->kdv_disc >= 0 || !plan->pl->tree_valid) return -FNFT_EC_INVALID_ARGUMENT;
-    if (plan->pl->nskip > 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
+    if (plan->kdv_disc >= 0 || !plan->core->tree_valid) return -FNFT_EC_INVALID_ARGUMENT;
+    if (plan->core->nskip > 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
     if (n == 0) return FNFT_SUCCESS;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    Plan &pl = *plan->pl;
-    plan->be.stream = (hipStream_t)stream;
-    plan->be.failed = false;
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
     const int rc = pl.run_eval(T, plan->nse_disc, (const cplx *)d_lambda, n, lambda_stride, derivative_flag != 0,
                                (cplx *)d_out);
     if (plan->be.failed) return FNFT_EC_OTHER;
@@ -543,24 +560,13 @@ FNFT_INT fnft_amd_kdvv_plan_create(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UIN
     if (kd < 0) return FNFT_EC_INVALID_ARGUMENT;
     if (kd > (int)fnft_kdv_discretization_2SPLIT8B) return FNFT_EC_NOT_YET_IMPLEMENTED;
     const int akns = kd + 1;   // same scheme names, fnft__kdv_discretization.c:86-150
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    fnft_amd_plan *P = new (std::nothrow) fnft_amd_plan();
-    if (!P) return FNFT_EC_NOMEM;
-    P->device = device;
-    P->nse_disc = -1;
-    P->kdv_disc = kd;
-    P->pl.reset(new (std::nothrow) Plan(P->be, D, M, batch, akns, nft_akns_degree(akns)));
-    if (!P->pl) { delete P; return FNFT_EC_NOMEM; }
-    P->pl->kdv = true;
-    const int rc = P->pl->init();
-    if (rc != NFT_SUCCESS || P->be.failed) {
-        delete P;
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
+    auto h = batch_new<fnft_amd_plan>((size_t)D, (size_t)M, (size_t)batch, akns, nft_akns_degree(akns));
+    if (h) {
+        h->nse_disc = -1;
+        h->kdv_disc = kd;
+        h->core->kdv = true;
     }
-    (void)P->be.sync();
-    *plan = P;
-    return FNFT_SUCCESS;
+    return batch_init(plan, std::move(h), device);
 }
 
 FNFT_INT fnft_amd_kdvv_contspec_device(fnft_amd_plan_t *plan, const void *d_u, void *d_contspec,
@@ -568,12 +574,9 @@ FNFT_INT fnft_amd_kdvv_contspec_device(fnft_amd_plan_t *plan, const void *d_u, v
 {
     if (!plan || plan->kdv_disc < 0 || !d_u || !d_contspec || !T || !(T[0] < T[1]) || !XI || !(XI[0] < XI[1]))
         return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    Plan &pl = *plan->pl;
-    plan->be.stream = (hipStream_t)stream;
-    plan->be.failed = false;
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
     plan->be.mark(0);
     // a real potential takes the real-coefficient tree (nft_real.h: half the transforms and bytes); in the default mode
     // the device is asked first -- one small kernel and a 4-byte read-back, i.e. this call then waits for the stream once
@@ -605,7 +608,8 @@ FNFT_INT fnft_amd_kdvv_contspec_device(fnft_amd_plan_t *plan, const void *d_u, v
 FNFT_INT fnft_amd_kdvv_plan_set_real_mode(fnft_amd_plan_t *plan, int mode)
 {
     if (!plan || plan->kdv_disc < 0 || mode < -1 || mode > 1) return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
+    PlanCall call(plan->mtx, plan->device);
+    if (!call.ok) return FNFT_EC_OTHER;
     plan->real_mode = mode;
     return FNFT_SUCCESS;
 }
@@ -613,20 +617,19 @@ FNFT_INT fnft_amd_kdvv_plan_set_real_mode(fnft_amd_plan_t *plan, int mode)
 FNFT_INT fnft_amd_plan_finish(fnft_amd_plan_t *plan, void *stream)
 {
     if (!plan) return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    plan->be.stream = (hipStream_t)stream;
-    return plan->pl->read_status();
+    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return plan->core->read_status();
 }
 
 FNFT_INT fnft_amd_plan_get_transfer_matrix(fnft_amd_plan_t *plan, FNFT_UINT b,
                                            FNFT_COMPLEX *result_host, FNFT_UINT *deg, FNFT_INT *W)
 {
-    if (!plan || !result_host || !plan->pl->tree_valid || b >= plan->pl->batch)
+    if (!plan || !result_host || !plan->core->tree_valid || b >= plan->core->batch)
         return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    Plan &pl = *plan->pl;
+    PlanCall call(plan->mtx, plan->device);   // on the stream of the call that ran the tree
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
     pl.export_tm();
     const size_t per = 4 * (pl.res_deg + 1);
     plan->be.d2h(result_host, pl.tm_out + b * per, per * sizeof(cplx));
@@ -643,12 +646,10 @@ FNFT_INT fnft_amd_plan_get_transfer_matrix(fnft_amd_plan_t *plan, FNFT_UINT b,
 FNFT_INT fnft_amd_plan_get_transfer_matrix_device(fnft_amd_plan_t *plan, FNFT_UINT b, void *d_result,
                                                   FNFT_UINT *deg, FNFT_INT *W, void *stream)
 {
-    if (!plan || !d_result || !plan->pl->tree_valid || b >= plan->pl->batch) return FNFT_EC_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(plan->mtx);
-    DeviceGuard dg(plan->device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    Plan &pl = *plan->pl;
-    plan->be.stream = (hipStream_t)stream;
+    if (!plan || !d_result || !plan->core->tree_valid || b >= plan->core->batch) return FNFT_EC_INVALID_ARGUMENT;
+    PlanCall call(plan->mtx, plan->device, plan->be, nullptr, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
     pl.export_tm();
     const size_t per = 4 * (pl.res_deg + 1);
     if (!hip_ok(hipMemcpyAsync(d_result, pl.tm_out + b * per, per * sizeof(cplx), hipMemcpyDeviceToDevice,
@@ -672,10 +673,9 @@ FNFT_UINT fnft__poly_fmult2x2_numel(const FNFT_UINT deg, const FNFT_UINT n)
 FNFT_INT fnft__poly_fmult2x2(FNFT_UINT *const d, FNFT_UINT n, FNFT_COMPLEX *const p,
                              FNFT_COMPLEX *const result, FNFT_INT *const W_ptr)
 {
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    HipBackend be;
-    return api_poly_fmult2x2(be, d, n, p, result, W_ptr);
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return call.done(api_poly_fmult2x2(call.be, d, n, p, result, W_ptr));
 }
 
 // fnft__poly_fmult2x2 on matrices that are already in device memory (the root's step of a sample-axis split: the G
@@ -686,10 +686,9 @@ FNFT_INT fnft_amd_poly_fmult2x2_device(FNFT_UINT deg, FNFT_UINT n, const void *d
                                        FNFT_INT *W_out, void *stream)
 {
     if (deg == 0 || n == 0 || !d_p || !d_result || !W_out || deg > 0x7fffffff) return FNFT_EC_INVALID_ARGUMENT;
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
-    be.stream = (hipStream_t)stream;
+    HostCall call(HostCall::kLock, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     Plan pl(be, n, 0, 1, -1, (int)deg);
     int rc = pl.init();
     if (rc == NFT_SUCCESS) rc = pl.load_level0_from_device(d_p);
@@ -702,8 +701,7 @@ FNFT_INT fnft_amd_poly_fmult2x2_device(FNFT_UINT deg, FNFT_UINT n, const void *d
         *W_out = W;
         if (deg_out) *deg_out = pl.res_deg;
     }
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    return call.done(rc);
 }
 
 // ---- scalar products and single pair products (src/private/fnft__poly_fmult.c:35-38,45-121,152-328) ----------
@@ -717,17 +715,16 @@ FNFT_UINT fnft__poly_fmult_numel(const FNFT_UINT deg, const FNFT_UINT n)
 FNFT_INT fnft__poly_fmult(FNFT_UINT *const d, FNFT_UINT n, FNFT_COMPLEX *const p, FNFT_INT *const W_ptr)
 {
     if (!d || !p || n == 0 || *d == 0) return FNFT_EC_INVALID_ARGUMENT;
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
     const size_t deg = *d, w = deg + 1;
     std::vector<std::complex<double>> m(fnft__poly_fmult2x2_numel(deg, n)), r(m.size());
     for (size_t i = 0; i < n * w; i++) {
         m[i] = p[i];                  // entry 11
         m[3 * n * w + i] = p[i];      // entry 22
     }
-    HipBackend be;
     size_t dd = deg;
-    const int rc = api_poly_fmult2x2(be, &dd, n, m.data(), r.data(), W_ptr);
+    const FNFT_INT rc = call.done(api_poly_fmult2x2(call.be, &dd, n, m.data(), r.data(), W_ptr));
     if (rc != FNFT_SUCCESS) return rc;
     for (size_t i = 0; i <= dd; i++) p[i] = r[i];
     *d = dd;
@@ -748,7 +745,7 @@ FNFT_INT fnft__poly_fmult_two_polys_len(const FNFT_UINT deg)
     }
 }
 
-static int two_polys_product(size_t deg, const std::complex<double> *p1, const std::complex<double> *p2,
+static int two_polys_product(HipBackend &be, size_t deg, const std::complex<double> *p1, const std::complex<double> *p2,
                              std::complex<double> *out /* 2*deg+1 */)
 {
     const size_t w = deg + 1;
@@ -757,7 +754,6 @@ static int two_polys_product(size_t deg, const std::complex<double> *p1, const s
         m[i] = p1[i];           m[w + i] = p2[i];                  // entry 11 of both factors
         m[6 * w + i] = p1[i];   m[7 * w + i] = p2[i];              // entry 22
     }
-    HipBackend be;
     size_t dd = deg;
     const int rc = api_poly_fmult2x2(be, &dd, 2, m.data(), r.data(), nullptr);
     if (rc != FNFT_SUCCESS) return rc;
@@ -776,14 +772,15 @@ FNFT_INT fnft__poly_fmult_two_polys(const FNFT_UINT deg, FNFT_COMPLEX const *con
 {
     (void)plan_fwd; (void)plan_inv; (void)buf0;
     if (!result || !buf1 || !buf2 || mode > 3) return FNFT_EC_INVALID_ARGUMENT;
-    if (current_device() < 0) return FNFT_EC_OTHER;
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
     const size_t w = deg + 1, wr = 2 * deg + 1;
     if (p1) for (size_t i = 0; i < w; i++) buf1[i] = p1[i];
     if (p2) for (size_t i = 0; i < w; i++) buf2[i] = p2[i];
     std::vector<std::complex<double>> prod(wr);
     if (deg == 0) prod[0] = buf1[0] * buf2[0];
     else {
-        const int rc = two_polys_product(deg, buf1, buf2, prod.data());
+        const FNFT_INT rc = call.done(two_polys_product(call.be, deg, buf1, buf2, prod.data()));
         if (rc != FNFT_SUCCESS) return rc;
     }
     switch (mode) {
@@ -805,7 +802,8 @@ FNFT_INT fnft__poly_fmult_two_polys2x2(const FNFT_UINT deg, FNFT_COMPLEX const *
 {
     (void)plan_fwd; (void)plan_inv; (void)buf0; (void)buf1; (void)buf2; (void)mode_offset;
     if (!p1_11 || !p2_11 || !result_11 || deg == 0) return FNFT_EC_INVALID_ARGUMENT;
-    if (current_device() < 0) return FNFT_EC_OTHER;
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
     const size_t w = deg + 1, wr = 2 * deg + 1;
     std::vector<std::complex<double>> m(fnft__poly_fmult2x2_numel(deg, 2)), r(m.size());
     for (int e = 0; e < 4; e++)
@@ -813,9 +811,8 @@ FNFT_INT fnft__poly_fmult_two_polys2x2(const FNFT_UINT deg, FNFT_COMPLEX const *
             m[(size_t)e * 2 * w + i] = p1_11[(size_t)e * p1_stride + i];
             m[(size_t)e * 2 * w + w + i] = p2_11[(size_t)e * p2_stride + i];
         }
-    HipBackend be;
     size_t dd = deg;
-    const int rc = api_poly_fmult2x2(be, &dd, 2, m.data(), r.data(), nullptr);
+    const FNFT_INT rc = call.done(api_poly_fmult2x2(call.be, &dd, 2, m.data(), r.data(), nullptr));
     if (rc != FNFT_SUCCESS) return rc;
     for (int e = 0; e < 4; e++)
         for (size_t i = 0; i < wr; i++) result_11[(size_t)e * result_stride + i] = r[(size_t)e * wr + i];
@@ -851,27 +848,17 @@ FNFT_INT fnft__nse_finvscatter(const FNFT_UINT deg, FNFT_COMPLEX *const transfer
     // the base case exists for the two degree-1 schemes only, :164-211
     const bool modal = discretization == fnft_nse_discretization_2SPLIT2_MODAL;
     SEAM_CHECK(!modal && discretization != fnft_nse_discretization_2SPLIT2A, discretization);
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    // one resident peeler per device: its pair-product plans (one per degree) and work arrays are reused by later
-    // calls; sizes beyond 2^18 samples release everything again (workspace footprint)
-    const int dev = current_device();
-    Peeler *pp = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_peelers_mtx);
-        Peeler *&slot = g_peelers[dev];
-        if (!slot) slot = new (std::nothrow) Peeler();
-        pp = slot;
-    }
-    if (!pp) return FNFT_EC_NOMEM;
-    pp->be.failed = false;
-    pp->lp.eps_t = eps_t;
-    pp->lp.kappa = (int)kappa;
-    pp->lp.modal = modal ? 1 : 0;
-    const int rc = pp->lp.run_host(deg, transfer_matrix, q);
-    const bool failed = pp->be.failed;
-    if (failed || rc != FNFT_SUCCESS || deg > ((size_t)1 << 18)) pp->lp.destroy();
-    if (failed) return FNFT_EC_OTHER;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    // the device's resident peeler, on its own back end: its pair-product plans (one per degree) and work arrays are
+    // reused by later calls; a failure, or a size beyond 2^18 samples (workspace footprint), releases everything again
+    Peeler &pp = call.hs->peeler;
+    pp.be.failed = false;
+    pp.lp.eps_t = eps_t;
+    pp.lp.kappa = (int)kappa;
+    pp.lp.modal = modal ? 1 : 0;
+    const FNFT_INT rc = drained(pp.be, pp.lp.run_host(deg, transfer_matrix, q));
+    if (rc != FNFT_SUCCESS || deg > ((size_t)1 << 18)) pp.lp.destroy();
     return rc;
 }
 
@@ -885,13 +872,11 @@ FNFT_INT fnft__poly_specfact(const FNFT_UINT deg, FNFT_COMPLEX const *const poly
     SEAM_CHECK(!result, result);
     SEAM_CHECK(oversampling_factor == 0, oversampling_factor);
     SEAM_CHECK(kappa != 0 && kappa != 1 && kappa != -1, kappa);  // :105-107
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
-    NftInverseDev<HipBackend> inv(be);
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    NftInverseDev<HipBackend> inv(call.be);
     int warn = 0;
-    const int rc = inv.specfact_host(deg, poly, result, oversampling_factor, (int)kappa, &warn);
-    if (be.failed) return FNFT_EC_OTHER;
+    const FNFT_INT rc = call.done(inv.specfact_host(deg, poly, result, oversampling_factor, (int)kappa, &warn));
     if (rc == FNFT_SUCCESS && warn) fnft_amd__warn("Ill-posed spectral factorization problem.", "fnft__poly_specfact", __LINE__);
     return rc;
 }
@@ -902,14 +887,11 @@ extern "C" FNFT_INT fnft_amd__inverse_transfer_matrix(FNFT_UINT M, FNFT_COMPLEX 
                                                       int method, FNFT_UINT max_iter, FNFT_UINT oversampling,
                                                       FNFT_REAL phase_factor, int *warn_specfact, int *warn_maxiter)
 {
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
-    NftInverseDev<HipBackend> inv(be);
-    const int rc = inv.transfer_matrix(M, contspec, XI, K, bound_states, D, T, deg, tm, (int)kappa, cstype, method,
-                                       max_iter, oversampling, phase_factor, warn_specfact, warn_maxiter);
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    NftInverseDev<HipBackend> inv(call.be);
+    return call.done(inv.transfer_matrix(M, contspec, XI, K, bound_states, D, T, deg, tm, (int)kappa, cstype, method,
+                                         max_iter, oversampling, phase_factor, warn_specfact, warn_maxiter));
 }
 
 // src/fnft_nsev_inverse.c:680-903: host bookkeeping (sorting, residues -> norming constants), device Darboux steps
@@ -920,15 +902,15 @@ extern "C" FNFT_INT fnft_amd__inverse_add_discrete(FNFT_UINT K, const FNFT_COMPL
 {
     typedef std::complex<double> cd;
     if (K == 0 || !bound_states || !normconsts_or_residues) return FNFT_EC_INVALID_ARGUMENT;
-    if (current_device() < 0) return FNFT_EC_OTHER;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     std::vector<cd> bs(bound_states, bound_states + K), nc(normconsts_or_residues, normconsts_or_residues + K);
     for (size_t i = 0; i < K; i++)            // descending imaginary part, the reference's exchange sort (:742-754)
         for (size_t j = i + 1; j < K; j++)
             if (bs[i].imag() < bs[j].imag()) { std::swap(bs[i], bs[j]); std::swap(nc[i], nc[j]); }
     for (size_t i = 0; i + 1 < K; i++)
-        if (bs[i + 1] == bs[i]) return FNFT_EC_SANITY_CHECK_FAILED;   // :756-761
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+        if (bs[i + 1] == bs[i]) return call.done(FNFT_EC_SANITY_CHECK_FAILED);   // :756-761
     int rc = FNFT_SUCCESS;
     if (residues) {                                                    // :771-795
         std::vector<cd> acs(K, cd(1.0, 0.0)), ap(K), bdummy(K);
@@ -938,7 +920,7 @@ extern "C" FNFT_INT fnft_amd__inverse_add_discrete(FNFT_UINT K, const FNFT_COMPL
             NftDiscSpec<HipBackend>::Prepared P(be);
             rc = ds.prepare(D, q, T, D, (int)fnft_nse_discretization_2SPLIT4B, P, false);
             if (rc == FNFT_SUCCESS) rc = ds.scatter(P, K, bs.data(), acs.data(), ap.data(), bdummy.data(), true);
-            if (rc != FNFT_SUCCESS || be.failed) return be.failed ? FNFT_EC_OTHER : rc;
+            if (rc != FNFT_SUCCESS || be.failed) return call.done(rc);
         }
         for (size_t i = 0; i < K; i++) {
             cd tmp = acs[i];
@@ -950,11 +932,9 @@ extern "C" FNFT_INT fnft_amd__inverse_add_discrete(FNFT_UINT K, const FNFT_COMPL
     int mode;
     if (contspec_flag == 0 && !seed_method) mode = 0;
     else if ((contspec_flag == 0 && seed_method) || (contspec_flag == 1 && !seed_method)) mode = 1;
-    else return FNFT_EC_INVALID_ARGUMENT;                              // :890-891
+    else return call.done(FNFT_EC_INVALID_ARGUMENT);                   // :890-891
     NftInverseDev<HipBackend> inv(be);
-    rc = inv.add_discrete(K, bs.data(), nc.data(), D, q, T, mode);
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    return call.done(inv.add_discrete(K, bs.data(), nc.data(), D, q, T, mode));
 }
 
 // ---- batched, device-resident fnft_nsev_inverse (continuous part) ----------------------------------------------------
@@ -1454,10 +1434,9 @@ FNFT_INT fnft_amd_poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, 
     SEAM_CHECK(M == 0, M);
     SEAM_CHECK(!result, result);
     SEAM_CHECK(!A || !W, A);
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    HipBackend be;
-    return Plan::chirpz_host(be, deg, p, {A[0], A[1]}, {W[0], W[1]}, M, result);
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return call.done(Plan::chirpz_host(call.be, deg, p, {A[0], A[1]}, {W[0], W[1]}, M, result));
 }
 
 FNFT_INT fnft__poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_COMPLEX A,
@@ -1472,12 +1451,13 @@ FNFT_INT fnft__poly_chirpz(const FNFT_UINT deg, FNFT_COMPLEX const *const p, con
 static FNFT_INT poly_eval_host(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z,
                                FNFT_COMPLEX *const deriv)
 {
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     DevArena<HipBackend> tmp(be);
     cplx *dp = nullptr, *dz = nullptr, *dv = nullptr, *dd = nullptr;
-    if (!tmp.get(dp, deg + 1) || !tmp.get(dz, nz) || !tmp.get(dv, nz) || (deriv && !tmp.get(dd, nz))) return FNFT_EC_NOMEM;
+    if (!tmp.get(dp, deg + 1) || !tmp.get(dz, nz) || !tmp.get(dv, nz) || (deriv && !tmp.get(dd, nz)))
+        return call.done(FNFT_EC_NOMEM);
     be.h2d(dp, p, (deg + 1) * sizeof(cplx));
     be.h2d(dz, z, nz * sizeof(cplx));
     int rc = polyeval_device(be, deg, 1, 1, dp, deg + 1, deg + 1, nz, dz, 0, dv, dd);
@@ -1486,8 +1466,7 @@ static FNFT_INT poly_eval_host(const FNFT_UINT deg, FNFT_COMPLEX const *const p,
         if (deriv) be.d2h(deriv, dd, nz * sizeof(cplx));
         rc = be.sync();
     }
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    return call.done(rc);
 }
 
 FNFT_INT fnft__poly_eval(const FNFT_UINT deg, FNFT_COMPLEX const *const p, const FNFT_UINT nz, FNFT_COMPLEX *const z)
@@ -1519,14 +1498,10 @@ FNFT_INT fnft_amd_poly_eval_device(FNFT_UINT deg, FNFT_UINT npoly, FNFT_UINT bat
         return FNFT_EC_INVALID_ARGUMENT;
     if (batch > 1 && bstride < deg + 1) return FNFT_EC_INVALID_ARGUMENT;
     if (nz == 0) return FNFT_SUCCESS;
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
-    be.stream = (hipStream_t)stream;
-    const int rc = polyeval_device(be, deg, npoly, batch, (const cplx *)d_p, pstride, bstride, nz, (const cplx *)d_z, zstride,
-                                   (cplx *)d_val, (cplx *)d_deriv);
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    HostCall call(HostCall::kLock, stream);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return call.done(polyeval_device(call.be, deg, npoly, batch, (const cplx *)d_p, pstride, bstride, nz, (const cplx *)d_z,
+                                     zstride, (cplx *)d_val, (cplx *)d_deriv));
 }
 
 // include/private/fnft__misc.h:241-242 (src/private/fnft__misc.c:326-407): band-limited shift by delta
@@ -1538,12 +1513,10 @@ FNFT_INT fnft__misc_resample(const FNFT_UINT D, const FNFT_REAL eps_t, FNFT_COMP
     SEAM_CHECK(!q, q);
     SEAM_CHECK(!q_new, q_new);
     SEAM_CHECK(eps_t == 0.0, eps_t);
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
     int warn = 0;
-    const int rc = Plan::resample_host(be, D, eps_t, q, delta, q_new, &warn);
+    const FNFT_INT rc = call.done(Plan::resample_host(call.be, D, eps_t, q, delta, q_new, &warn));
     if (rc == FNFT_SUCCESS && warn) fnft_amd__warn(kNotBandlimitedMsg, "fnft__misc_resample", __LINE__);
     return rc;
 }
@@ -1555,19 +1528,17 @@ FNFT_INT fnft__poly_roots_fasteigen(const FNFT_UINT deg, FNFT_COMPLEX const *con
     SEAM_CHECK(!p, p);
     SEAM_CHECK(!roots, roots);
     if (deg == 0) return FNFT_SUCCESS;
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     NftDiscSpec<HipBackend> ds(be);
     DevArena<HipBackend> tmp(be);
     cplx *d_coef = nullptr;
-    if (!tmp.get(d_coef, deg + 1)) return FNFT_EC_NOMEM;
+    if (!tmp.get(d_coef, deg + 1)) return call.done(FNFT_EC_NOMEM);
     be.h2d(d_coef, p, (deg + 1) * sizeof(cplx));
     std::vector<std::complex<double>> z;
-    int rc = ds.roots(d_coef, deg, z);
-    if (be.failed) return FNFT_EC_OTHER;
-    if (rc != NFT_SUCCESS) return -abs(rc);   // E_SUBROUTINE, :44-47
+    const int rc = ds.roots(d_coef, deg, z);
+    if (rc != NFT_SUCCESS || be.failed) return call.done(-abs(rc));   // E_SUBROUTINE, :44-47
     for (size_t i = 0; i < deg; i++) roots[i] = z[i];
     return FNFT_SUCCESS;
 }
@@ -1583,10 +1554,9 @@ FNFT_INT fnft_amd__aberthb_roots(FNFT_UINT n, FNFT_UINT batch, FNFT_COMPLEX cons
                                  int *status, int *warn, int *sweeps, FNFT_UINT *sizes)
 {
     if (n < 2 || batch == 0 || !coef || !z || !mdeg || !status || !warn || !sweeps) return FNFT_EC_INVALID_ARGUMENT;
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     NftDsOpts o;
     o.bsfilt = 2; o.bsloc = 0; o.niter = 0; o.Dsub = 0; o.dstype = 0; o.nse_disc = 4; o.richardson = 0;   // 2SPLIT2A: n = D
     NftDiscSpecSearch<HipBackend> ds(be, n, 1, batch, o);
@@ -1618,9 +1588,7 @@ FNFT_INT fnft_amd__aberthb_roots(FNFT_UINT n, FNFT_UINT batch, FNFT_COMPLEX cons
         }
         if (sizes) sizes[0] = (FNFT_UINT)ds.S;
     }
-    (void)be.sync();   // the arenas hand their blocks back: nothing enqueued may still be using them
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    return call.done(rc);
 }
 
 // include/private/fnft__nse_scatter.h:76-80 (src/private/fnft__nse_scatter_bound_states.c:29-667) for the
@@ -1646,10 +1614,9 @@ FNFT_INT fnft__nse_scatter_bound_states(const FNFT_UINT D, FNFT_COMPLEX const *c
     if (discretization != fnft_nse_discretization_BO && !cf42) return FNFT_EC_NOT_YET_IMPLEMENTED;
     if (D < 2 || !(T[0] < T[1])) return FNFT_EC_INVALID_ARGUMENT;
     if (cf42 && (D % 2 != 0 || D < 4)) return FNFT_EC_ASSERTION_FAILED;   // :188-191
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     NftDiscSpec<HipBackend> ds(be);
     NftDiscSpec<HipBackend>::Prepared P(be);
     int rc;
@@ -1672,20 +1639,21 @@ FNFT_INT fnft__nse_scatter_bound_states(const FNFT_UINT D, FNFT_COMPLEX const *c
     if (rc == NFT_SUCCESS)
         rc = ds.scatter(P, K, (const std::complex<double> *)bound_states, (std::complex<double> *)a_vals,
                         (std::complex<double> *)aprime_vals, (std::complex<double> *)b, skip_b_flag != 0);
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    return call.done(rc);
 }
 
 // include/private/fnft__poly_roots_fftgridsearch.h (src/private/fnft__poly_roots_fftgridsearch.c:35-151 and :159-217):
 // roots of a polynomial on the arc PHI of the unit circle.  *M_ptr: grid points in, estimates out; roots: *M_ptr
 // entries.  The chirp z-transforms, the candidate test and the ordered compaction run on the GPU.
-static int gridsearch_common(const size_t deg, const std::complex<double> *p, size_t *M_ptr, const double *PHI,
-                             std::complex<double> *roots, bool paraherm)
+static FNFT_INT gridsearch_common(const size_t deg, const std::complex<double> *p, size_t *M_ptr, const double *PHI,
+                                  std::complex<double> *roots, bool paraherm)
 {
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     const size_t M = *M_ptr;
     const double eps = (PHI[1] - PHI[0]) / (double)(M - 1);
     const std::complex<double> W(std::cos(eps), std::sin(eps));
-    HipBackend be;
     const size_t nblk = (M + 255) / 256, rings = paraherm ? 1 : 3;
     DevArena<HipBackend> tmp(be);
     cplx *vals = nullptr, *cand = nullptr, *out = nullptr;
@@ -1724,7 +1692,7 @@ static int gridsearch_common(const size_t deg, const std::complex<double> *p, si
             rc = be.sync();
         }
     }
-    if (be.failed) return FNFT_EC_OTHER;
+    rc = call.done(rc);
     if (rc == FNFT_SUCCESS) *M_ptr = nroots;
     return rc;
 }
@@ -1737,12 +1705,7 @@ FNFT_INT fnft__poly_roots_fftgridsearch(const FNFT_UINT deg, FNFT_COMPLEX const 
     SEAM_CHECK(!M_ptr || *M_ptr < 2, M_ptr);
     SEAM_CHECK(!PHI || !(PHI[0] < PHI[1]) || PHI[0] == -INFINITY || PHI[1] == INFINITY, PHI);
     SEAM_CHECK(!roots, roots);
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    size_t M = *M_ptr;
-    const int rc = gridsearch_common(deg, p, &M, PHI, roots, false);
-    if (rc == FNFT_SUCCESS) *M_ptr = M;
-    return rc;
+    return gridsearch_common(deg, p, M_ptr, PHI, roots, false);
 }
 FNFT_INT fnft__poly_roots_fftgridsearch_paraherm(const FNFT_UINT deg, FNFT_COMPLEX const *const p, FNFT_UINT *const M_ptr,
                                                  FNFT_REAL const *const PHI, FNFT_COMPLEX *const roots)
@@ -1753,12 +1716,7 @@ FNFT_INT fnft__poly_roots_fftgridsearch_paraherm(const FNFT_UINT deg, FNFT_COMPL
     SEAM_CHECK(!M_ptr || *M_ptr < 2, M_ptr);
     SEAM_CHECK(!PHI || !(PHI[0] < PHI[1]) || PHI[0] == -INFINITY || PHI[1] == INFINITY, PHI);
     SEAM_CHECK(!roots, roots);
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    size_t M = *M_ptr;
-    const int rc = gridsearch_common(deg, p, &M, PHI, roots, true);
-    if (rc == FNFT_SUCCESS) *M_ptr = M;
-    return rc;
+    return gridsearch_common(deg, p, M_ptr, PHI, roots, true);
 }
 
 // include/private/fnft__nse_scatter.h:119-123 (src/private/fnft__nse_scatter_matrix.c:33-86 ->
@@ -1778,9 +1736,9 @@ FNFT_INT fnft__nse_scatter_matrix(const FNFT_UINT D, FNFT_COMPLEX const *const q
     const bool cf42 = discretization == fnft_nse_discretization_CF4_2;
     if (discretization != fnft_nse_discretization_BO && !cf42) return FNFT_EC_NOT_YET_IMPLEMENTED;
     if (cf42 && D % 2 != 0) return FNFT_EC_ASSERTION_FAILED;
-    if (current_device() < 0) return FNFT_EC_OTHER;
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    HipBackend be;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    HipBackend &be = call.be;
     BsParams B;
     std::memset(&B, 0, sizeof(B));
     const size_t L = nft_bs_chunk_len(D);
@@ -1809,8 +1767,7 @@ FNFT_INT fnft__nse_scatter_matrix(const FNFT_UINT D, FNFT_COMPLEX const *const q
         be.d2h(result, ds, K * w * sizeof(cplx));
         rc = be.sync();
     }
-    if (be.failed) return FNFT_EC_OTHER;
-    return rc;
+    return call.done(rc);
 }
 
 FNFT_UINT fnft__akns_fscatter_numel(FNFT_UINT D, fnft__akns_discretization_t discretization)
@@ -1832,10 +1789,9 @@ FNFT_INT fnft__akns_fscatter(const FNFT_UINT D, FNFT_COMPLEX const *const q,
     SEAM_CHECK(!result, result);
     SEAM_CHECK(!deg_ptr, deg_ptr);
     SEAM_CHECK(nft_akns_degree((int)discretization) == 0, discretization);
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    HipBackend be;
-    return api_akns_fscatter(be, D, q, r, eps_t, 1, result, deg_ptr, W_ptr, (int)discretization);
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return call.done(api_akns_fscatter(call.be, D, q, r, eps_t, 1, result, deg_ptr, W_ptr, (int)discretization));
 }
 
 FNFT_UINT fnft__nse_fscatter_numel(FNFT_UINT D, fnft_nse_discretization_t discretization)
@@ -1854,10 +1810,9 @@ FNFT_INT fnft__nse_fscatter(const FNFT_UINT D, FNFT_COMPLEX const *const q, cons
         return FNFT_EC_INVALID_ARGUMENT;
     const int a = nft_nse_to_akns((int)discretization);
     if (a < 0) return FNFT_EC_INVALID_ARGUMENT;
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    HipBackend be;
-    return api_akns_fscatter(be, D, q, nullptr, eps_t, kappa, result, deg_ptr, W_ptr, a);
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return call.done(api_akns_fscatter(call.be, D, q, nullptr, eps_t, kappa, result, deg_ptr, W_ptr, a));
 }
 
 // 4SPLIT4A / 4SPLIT4B of the KdV seams: per-sample formulas and degrees of 2SPLIT4A / 2SPLIT4B on the samples as they
@@ -1888,61 +1843,33 @@ FNFT_INT fnft__kdv_fscatter(const FNFT_UINT D, FNFT_COMPLEX const *const u, cons
     SEAM_CHECK(!deg_ptr, deg_ptr);
     const int kd = kdv_alias((int)discretization);
     if (kd < 0 || kd > (int)fnft_kdv_discretization_2SPLIT8B) return FNFT_EC_INVALID_ARGUMENT;
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    HipBackend be;
-    return api_kdv_fscatter(be, D, (const std::complex<double> *)u, eps_t, (std::complex<double> *)result, deg_ptr,
-                            W_ptr, kd + 1);
+    HostCall call(HostCall::kNoLock);
+    if (!call.ok) return FNFT_EC_OTHER;
+    return call.done(api_kdv_fscatter(call.be, D, (const std::complex<double> *)u, eps_t, (std::complex<double> *)result,
+                                      deg_ptr, W_ptr, kd + 1));
 }
 
 // internal entry used by fnft_kdvv_host.c: host buffers in and out, plans cached per (D, M, scheme)
 FNFT_INT fnft_amd__kdvv_contspec_host(FNFT_UINT D, const FNFT_COMPLEX *u, const FNFT_REAL *T, FNFT_UINT M,
                                       FNFT_COMPLEX *contspec, const FNFT_REAL *XI, int discretization)
 {
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
     fnft_amd_plan *P = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mtx);
-        auto &cache = g_kdvv_cache;
-        auto key = std::make_tuple(dev, (size_t)D, (size_t)M, discretization);
-        auto it = cache.find(key);
-        if (it == cache.end()) {
-            if (cache.size() >= 4) {
-                for (auto &kv : cache) fnft_amd_plan_destroy(kv.second);
-                cache.clear();
-            }
-            const FNFT_INT rc = fnft_amd_kdvv_plan_create(&P, D, M, 1, (fnft_kdv_discretization_t)discretization, dev);
-            if (rc != FNFT_SUCCESS) return rc;
-            cache[key] = P;
-        } else {
-            P = it->second;
-        }
-    }
-    // staging buffers on the device: from the block cache (no hipMalloc / hipFree per call)
-    cplx *du = (cplx *)fa_pool_alloc(D * sizeof(cplx)), *dcs = (cplx *)fa_pool_alloc(M * sizeof(cplx));
-    if (!du || !dcs) {
-        if (du) fa_pool_free(du);
-        if (dcs) fa_pool_free(dcs);
-        return FNFT_EC_NOMEM;
-    }
+    const FNFT_INT rc = call.hs->kdvv.get(std::make_tuple((size_t)D, (size_t)M, discretization), &P, [&](fnft_amd_plan **h) {
+        return fnft_amd_kdvv_plan_create(h, D, M, 1, (fnft_kdv_discretization_t)discretization, call.dev);
+    });
+    if (rc != FNFT_SUCCESS) return call.done(rc);
     {   // the potential is in host memory: look at it here instead of asking the device
         bool real = true;
         const std::complex<double> *uh = (const std::complex<double> *)u;
         for (size_t i = 0; i < D && real; i++) real = (uh[i].imag() == 0.0);
         P->real_mode = real ? 1 : 0;
     }
-    FNFT_INT rc = FNFT_SUCCESS;
-    if (!hip_ok(hipMemcpy(du, u, D * sizeof(cplx), hipMemcpyHostToDevice), "hipMemcpy(H2D)")) rc = FNFT_EC_OTHER;
-    if (rc == FNFT_SUCCESS) rc = fnft_amd_kdvv_contspec_device(P, du, dcs, T, XI, nullptr);
-    if (rc == FNFT_SUCCESS) rc = fnft_amd_plan_finish(P, nullptr);
-    if (rc == FNFT_SUCCESS)
-        if (!hip_ok(hipMemcpy(contspec, dcs, M * sizeof(cplx), hipMemcpyDeviceToHost), "hipMemcpy(D2H)"))
-            rc = FNFT_EC_OTHER;
-    fa_pool_free(du);
-    fa_pool_free(dcs);
-    return rc;
+    return staged_run(call, u, D, contspec, M, [&](cplx *du, cplx *dcs) {
+        const FNFT_INT r = fnft_amd_kdvv_contspec_device(P, du, dcs, T, XI, nullptr);
+        return r == FNFT_SUCCESS ? fnft_amd_plan_finish(P, nullptr) : r;
+    });
 }
 
 // internal entry used by fnft_nsev_host.c: discrete spectrum (kappa = +1), host buffers.
@@ -1952,19 +1879,16 @@ FNFT_INT fnft_amd__nsev_discspec_host(FNFT_UINT D, const FNFT_COMPLEX *q, const 
                                       int richardson, FNFT_UINT *K_ptr, FNFT_COMPLEX *bound_states,
                                       FNFT_COMPLEX *normconsts_or_residues, int *warn)
 {
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
-    HipBackend be;
-    NftDiscSpec<HipBackend> ds(be);
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
+    NftDiscSpec<HipBackend> ds(call.be);
     NftDsOpts o;
     o.bsfilt = bsfilt; o.bsloc = bsloc; o.niter = niter; o.Dsub = Dsub; o.dstype = dstype;
     o.nse_disc = discretization; o.richardson = richardson;
     size_t K = *K_ptr;
-    const int rc = ds.run(D, (const std::complex<double> *)q, T, o, &K, (std::complex<double> *)bound_states,
-                          (std::complex<double> *)normconsts_or_residues);
+    const FNFT_INT rc = call.done(ds.run(D, (const std::complex<double> *)q, T, o, &K, (std::complex<double> *)bound_states,
+                                         (std::complex<double> *)normconsts_or_residues));
     if (warn) *warn = (ds.warn_more_than_K ? 1 : 0) | (ds.warn_roots_unconverged ? 2 : 0);
-    if (be.failed) return FNFT_EC_OTHER;
     if (rc == NFT_SUCCESS) *K_ptr = K;
     return rc;
 }
@@ -1978,54 +1902,23 @@ FNFT_INT fnft_amd__nsev_contspec_host(FNFT_UINT D, const FNFT_COMPLEX *q, const 
                                       FNFT_INT kappa, int discretization, int contspec_type,
                                       FNFT_INT normalization_flag, FNFT_UINT nskip)
 {
-    std::lock_guard<std::mutex> host_lk(host_call_mutex());
-    const int dev = current_device();
-    if (dev < 0) return FNFT_EC_OTHER;
+    HostCall call;
+    if (!call.ok) return FNFT_EC_OTHER;
     fnft_amd_plan *P = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mtx);
-        auto &cache = g_nsev_cache;
-        auto key = std::make_tuple(dev, (size_t)D, (size_t)M, discretization, (size_t)nskip);
-        auto it = cache.find(key);
-        if (it == cache.end()) {
-            if (cache.size() >= 4) {  // keep the workspace footprint bounded
-                for (auto &kv : cache) fnft_amd_plan_destroy(kv.second);
-                cache.clear();
-            }
-            const FNFT_INT rc = fnft_amd_plan_create_sub(&P, D, M, 1,
-                                                         (fnft_nse_discretization_t)discretization, dev, nskip);
-            if (rc != FNFT_SUCCESS) return rc;
-            cache[key] = P;
-        } else {
-            P = it->second;
-        }
-    }
+    const FNFT_INT rc = call.hs->nsev.get(
+        std::make_tuple((size_t)D, (size_t)M, discretization, (size_t)nskip), &P, [&](fnft_amd_plan **h) {
+            return fnft_amd_plan_create_sub(h, D, M, 1, (fnft_nse_discretization_t)discretization, call.dev, nskip);
+        });
+    if (rc != FNFT_SUCCESS) return call.done(rc);
     const size_t cs_len = M * (contspec_type == 0 ? 1 : (contspec_type == 1 ? 2 : 3));
-    // staging buffers on the device: from the block cache (no hipMalloc / hipFree per call).  The caller's arrays are
-    // ordinary pageable memory: hipMemcpy moves them at the link rate once their pages are resident.
-    cplx *dq = (cplx *)fa_pool_alloc(D * sizeof(cplx));
-    cplx *dcs = (cplx *)fa_pool_alloc((cs_len ? cs_len : 1) * sizeof(cplx));
-    if (!dq || !dcs) {
-        if (dq) fa_pool_free(dq);
-        if (dcs) fa_pool_free(dcs);
-        return FNFT_EC_NOMEM;
-    }
-    FNFT_INT rc = FNFT_SUCCESS;
-    if (!hip_ok(hipMemcpy(dq, q, D * sizeof(cplx), hipMemcpyHostToDevice), "hipMemcpy(H2D)"))
-        rc = FNFT_EC_OTHER;
-    if (rc == FNFT_SUCCESS)
-        rc = fnft_amd_nsev_contspec_device(P, dq, contspec ? dcs : nullptr, T, XI, kappa,
-                                           (fnft_nsev_cstype_t)contspec_type, normalization_flag,
-                                           nullptr);
-    if (rc == FNFT_SUCCESS) rc = fnft_amd_plan_finish(P, nullptr);
-    // the resampler of the 4SPLIT4A/B front end warns when the spectrum has not decayed (fnft__misc.c:371-381)
-    if (fnft_amd_plan_last_warnings(P) & 1) fnft_amd__warn(kNotBandlimitedMsg, "fnft__misc_resample", __LINE__);
-    if (rc == FNFT_SUCCESS && contspec && cs_len)
-        if (!hip_ok(hipMemcpy(contspec, dcs, cs_len * sizeof(cplx), hipMemcpyDeviceToHost), "hipMemcpy(D2H)"))
-            rc = FNFT_EC_OTHER;
-    fa_pool_free(dq);
-    fa_pool_free(dcs);
-    return rc;
+    return staged_run(call, q, D, contspec, cs_len, [&](cplx *dq, cplx *dcs) {
+        FNFT_INT r = fnft_amd_nsev_contspec_device(P, dq, contspec ? dcs : nullptr, T, XI, kappa,
+                                                   (fnft_nsev_cstype_t)contspec_type, normalization_flag, nullptr);
+        if (r == FNFT_SUCCESS) r = fnft_amd_plan_finish(P, nullptr);
+        // the resampler of the 4SPLIT4A/B front end warns when the spectrum has not decayed (fnft__misc.c:371-381)
+        if (fnft_amd_plan_last_warnings(P) & 1) fnft_amd__warn(kNotBandlimitedMsg, "fnft__misc_resample", __LINE__);
+        return r;
+    });
 }
 
 // Everything the host-pointer entry points keep on `device` between calls goes back to the driver: cached plans, the
@@ -2037,31 +1930,15 @@ void fnft_amd_release_cached(int device)
     if (hipGetDeviceCount(&ndev) != hipSuccess) return;
     for (int d = 0; d < ndev; d++) {
         if (device >= 0 && d != device) continue;
-        std::lock_guard<std::mutex> host_lk(host_call_mutex_of(d));
-        {
-            std::lock_guard<std::mutex> lk(g_cache_mtx);
-            for (auto it = g_nsev_cache.begin(); it != g_nsev_cache.end();) {
-                if (std::get<0>(it->first) == d) { fnft_amd_plan_destroy(it->second); it = g_nsev_cache.erase(it); }
-                else ++it;
-            }
-            for (auto it = g_kdvv_cache.begin(); it != g_kdvv_cache.end();) {
-                if (std::get<0>(it->first) == d) { fnft_amd_plan_destroy(it->second); it = g_kdvv_cache.erase(it); }
-                else ++it;
-            }
-        }
-        {
-            std::lock_guard<std::mutex> lk(g_peelers_mtx);
-            auto it = g_peelers.find(d);
-            if (it != g_peelers.end() && it->second) {
-                DeviceGuard dg(d);
-                if (dg.ok) {
-                    (void)hipDeviceSynchronize();
-                    it->second->lp.destroy();
-                }
-            }
-        }
+        HostState &hs = host_state(d);
+        std::lock_guard<std::mutex> host_lk(hs.mtx);
+        hs.nsev.clear();
+        hs.kdvv.clear();
         DeviceGuard dg(d);
-        if (dg.ok) (void)hipDeviceSynchronize();
+        if (dg.ok) {
+            (void)hipDeviceSynchronize();
+            hs.peeler.lp.destroy();
+        }
         DevPool &P = pool();
         std::lock_guard<std::mutex> lk(P.m);
         P.trim_locked(d);

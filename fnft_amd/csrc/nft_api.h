@@ -28,6 +28,14 @@ int api_export_result(NftPlan<BE> &pl, std::complex<double> *result, size_t *deg
     return NFT_SUCCESS;
 }
 
+// what a host-pointer entry returns while its plan is still alive: a call that failed half-way waits for what it has
+// enqueued, so that the plan's arena hands its blocks back from an idle stream
+template <class BE> int api_return(BE &be, int rc)
+{
+    if (rc != NFT_SUCCESS) (void)be.sync();
+    return rc;
+}
+
 // fnft__poly_fmult2x2, src/private/fnft__poly_fmult.c:381-546 (host buffers in and out)
 template <class BE>
 int api_poly_fmult2x2(BE &be, size_t *d, size_t n, std::complex<double> *p,
@@ -41,7 +49,7 @@ int api_poly_fmult2x2(BE &be, size_t *d, size_t n, std::complex<double> *p,
     if (rc == NFT_SUCCESS) rc = pl.load_level0_from_host(p);
     if (rc == NFT_SUCCESS) rc = pl.run_tree();
     if (rc == NFT_SUCCESS) rc = api_export_result(pl, result, d, W_ptr, false);
-    return rc;
+    return api_return(be, rc);
 }
 
 // fnft__akns_fscatter, src/private/fnft__akns_fscatter.c:64-925 (r may be NULL: r = -kappa q*)
@@ -54,15 +62,15 @@ int api_akns_fscatter(BE &be, size_t D, const std::complex<double> *q, const std
     if (deg0 == 0) return NFT_EC_INVALID_ARGUMENT;
     NftPlan<BE> pl(be, D, 0, 1, akns_disc, deg0);
     int rc = pl.init();
-    if (rc != NFT_SUCCESS) return rc;
+    if (rc != NFT_SUCCESS) return api_return(be, rc);
     cplx *dq = nullptr, *dr = nullptr;
-    if (!pl.mem.get(dq, D) || (r && !pl.mem.get(dr, D))) return NFT_EC_NOMEM;
+    if (!pl.mem.get(dq, D) || (r && !pl.mem.get(dr, D))) return api_return(be, NFT_EC_NOMEM);
     be.h2d(dq, q, D * sizeof(cplx));
     if (r) be.h2d(dr, r, D * sizeof(cplx));
     rc = pl.run_coeffs(dq, dr, eps_t, kappa);
     if (rc == NFT_SUCCESS) rc = pl.run_tree();
     if (rc == NFT_SUCCESS) rc = api_export_result(pl, result, deg_ptr, W_ptr, true);
-    return rc;
+    return api_return(be, rc);
 }
 
 // fnft__kdv_fscatter, src/private/fnft__kdv_fscatter.c:45-83: r = -1 for every sample; a real potential takes the
@@ -79,12 +87,12 @@ int api_kdv_fscatter(BE &be, size_t D, const std::complex<double> *u, double eps
     pl.kdv = true;
     pl.want_real = real;
     int rc = pl.init();
-    if (rc != NFT_SUCCESS) return rc;
+    if (rc != NFT_SUCCESS) return api_return(be, rc);
     cplx *dq = nullptr;
-    if (!pl.mem.get(dq, D)) return NFT_EC_NOMEM;
+    if (!pl.mem.get(dq, D)) return api_return(be, NFT_EC_NOMEM);
     be.h2d(dq, u, D * sizeof(cplx));
     rc = pl.run_coeffs(dq, pl.rneg, eps_t, 1);
     if (rc == NFT_SUCCESS) rc = pl.run_tree();
     if (rc == NFT_SUCCESS) rc = api_export_result(pl, result, deg_ptr, W_ptr, true);
-    return rc;
+    return api_return(be, rc);
 }

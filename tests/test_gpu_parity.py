@@ -975,6 +975,52 @@ def test_release_cached_keeps_results(capi):
     assert rc == 0 and np.array_equal(a, c)
 
 
+def test_host_cache_eviction_sequence(capi):
+    """The host-pointer entries keep at most four plans per device and transform: six sizes of fnft_nsev (five of
+    fnft_kdvv) in order, twice over, take the cache past its capacity, so the second round runs on rebuilt plans and on
+    blocks the pool has handed out before -- every result is bit-equal to the first round's.  A device-resident plan of
+    the caller's is not the cache's: it gives the same output before, after the sequence and after release_cached."""
+    import torch
+    T, XI = [-25.0, 25.0], [-1.4, 1.6]
+    Dp, Mp = 1024, 64
+    qp = torch.from_numpy(S.sech_focusing(Dp, amp=2.3)).cuda()
+    plan = capi.Plan(Dp, Mp, batch=1, discretization="2SPLIT4B")
+
+    def run_plan():
+        out = torch.zeros(3 * Mp, dtype=torch.complex128, device="cuda")
+        assert plan.contspec_device(qp.data_ptr(), out.data_ptr(), T, XI) == 0 and plan.finish() == 0
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    before = run_plan()
+    nsev_sizes = [(64, 16), (128, 16), (256, 32), (512, 32), (1024, 64), (2048, 64)]
+    rounds = []
+    for _ in range(2):
+        res = []
+        for D, M in nsev_sizes:
+            rc, cs = capi.fnft_nsev(S.sech_focusing(D), T, M, XI, discretization="2SPLIT4B", contspec_type="BOTH")
+            assert rc == 0 and cs.size == 3 * M and np.all(np.isfinite(cs)) and np.all(cs != 0), capi.last_error()
+            res.append(cs.copy())
+        rounds.append(res)
+    for a, b in zip(*rounds):
+        assert np.array_equal(a, b)
+    Tk, XIk = [-16.0, 15.0], [-3.0, 3.5]
+    rounds = []
+    for _ in range(2):
+        res = []
+        for D, M in nsev_sizes[:5]:
+            rc, cs = capi.fnft_kdvv(0.8 * S.kdvv_sech(D, Tk), Tk, M, XIk, discretization="2SPLIT4B")
+            assert rc == 0 and cs.size == M and np.all(np.isfinite(cs)) and np.all(cs != 0), capi.last_error()
+            res.append(cs.copy())
+        rounds.append(res)
+    for a, b in zip(*rounds):
+        assert np.array_equal(a, b)
+    assert np.array_equal(run_plan(), before)
+    capi.release_cached(-1)
+    assert np.array_equal(run_plan(), before)
+    plan.close()
+
+
 def test_contspec_from_transfer_matrix_and_div_by_zero(capi, oracle):
     """nsev_compute_contspec on a caller-supplied transfer matrix (fnft_amd_nsev_contspec_from_tm_device):
     (i) fed with the plan's own transfer matrix it reproduces the spectrum of the full call; (ii) a transfer
