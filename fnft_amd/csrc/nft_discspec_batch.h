@@ -4,7 +4,7 @@
 // src/fnft_nsev.c:971-1038 Newton refinement, misc_filter / misc_merge, :895-968 norming constants / residues), with
 // one workgroup per (signal, eigenvalue) instead of a host loop over chunk kernels (nft_kernels.h: body_ds_*).
 //   box kernel -> Newton kernel (all iterations on chip) -> filter + merge kernel -> norming kernel
-// 4SPLIT4A/B refine on the resampled signal of the batched front end of NftPlan (set_front / run_front, qpre).
+// 4SPLIT4A/B refine on the resampled signal of that scheme's front end (NftResampler::run_4split4, qpre).
 // Back-end independent like NftDiscSpec: hip_backend.hip instantiates it with the HIP back end, tests/emu with the
 // lane emulator.
 #pragma once
@@ -13,13 +13,15 @@
 template <class BE> class NftDiscSpecBatch {
 public:
     BE &be;
-    DevArena<BE> mem;                 // owns lam, box, status, phi
+    DevArena<BE> mem;                 // owns lam, box, status, phi and the front end's tables and arrays
     const size_t D, K, batch;
     const NftDsOpts o;
     int ups = 1, deg0 = 0, akns = -1;
     size_t Dq = 0;                    // preprocessed samples per signal
     int G = 1;                        // samples per lane
-    std::unique_ptr<NftPlan<BE>> front;   // 4SPLIT4A/B: resampling workspace
+    NftTwiddles<BE> tw;
+    NftResampler<BE> rs;              // 4SPLIT4A/B: the front end's shifted copies, combined into qpre (batch * Dq)
+    cplx *qpre = nullptr;
     cplx *lam = nullptr;              // batch*K refined eigenvalues
     double *box = nullptr;            // batch*4
     int *status = nullptr;            // batch
@@ -30,7 +32,7 @@ public:
     static constexpr size_t kPhiBytes = (size_t)256 << 20;      // phi workspace of one norming launch
 
     NftDiscSpecBatch(BE &be_, size_t D_, size_t K_, size_t batch_, const NftDsOpts &o_)
-        : be(be_), mem(be_), D(D_), K(K_), batch(batch_), o(o_)
+        : be(be_), mem(be_), D(D_), K(K_), batch(batch_), o(o_), rs(be_, tw)
     {
         akns = nft_nse_to_akns(o.nse_disc);
         ups = nft_nse_upsampling(o.nse_disc);
@@ -48,10 +50,12 @@ public:
         if (K > kMaxK || batch > kMaxGroups / K || Dq > (size_t)0x7fffffff * (size_t)kDsLanes)
             return NFT_EC_NOT_YET_IMPLEMENTED;
         if (ups == 2) {
-            front.reset(new NftPlan<BE>(be, Dq, 0, batch, akns, deg0));
-            front->set_front(D, 1, ups);
-            const int rc = front->init();
+            if (D <= 2) return NFT_EC_INVALID_ARGUMENT;
+            if (nft_tree_too_large(Dq, deg0)) return NFT_EC_NOT_YET_IMPLEMENTED;   // the limit of the scheme's tree plan, kept
+            const int rc = rs.init(mem, D, batch);
             if (rc != NFT_SUCCESS) return rc;
+            // the tables last: their upload waits for the cleared status word
+            if (!(mem.get(qpre, batch * Dq) && tw.init(mem))) return NFT_EC_NOMEM;
         }
         const size_t per_signal = K * sphi * sizeof(cplx);
         slab = kPhiBytes / per_signal;
@@ -63,9 +67,9 @@ public:
     }
 
     // the workspace back before the plan goes out of scope (the destructor does the same); init() again before reuse
-    void destroy() { front.reset(); mem.clear(); }
+    void destroy() { mem.clear(); }
 
-    size_t workspace_bytes() const { return mem.bytes + (front ? front->mem.bytes : 0); }
+    size_t workspace_bytes() const { return mem.bytes; }
 
     // enqueues everything; waits for nothing.  d_nc may be NULL (no norming constants / residues); d_nguess: live guesses
     // per signal (the guess-free plan's candidates, nft_discspec_search.h), NULL: K each
@@ -77,16 +81,13 @@ public:
         const double T1 = T[0] + (double)(D - 1) * eps_in;
         const double eps_t = (T1 - T[0]) / (double)(D - 1);
         be.memset0(status, batch * sizeof(int));
-        const cplx *qpre = d_q;
         if (ups == 2) {
-            double Tsub[2];
-            const int rc = front->run_front(d_q, T, +1, Tsub);   // resampling (and level 0 of the tree, unused here)
+            const int rc = rs.run_4split4(d_q, 1, D, qpre, rs.ft.status);   // the band check's bit: read by nobody
             if (rc != NFT_SUCCESS) return rc;
-            qpre = front->qpre;
         }
         DsBatchParams P;
         std::memset(&P, 0, sizeof(P));
-        P.q = qpre;
+        P.q = (ups == 2) ? qpre : d_q;
         P.D = (long long)Dq;
         P.ups = ups;
         P.G = G;

@@ -42,7 +42,9 @@ public:
     static constexpr size_t kLeaf = 256;
     static constexpr size_t kOneLaunchMaxDeg = 1024;   // products up to this degree: KPeelProduct
     BE &be;
-    DevArena<BE> mem;            // owns the status words and the work arrays
+    DevArena<BE> mem;            // owns the status words, the work arrays and, unless borrowed, the twiddle tables
+    NftTwiddles<BE> own_tw;      // allocated with the first product above the leaf
+    const NftTwiddles<BE> &tw;   // the one table set of the peeler and of its per-degree trees
     double eps_t;
     int kappa, modal;
     size_t batch = 1;
@@ -52,8 +54,9 @@ public:
     struct Work { cplx *T2i = nullptr, *T1 = nullptr, *T1i = nullptr; };
     std::vector<Work> work;
 
-    NftLayerPeelingDev(BE &b, double eps, int kap, int is_modal)
-        : be(b), mem(b), eps_t(eps), kappa(kap), modal(is_modal) {}
+    // borrowed: the tables of the class the peeler is a part of, initialised before prepare() / peel()
+    NftLayerPeelingDev(BE &b, double eps, int kap, int is_modal, const NftTwiddles<BE> *borrowed = nullptr)
+        : be(b), mem(b), tw(borrowed ? *borrowed : own_tw), eps_t(eps), kappa(kap), modal(is_modal) {}
     size_t status_words() const { return std::max<size_t>(4, batch); }
     // everything back, the object stays usable: the resident peeler of the host-pointer entries is emptied and reused
     void destroy()
@@ -62,6 +65,7 @@ public:
         work.clear();
         work_deg = 0;
         mem.clear();
+        own_tw = NftTwiddles<BE>();
         d_status = nullptr;
     }
     size_t workspace_bytes() const
@@ -95,11 +99,18 @@ public:
         }
         return NFT_SUCCESS;
     }
+    bool tables()
+    {
+        if (tw.ready() || (&tw == &own_tw && own_tw.init(mem))) return true;
+        rc = NFT_EC_NOMEM;
+        return false;
+    }
     NftPlan<BE> *plan_for(size_t deg)
     {
         auto it = plans.find(deg);
         if (it != plans.end()) return it->second.get();
-        std::unique_ptr<NftPlan<BE>> pl(new (std::nothrow) NftPlan<BE>(be, 2, 0, batch, -1, (int)deg));
+        if (!tables()) return nullptr;
+        std::unique_ptr<NftPlan<BE>> pl(new (std::nothrow) NftPlan<BE>(be, 2, 0, batch, -1, (int)deg, &tw));
         if (!pl) { rc = NFT_EC_NOMEM; return nullptr; }
         const int r = pl->init();
         if (r != NFT_SUCCESS) { rc = r; return nullptr; }
@@ -110,7 +121,7 @@ public:
     {
         const int r = init(deg);
         if (r != NFT_SUCCESS) return r;
-        if (deg > kLeaf && !plan_for(kLeaf * 2)) return rc;
+        if (deg > kLeaf && !tables()) return rc;
         for (size_t d = deg; d > kLeaf; d /= 2)
             if (d != 256 && d != 512 && d != kOneLaunchMaxDeg && !plan_for(d)) return rc;
         return NFT_SUCCESS;
@@ -122,12 +133,11 @@ public:
     {
         if (rc != NFT_SUCCESS) return;
         if (deg == 256 || deg == 512 || deg == kOneLaunchMaxDeg) {   // one launch, entries transformed concurrently
-            NftPlan<BE> *tp = plan_for(kLeaf * 2);                  // any resident plan: its twiddle tables
-            if (!tp) return;
+            if (!tables()) return;
             PeelProdParams Q;
             std::memset(&Q, 0, sizeof(Q));
             Q.A = A; Q.B = B; Q.As = (long long)As; Q.Bs = (long long)Bs; Q.C = C; Q.Cs = (long long)Cs;
-            Q.tw = tp->tw_table(2 * deg);
+            Q.tw = tw.tw_table(2 * deg);
             Q.Ab = (long long)Ab; Q.Bb = (long long)Bb; Q.Cb = (long long)Cb;
             const int gy = (int)batch;
             if (deg == 256) be.template run<KPeelProduct<512>>(1, gy, Q);
@@ -204,55 +214,26 @@ template <class BE> class NftInverseDev {
 public:
     typedef std::complex<double> cd;
     BE &be;
-    NftPlan<BE> pl;              // twiddle tables only
-    DevArena<BE> mem;            // owns the DFT workspace below; the entry points' temporaries have arenas of their own
-    size_t Lcap = 0;
-    cplx *dY = nullptr, *dV = nullptr;
-    int *dstatus = nullptr;
+    DevArena<BE> mem;            // owns the tables and the workspace below; the entry points' temporaries have their own
+    NftTwiddles<BE> tw;
+    NftAnyDft<BE> ft;
+    int *dstatus = nullptr;      // the DFTs' status word, shared with the element-wise stages (bit 3: specfact)
     double *dacc = nullptr;
     size_t acc_cap = 0;
 
-    explicit NftInverseDev(BE &b) : be(b), pl(b), mem(b) {}
+    explicit NftInverseDev(BE &b) : be(b), mem(b), ft(b, tw) {}
 
-    static size_t dft_L(size_t n)
-    {
-        size_t L = nft_nextpow2(2 * n - 1);
-        if (L < 2 * (size_t)kRowChirp) L = 2 * (size_t)kRowChirp;
-        return L;
-    }
     // workspace for DFTs of up to nmax points
     int init(size_t nmax)
     {
-        const size_t L = dft_L(nmax);
-        if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
+        if (!tw.init(mem)) return NFT_EC_NOMEM;
+        const int rc = ft.init(mem, nmax, 1);
+        if (rc != NFT_SUCCESS) return rc;
+        dstatus = ft.status;
         acc_cap = (nmax + 255) / 256;
-        if (!(pl.init_twiddles_only() && mem.get(dY, L) && mem.get(dV, L) && mem.get(dstatus, 4)
-              && mem.get(dacc, acc_cap)))
-            return NFT_EC_NOMEM;
-        Lcap = L;
-        be.memset0(dstatus, 4 * sizeof(int));
-        return NFT_SUCCESS;
+        return mem.get(dacc, acc_cap) ? NFT_SUCCESS : NFT_EC_NOMEM;
     }
-    // out[k] = sum_n in[n] exp(sign * 2 pi i n k / n), un-normalised (fft_wrapper_execute_plan)
-    int dft(const cplx *d_in, cplx *d_out, size_t n, int sign)
-    {
-        const size_t L = dft_L(n);
-        if (L > Lcap) return NFT_EC_OTHER;
-        ChirpParams C;
-        std::memset(&C, 0, sizeof(C));
-        C.poly = d_in;
-        C.deg = (long long)n - 1;
-        C.batch = 1;
-        C.npoly = 1;
-        C.M = (long long)n;
-        C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = d_out;
-        pl.fill_chirp_geometry(C, L);
-        C.status = dstatus;
-        C.cstype = -1;
-        C.dft_len = (long long)n;
-        C.dft_sign = sign;
-        return pl.run_chirp(C);
-    }
+    int dft(const cplx *d_in, cplx *d_out, size_t n, int sign) { return ft.dft(d_in, d_out, n, 1, 1, sign); }
     void op(int code, size_t n, const cplx *a, const cplx *b, cplx *out, cplx *out2 = nullptr, double s0 = 0, double s1 = 0,
             double s2 = 0, long long i0 = 0, int kappa = 0, int K = 0, const cplx *bs = nullptr)
     {
@@ -627,25 +608,25 @@ public:
     const size_t os;             // oversampling factor of the spectral factorization
     const size_t K;              // bound states per signal
     const int ds_mode, ds_residues;
-    NftPlan<BE> pl;              // twiddle tables only
-    DevArena<BE> mem;            // owns the arrays of the continuous part below
+    DevArena<BE> mem;            // owns the tables and the arrays of the continuous part below
+    NftTwiddles<BE> tw;          // one set: the DFTs', the peeler's and its trees'
+    NftAnyDft<BE> ft;
     NftLayerPeelingDev<BE> lp;
     std::unique_ptr<NftInverseDiscBatch<BE>> ds;
-    size_t Mf = 0, Lcap = 0;
-    cplx *dY = nullptr, *dV = nullptr, *dc = nullptr, *dr = nullptr, *db = nullptr, *da = nullptr, *dtm = nullptr;
+    size_t Mf = 0;
+    cplx *dc = nullptr, *dr = nullptr, *db = nullptr, *da = nullptr, *dtm = nullptr;
     cplx *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
-    int *dchirp = nullptr;       // status word of the DFTs (DFT mode sets no bit)
 
     NftInverseBatch(BE &b, size_t D_, size_t M_, size_t B_, int cstype_, size_t os_, int modal, size_t K_ = 0,
                     int ds_mode_ = 0, int ds_residues_ = 0)
         : be(b), D(D_), M(M_), B(B_), cstype(cstype_), os(os_), K(K_), ds_mode(ds_mode_), ds_residues(ds_residues_),
-          pl(b), mem(b), lp(b, 1.0, 1, modal)
+          mem(b), ft(b, tw), lp(b, 1.0, 1, modal, &tw)
     {
         lp.batch = B;
     }
     size_t workspace_bytes() const
     {
-        return pl.mem.bytes + mem.bytes + lp.workspace_bytes() + (ds ? ds->mem.bytes : 0);
+        return mem.bytes + lp.workspace_bytes() + (ds ? ds->mem.bytes : 0);
     }
     int init()
     {
@@ -668,38 +649,18 @@ public:
     {
         const size_t deg = D;
         if (cstype != 0) Mf = NftInverseDev<BE>::specfact_len(cstype == 1 ? deg : D - 1, os);
-        const size_t L = NftInverseDev<BE>::dft_L(std::max(cstype == 2 ? D : M, Mf));
-        if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-        Lcap = L;
-        bool ok = pl.init_twiddles_only() && mem.get(dY, B * L) && mem.get(dV, L) && mem.get(dchirp, 4)
-                  && mem.get(dtm, B * 4 * (deg + 1));
+        if (!tw.init(mem)) return NFT_EC_NOMEM;
+        const int r = ft.init(mem, std::max(cstype == 2 ? D : M, Mf), B);
+        if (r != NFT_SUCCESS) return r;
+        bool ok = mem.get(dtm, B * 4 * (deg + 1));
         if (cstype != 2) ok = ok && mem.get(dc, B * M) && mem.get(dr, B * M) && mem.get(db, B * M);
         else ok = ok && mem.get(db, B * D) && mem.get(da, B * D);
         if (cstype != 0) ok = ok && mem.get(w0, B * Mf) && mem.get(w1, B * Mf) && mem.get(w2, B * Mf);
         if (!ok) return NFT_EC_NOMEM;
-        be.memset0(dchirp, 4 * sizeof(int));
         return lp.prepare(deg);
     }
-    // out[s*n + k] = sum_j in[s*n + j] exp(sign 2 pi i j k / n) for every signal s (NftInverseDev::dft, batched)
-    int dft(const cplx *d_in, cplx *d_out, size_t n, int sign)
-    {
-        const size_t L = NftInverseDev<BE>::dft_L(n);
-        if (L > Lcap) return NFT_EC_OTHER;
-        ChirpParams C;
-        std::memset(&C, 0, sizeof(C));
-        C.poly = d_in;
-        C.deg = (long long)n - 1;
-        C.batch = (int)B;
-        C.npoly = 1;
-        C.M = (long long)n;
-        C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = d_out;
-        pl.fill_chirp_geometry(C, L);
-        C.status = dchirp;
-        C.cstype = -1;
-        C.dft_len = (long long)n;
-        C.dft_sign = sign;
-        return pl.run_chirp(C);
-    }
+    // out[s*n + k] = sum_j in[s*n + j] exp(sign 2 pi i j k / n) for every signal s
+    int dft(const cplx *d_in, cplx *d_out, size_t n, int sign) { return ft.dft(d_in, d_out, n, B, 1, sign); }
     // body_inv_op over n elements of every signal; sa, sb, so: distances between the signals of a, b, out
     void op(int code, size_t n, const cplx *a, size_t sa, const cplx *b, size_t sb, cplx *out, size_t so,
             cplx *out2 = nullptr, size_t so2 = 0, double s0 = 0, double s1 = 0, double s2 = 0, long long i0 = 0,

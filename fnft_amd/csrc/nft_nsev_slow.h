@@ -2,7 +2,7 @@
 // CF4_2, CF4_3, CF5_3, CF6_4, ES4, TES4): `batch` signals of D samples on one xi-grid of M points, every array on the
 // device, nothing read back.  Per signal it computes what the reference's fnft_nsev writes to contspec (src/fnft_nsev.c:
 // 133-453, nsev_compute_contspec :763-891):
-//   band-limited shifts (the resampling front end of NftPlan, CF4_2 ... CF6_4) -> record kernel -> scatter kernel over
+//   band-limited shifts (NftResampler, CF4_2 ... CF6_4) -> record kernel -> scatter kernel over
 //   (xi tile, chunk, signal) -> [reduce kernel: chunk maps in groups, from 64 chunks on] -> combine kernel (chunk or
 //   group maps, phase factors, Richardson extrapolation, status)
 // With Richardson extrapolation the first three stages run a second time on every nskip-th sample inside the same call.
@@ -129,14 +129,16 @@ public:
     size_t nskip2 = 1, D2 = 0;        // Richardson pass: stride and kept grid points
     size_t L = 1, nchunk = 1, nchunk2 = 0, ntile = 1;
     size_t per = 1;                   // record values per grid point
-    std::unique_ptr<NftPlan<BE>> front;   // CF4_2 ... CF6_4 from kSlowDirectBelow samples on: resampling workspace
+    NftTwiddles<BE> tw;
+    NftResampler<BE> rs;              // CF4_2 ... CF6_4 from kSlowDirectBelow samples on (resample): the shifted copies
+    bool resample = false;
     cplx *wtab = nullptr, *rec = nullptr, *rec2 = nullptr, *cm = nullptr, *cm2 = nullptr, *cmr = nullptr, *cmr2 = nullptr;
     size_t gsize = 1;                 // chunk maps per group of the reduce stage (1: none)
     int *status = nullptr, *warn = nullptr;
     static constexpr size_t kMaxGroups = 0x7fffffff;
 
     NftSlowPlan(BE &be_, size_t D_, size_t M_, size_t batch_, const NftSlowOpts &o_)
-        : be(be_), mem(be_), D(D_), M(M_), batch(batch_), o(o_)
+        : be(be_), mem(be_), D(D_), M(M_), batch(batch_), o(o_), rs(be_, tw)
     {
         scheme = nft_slow_scheme(o.nse_disc);
         if (scheme < 0) return;
@@ -175,12 +177,11 @@ public:
         std::complex<double> w[16];
         shift = nft_slow_weights(scheme, w);
         if (shift != 0.0 && D >= (size_t)kSlowDirectBelow) {   // shorter signals: the prep kernel sums the shifts directly
-            const int akns = nft_nse_to_akns(21);   // the front end of 4SPLIT4B; only its resampler runs
-            front.reset(new NftPlan<BE>(be, 2 * D, 0, batch, akns, nft_akns_degree(akns)));
-            front->set_front(D, 1, 2);
-            front->front_only = true;
-            const int rc = front->init();
+            if (nft_tree_too_large(2 * D, 2)) return NFT_EC_NOT_YET_IMPLEMENTED;   // the limit of 4SPLIT4B's tree plan, kept
+            const int rc = rs.init(mem, D, batch);
             if (rc != NFT_SUCCESS) return rc;
+            if (!tw.init(mem)) return NFT_EC_NOMEM;   // last: the upload waits for the cleared status word
+            resample = true;
         }
         bool ok = mem.get(wtab, 16) && mem.get(rec, batch * D * per) && mem.get(cm, batch * nchunk * 4 * M)
                   && mem.get(status, batch) && mem.get(warn, batch);
@@ -195,19 +196,19 @@ public:
     size_t groups(size_t nc) const { return (nc + gsize - 1) / gsize; }
 
     // the workspace back before the plan goes out of scope (the destructor does the same); init() again before reuse
-    void destroy() { front.reset(); mem.clear(); }
+    void destroy() { resample = false; mem.clear(); }
 
-    size_t workspace_bytes() const { return mem.bytes + (front ? front->mem.bytes : 0); }
+    size_t workspace_bytes() const { return mem.bytes; }
 
     // records and chunk maps of one pass: Dk kept grid points, every nskip-th sample, interval Tk
     int pass(SlowParams P, const cplx *d_q, size_t Dk, size_t nskip, const double Tk[2], double eps_in, bool first,
              cplx *rec_k, cplx *cm_k, size_t nchunk_k, cplx *cmr_k)
     {
-        if (front) {
+        if (resample) {
             ResampleParams R;
-            const int rc = front->run_resample(d_q, shift * (double)nskip, warn, 1, first, R);
+            const int rc = rs.run(d_q, shift * (double)nskip / (double)D, warn, 1, first, R);
             if (rc != NFT_SUCCESS) return rc;
-            P.Q12 = front->rsQ12;
+            P.Q12 = rs.Q12;
         }
         P.dsteps = shift * (double)nskip;
         P.rec = rec_k;

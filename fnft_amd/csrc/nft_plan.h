@@ -1,5 +1,6 @@
 // nft_plan.h -- back-end independent host logic of the fnft_nsev continuous-spectrum path:
-// workspace layout in HBM, level schedule of the product tree, chirp z-transform set-up.
+// workspace layout in HBM, level schedule of the product tree, chirp z-transform set-up.  The twiddle tables, the chirp
+// launches and the resampler of the 4SPLIT4A/B front end are parts of their own (nft_twiddles.h, nft_chirp.h).
 //
 // Mirrors the control flow of the reference (file:line relative to the FNFT source tree):
 //   fnft_nsev_base           src/fnft_nsev.c:458-565
@@ -19,28 +20,8 @@
 #include <cstring>
 #include <vector>
 
-#include "nft_arena.h"
-#include "nft_dispatch.h"
+#include "nft_chirp.h"
 #include "nft_schemes.h"
-
-// return codes (include/fnft_errwarn.h:44-94)
-enum {
-    NFT_SUCCESS = 0, NFT_EC_NOMEM = 1, NFT_EC_INVALID_ARGUMENT = 2, NFT_EC_DIV_BY_ZERO = 3,
-    NFT_EC_OTHER = 5, NFT_EC_NOT_YET_IMPLEMENTED = 6
-};
-
-inline size_t nft_nextpow2(size_t n)
-{
-    size_t r = 1;
-    while (r < n) r *= 2;
-    return r;
-}
-inline int nft_log2(size_t n)
-{
-    int l = 0;
-    while (((size_t)1 << l) < n) l++;
-    return l;
-}
 
 // fnft__akns_discretization.c:29-67 restricted to what the coefficient kernel implements
 inline int nft_akns_degree(int akns_disc)
@@ -86,20 +67,6 @@ inline int nft_nse_upsampling(int nse_disc) { return (nse_disc == 20 || nse_disc
 // fnft__akns_discretization.c:157-192: order used by Richardson extrapolation
 inline int nft_nse_method_order(int nse_disc) { return (nse_disc == 20 || nse_disc == 21) ? 4 : 2; }
 
-// log of a complex number through libm's clog -- the routine glibc's cpow() (which the reference
-// calls for every chirp factor, src/private/fnft__poly_chirpz.c:69,77,81,95) is built on.  It keeps
-// the tiny real part log|z| of a z that is on the unit circle only up to rounding; the generic
-// std::log(std::complex) of some C++ runtimes returns log(hypot) = 0 there, which changes
-// |z|^(n^2/2) by up to 1e-9 at n = 2^16.
-inline std::complex<double> nft_clog(std::complex<double> z)
-{
-    __complex__ double zz;
-    __real__ zz = z.real();
-    __imag__ zz = z.imag();
-    const __complex__ double r = __builtin_clog(zz);
-    return std::complex<double>(__real__ r, __imag__ r);
-}
-
 // transform length used for a product of two degree-d polynomials
 inline size_t nft_product_len(size_t d)
 {
@@ -107,13 +74,12 @@ inline size_t nft_product_len(size_t d)
     return (p == 2 * d) ? p : nft_nextpow2(2 * d + 1);
 }
 
-constexpr int kFineLog2 = 12;           // master twiddle: NMAX = 2^24
-constexpr int kMaxTwTable = 16384;      // per-length tables up to this length (longest column transform; the real path's
-                                        // quarter-step tables of 4*N1 entries)
 constexpr size_t kMaxSplitTree = (size_t)kRowTree * 8192;    // largest column transform: 8192 (N up to 2^24)
-constexpr size_t kMaxSplitChirp = (size_t)kRowChirp * 8192;  // chirp length up to 2^25 (any-length DFTs up to 2^24 points)
-// fine tables of the two master twiddle pairs: 2^12 entries exp(-2 pi i j/2^24), then 2^13 entries exp(-2 pi i j/2^26)
-constexpr size_t kTwLoEntries = ((size_t)1 << kFineLog2) + ((size_t)1 << (kFineLog2 + 1));
+inline bool nft_tree_too_large(size_t D, int deg0)   // the top product of D matrices of degree deg0: beyond the split limit
+{
+    const size_t Dpad = nft_nextpow2(D);
+    return Dpad > 1 && nft_product_len(Dpad / 2 * (size_t)deg0) > kMaxSplitTree;
+}
 
 // ---- polynomials at arbitrary points (KPolyEval, KPolyJoin) ------------------------------------------------------------
 // Segments of the coefficient range: a call with few points and a long polynomial must still fill the chip.  One
@@ -185,6 +151,9 @@ public:
     DevArena<BE> mem;        // owns every device buffer below; mem.bytes is the plan's workspace size
     size_t D, M, batch;
     int akns_disc, deg0;
+    NftTwiddles<BE> own_tw;          // allocated by init() unless the plan borrows its owner's
+    const NftTwiddles<BE> &tw;
+    NftResampler<BE> rs;             // ups == 2: the band-limited shifts of the 4SPLIT4A/B front end
     size_t Dpad, plane, n0;
 
     // device buffers
@@ -217,19 +186,13 @@ public:
     // ups preprocessed samples per kept step; D = ups * Dsub matrices enter the tree
     size_t Din = 0, nskip = 1;
     int ups = 1;
-    cplx *qpre = nullptr, *rsX = nullptr, *rsX12 = nullptr, *rsQ12 = nullptr, *rsY = nullptr, *rsV = nullptr;
-    size_t Lr = 0;
+    cplx *qpre = nullptr;
     cplx *Y = nullptr, *Z = nullptr, *Z2 = nullptr;   // Z ping-pongs: spectral doubling reads the previous level's Z
     cplx *chY = nullptr, *chV = nullptr;
     cplx *chVS = nullptr;                 // cached spectrum of the chirp filter
     double vs_key[4] = {0, 0, 0, 0};      // log W (re, im), M, deg+1 it was computed for
     bool vs_valid = false;
     cplx *tm_out = nullptr;
-    cplx *twtab = nullptr;   // concatenated tables for N = 2,4,...,kMaxTwTable
-    cplx *twlo = nullptr;    // exp(-2 pi i j / 2^24), j < 4096
-    // lengths 3*2^b (column transforms of the real path, nft_real.h): tables for L = 3, 6, ..., 3*2^kTw3MaxLog back to
-    // back (offset L - 3), and the fine table exp(-2 pi i j/(3*2^22)), j < 4096, of the master pair for 3*2^22
-    cplx *tw3tab = nullptr, *twlo3 = nullptr;
     size_t Lc = 0;           // chirp transform length
     int cur = 0;             // index of the body/tail/scale set holding the current level
     bool tree_valid = false;
@@ -280,55 +243,21 @@ public:
     int tune_fuse_root = 1;  // 0: the tree always runs its last inverse column pass itself (A/B runs of ChirpParams::root_fused)
     int dbg_flags = 0;       // timing ablation: only builds with -DFNFT_AMD_ABLATION ever set it (hip_backend.hip)
 
-    NftPlan(BE &be_, size_t D_, size_t M_, size_t batch_, int akns_disc_, int deg0_)
-        : be(be_), mem(be_), D(D_), M(M_), batch(batch_), akns_disc(akns_disc_), deg0(deg0_)
+    // borrowed: the twiddle tables of the class this plan is a part of (KdV plans: with the lengths 3*2^b); without it the
+    // plan allocates its own
+    NftPlan(BE &be_, size_t D_, size_t M_, size_t batch_, int akns_disc_, int deg0_, const NftTwiddles<BE> *borrowed = nullptr)
+        : be(be_), mem(be_), D(D_), M(M_), batch(batch_), akns_disc(akns_disc_), deg0(deg0_), tw(borrowed ? *borrowed : own_tw),
+          rs(be_, tw)
     {
         Dpad = nft_nextpow2(D);
         n0 = batch * Dpad;
         plane = n0 * (size_t)deg0;
     }
-    // a plan that exists only for its twiddle tables (init_twiddles_only): the stand-alone chirp z-transforms and DFTs
-    explicit NftPlan(BE &be_) : NftPlan(be_, 2, 0, 1, 0, 1) {}
 
     // fnft__nse_discretization.c:419-427: samples kept when every nskip-th of Din is used
     static size_t sub_count(size_t Din_, size_t nskip_) { return (size_t)std::llround((double)Din_ / (double)nskip_); }
     // call before init(): this plan was constructed with D = ups_ * sub_count(Din_, nskip_)
     void set_front(size_t Din_, size_t nskip_, int ups_) { Din = Din_; nskip = nskip_; ups = ups_; }
-    // call before init(): only run_resample will be used, so neither the tree's nor the evaluation's buffers are made
-    bool front_only = false;
-
-    const cplx *tw_table(size_t N) const
-    {   // tables are stored back to back: N=2 at offset 0, N=4 at 2, N=8 at 6, ... offset = N-2
-        return twtab + (N - 2);
-    }
-    static constexpr int kTw3MaxLog = 12;
-    const cplx *tw3_table(size_t L) const { return tw3tab + (L - 3); }
-    BigTwiddle big_tw3(size_t N) const   // N = 3*2^a <= 3*2^22
-    {
-        BigTwiddle t;
-        t.hi = tw3_table((size_t)3 << 10);   // exp(-2 pi i jh/3072)
-        t.lo = twlo3;
-        t.fine_log2 = kFineLog2;
-        t.shift = 22 - nft_log2(N / 3);
-        return t;
-    }
-    BigTwiddle big_tw(size_t N) const
-    {
-        BigTwiddle t;
-        if (N > ((size_t)1 << (2 * kFineLog2))) {   // 2^24 < N <= 2^26: the pair with 2^13-entry tables
-            t.hi = tw_table((size_t)1 << (kFineLog2 + 1));
-            t.lo = twlo + ((size_t)1 << kFineLog2);
-            t.fine_log2 = kFineLog2 + 1;
-            t.shift = 2 * (kFineLog2 + 1) - nft_log2(N);
-            return t;
-        }
-        t.hi = tw_table((size_t)1 << kFineLog2);   // exp(-2 pi i jh / 2^FINE)
-        t.lo = twlo;
-        t.fine_log2 = kFineLog2;
-        t.shift = 2 * kFineLog2 - nft_log2(N);
-        return t;
-    }
-
     // largest pair product done by one workgroup.  General (4-entry) form: 2048 -- a 4096-point pair needs 8 + 4
     // transforms of 16 points per lane in one workgroup (616 B of scratch per lane, 75 us for ONE pair); as a split
     // transform of 4 columns x 1024-point rows it is three small launches (~30 us for one pair, rows over 4 CUs)
@@ -341,20 +270,18 @@ public:
         if (ups == 1 && (nskip != 1 || Din != D)) return NFT_EC_NOT_YET_IMPLEMENTED;
         if (ups == 2 && (Din <= 2 || D != 2 * sub_count(Din, nskip))) return NFT_EC_INVALID_ARGUMENT;
         // largest product transform of the tree and chirp length must be within the split limits
-        const size_t topN = (Dpad > 1) ? nft_product_len(Dpad / 2 * (size_t)deg0) : 2;
-        if (topN > kMaxSplitTree) return NFT_EC_NOT_YET_IMPLEMENTED;
+        if (nft_tree_too_large(D, deg0)) return NFT_EC_NOT_YET_IMPLEMENTED;
         bool ok = true;
-        for (int i = 0; i < 2 && !front_only; i++) {
+        for (int i = 0; i < 2; i++) {
             ok = ok && mem.get(body[i], 4 * plane) && mem.get(tail[i], 4 * n0) && mem.get(scale[i], n0)
                  && mem.get(wexp[i], n0);
         }
         {   // split levels hold at most n0*deg0/2048 matrices, kMax2Slots slots each
             const size_t nm = n0 * (size_t)deg0 / 32 + 4 * (size_t)kMax2Slots;
-            if (!front_only) ok = ok && mem.get(max2[0], nm) && mem.get(max2[1], nm);
-            ok = ok && mem.get(status, 4);
+            ok = ok && mem.get(max2[0], nm) && mem.get(max2[1], nm) && mem.get(status, 4);
             if (ok) be.memset0(status, 4 * sizeof(int));
         }
-        if (!front_only) {   // scratch of the split transforms: 4*n_in polynomials of N forward, 4*n_out inverse,
+        {   // scratch of the split transforms: 4*n_in polynomials of N forward, 4*n_out inverse,
             // maximised over the levels that use them (N can exceed 2d when d is not 2^k)
             size_t needY = 0, needZ = 0, n = n0, d = (size_t)deg0;
             while (n / batch > 1) {
@@ -368,16 +295,14 @@ public:
             }
             if (needY) ok = ok && mem.get(Y, needY) && mem.get(Z, needZ) && mem.get(Z2, needZ);
         }
-        if (M > 0 && !front_only) {
-            const size_t Np = D * (size_t)deg0 + 1;
-            Lc = nft_nextpow2(Np + M - 1);
-            if (Lc < 2 * (size_t)kRowChirp) Lc = 2 * (size_t)kRowChirp;
+        if (M > 0) {
+            Lc = nft_chirp_len(D * (size_t)deg0 + 1 + M - 1);
             if (Lc > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
             ok = ok && mem.get(chY, batch * 2 * Lc) && mem.get(chV, Lc) && mem.get(chVS, Lc);
         }
-        if (!front_only) ok = ok && mem.get(tm_out, batch * 4 * (D * (size_t)deg0 + 1));
-        ok = ok && mem.get(twtab, (size_t)2 * kMaxTwTable) && mem.get(twlo, kTwLoEntries);
-        if (kdv) ok = ok && mem.get(tw3tab, (size_t)3 << (kTw3MaxLog + 1)) && mem.get(twlo3, (size_t)1 << kFineLog2);
+        ok = ok && mem.get(tm_out, batch * 4 * (D * (size_t)deg0 + 1));
+        if (&tw == &own_tw) ok = ok && own_tw.init(mem, kdv);
+        else if (!tw.ready() || (kdv && !tw.tw3tab)) return NFT_EC_INVALID_ARGUMENT;
         if (kdv) {
             ok = ok && mem.get(rneg, batch * D);
             if (ok) {
@@ -386,12 +311,9 @@ public:
             }
         }
         if (ups == 2) {
-            Lr = nft_nextpow2(2 * Din - 1);
-            if (Lr < 2 * (size_t)kRowChirp) Lr = 2 * (size_t)kRowChirp;
-            if (Lr > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-            if (!front_only) ok = ok && mem.get(qpre, batch * D);
-            ok = ok && mem.get(rsX, batch * Din) && mem.get(rsX12, batch * 2 * Din)
-                 && mem.get(rsQ12, batch * 2 * Din) && mem.get(rsY, batch * 2 * Lr) && mem.get(rsV, Lr);
+            ok = ok && mem.get(qpre, batch * D);
+            const int rc = ok ? rs.init(mem, Din, batch, status) : NFT_EC_NOMEM;
+            if (rc != NFT_SUCCESS) return rc;
         }
         CoeffProgramHost prog;
         const bool has_prog = akns_disc >= 11 && akns_disc <= 18;   // 2SPLIT5A .. 2SPLIT8B
@@ -409,74 +331,12 @@ public:
             prog_nB = (int)prog.bfrac.size();
             prog_maxf = prog.maxf;
         }
-        upload_twiddles();
+        if (&tw != &own_tw) (void)be.sync();   // no upload of own tables has waited for the cleared status word: wait here
         return NFT_SUCCESS;
     }
 
     // the workspace back before the plan goes out of scope (the destructor does the same); the plan is not usable after
     void destroy() { mem.clear(); }
-
-    // instead of init(): the two master twiddle tables and nothing else (fill_chirp_geometry, run_chirp, tw_table)
-    bool init_twiddles_only()
-    {
-        if (!(mem.get(twtab, (size_t)2 * kMaxTwTable) && mem.get(twlo, kTwLoEntries))) return false;
-        upload_twiddles();
-        return true;
-    }
-
-    // host copies of the tables, computed once per process (long-double sines: ~2 ms per plan otherwise)
-    struct HostTables {
-        std::vector<cplx> tw, lo, tw3, lo3;
-        HostTables()
-        {
-            const long double tau = 6.283185307179586476925286766559005768L;
-            tw.resize((size_t)2 * kMaxTwTable);
-            for (size_t N = 2; N <= (size_t)kMaxTwTable; N *= 2)
-                for (size_t j = 0; j < N; j++) {
-                    const long double a = -tau * (long double)j / (long double)N;
-                    tw[N - 2 + j] = cmake((double)cosl(a), (double)sinl(a));
-                }
-            lo.resize(kTwLoEntries);
-            const long double nmax = (long double)((size_t)1 << (2 * kFineLog2));
-            for (size_t j = 0; j < ((size_t)1 << kFineLog2); j++) {
-                const long double a = -tau * (long double)j / nmax;
-                lo[j] = cmake((double)cosl(a), (double)sinl(a));
-            }
-            for (size_t j = 0; j < ((size_t)1 << (kFineLog2 + 1)); j++) {
-                const long double a = -tau * (long double)j / (4.0L * nmax);
-                lo[((size_t)1 << kFineLog2) + j] = cmake((double)cosl(a), (double)sinl(a));
-            }
-            tw3.resize((size_t)3 << (kTw3MaxLog + 1));
-            for (int b = 0; b <= kTw3MaxLog; b++) {
-                const size_t Lb = (size_t)3 << b;
-                for (size_t j = 0; j < Lb; j++) {
-                    const long double a = -tau * (long double)j / (long double)Lb;
-                    tw3[Lb - 3 + j] = cmake((double)cosl(a), (double)sinl(a));
-                }
-            }
-            lo3.resize((size_t)1 << kFineLog2);
-            const long double nmax3 = 3.0L * (long double)((size_t)1 << 22);
-            for (size_t j = 0; j < lo3.size(); j++) {
-                const long double a = -tau * (long double)j / nmax3;
-                lo3[j] = cmake((double)cosl(a), (double)sinl(a));
-            }
-        }
-    };
-    static const HostTables &host_tables()
-    {
-        static const HostTables t;
-        return t;
-    }
-    void upload_twiddles()
-    {
-        const HostTables &H = host_tables();
-        be.h2d(twtab, H.tw.data(), H.tw.size() * sizeof(cplx));
-        be.h2d(twlo, H.lo.data(), H.lo.size() * sizeof(cplx));
-        if (tw3tab) {
-            be.h2d(tw3tab, H.tw3.data(), H.tw3.size() * sizeof(cplx));
-            be.h2d(twlo3, H.lo3.data(), H.lo3.size() * sizeof(cplx));
-        }
-    }
 
     // ---- front end: fnft__nse_discretization_preprocess_signal (:386-656) + level 0 ------------
     // T: interval of the Din input samples.  Tsub: interval of the kept steps (fnft_nsev.c:381-384),
@@ -493,59 +353,9 @@ public:
         Tsub[0] = T[0];
         Tsub[1] = T[0] + (double)((Dsub - 1) * nskip) * eps_in;
         const double eps_t = (Tsub[1] - Tsub[0]) / (double)(Dsub - 1);
-        // shifts -/+ sqrt(3)/6 of the kept step (:482-485), then the weighted pairs (:493-499)
-        const double scl = std::sqrt(3.0) / 6.0;
-        ResampleParams R;
-        const int rc = run_resample(d_q, scl * (double)nskip, status, 0, true, R);
+        const int rc = rs.run_4split4(d_q, nskip, Dsub, qpre, status);
         if (rc != NFT_SUCCESS) return rc;
-        R.qpre = qpre;
-        R.Dsub = (long long)Dsub; R.nskip = (long long)nskip;
-        R.w0 = 0.25 + scl;
-        R.w1 = 0.25 - scl;
-        be.template run<KResampleCombine>((int)((batch * Dsub + 255) / 256), 1, R);
         return run_coeffs(qpre, nullptr, eps_t, kappa, false);
-    }
-
-    // fnft__misc_resample for every signal of the batch and the two shifts -/+ delta_steps input steps: leaves the
-    // shifted copies times Din in rsQ12 (signal b: rows 2b and 2b + 1).  fwd: transform the signal first and check its
-    // band (bit 2 of wstat[b * wstride]); without it the spectrum of the last call with the same signal is used again.
-    int run_resample(const void *d_q, double delta_steps, int *wstat, long long wstride, bool fwd, ResampleParams &R)
-    {
-        // forward DFT of every signal (fnft__misc.c:366-370)
-        ChirpParams C;
-        std::memset(&C, 0, sizeof(C));
-        C.poly = (const cplx *)d_q;
-        C.deg = (long long)Din - 1;
-        C.batch = (int)batch;
-        C.npoly = 1;
-        C.M = (long long)Din;
-        C.Ybuf = rsY; C.Vbuf = rsV; C.Hbuf = rsX;
-        fill_chirp_geometry(C, Lr);
-        C.status = status;
-        C.cstype = -1;
-        C.dft_len = (long long)Din;
-        C.dft_sign = -1;
-        int rc = NFT_SUCCESS;
-        if (fwd) {
-            rc = run_chirp(C);
-            if (rc != NFT_SUCCESS) return rc;
-        }
-        // phase ramps for the two shifts (fnft__misc.c:383-393)
-        R.X = rsX; R.X12 = rsX12; R.Q12 = rsQ12; R.qpre = nullptr;
-        R.Din = (long long)Din; R.Dsub = 0; R.nskip = 1;
-        R.batch = (int)batch;
-        R.delta_over_span = delta_steps / (double)Din;
-        R.w0 = R.w1 = 0.0;
-        R.status = wstat;
-        R.sstat = wstride;
-        if (fwd) be.template run<KBandCheck>((int)batch, 1, R);     // fnft__misc.c:371-381 (warning only)
-        be.template run<KResamplePhase>((int)((batch * Din + 255) / 256), 1, R);
-        // inverse DFTs (:395-399)
-        C.poly = rsX12;
-        C.npoly = 2;
-        C.Hbuf = rsQ12;
-        C.dft_sign = +1;
-        return run_chirp(C);
     }
 
     // ---- level 0 from samples (fnft__akns_fscatter.c:116-917) --------------------------------
@@ -756,7 +566,7 @@ public:
         // degrees 3*2^a: the split levels take columns of 3*K rows of kRowGen points -- transform length M = d exactly
         // (nft_real.h) -- when the last level's column length is instantiated
         bool r3 = false;
-        if (tw3tab) {
+        if (tw.tw3tab) {
             size_t odd = start_d;
             while (odd % 2 == 0) odd /= 2;
             const size_t dtop = start_d * (start_n / batch) / 2;   // degree of the last level's factors
@@ -777,23 +587,23 @@ public:
                 G.N2 = kRowGen;
                 G.N1 = (int)(d / (size_t)kRowGen);   // 3*K
                 const size_t K = (size_t)G.N1 / 3;
-                G.btw = big_tw3(4 * d);              // row twiddle w_{4M}^{(4 k1 - 1) n2}, M = d
+                G.btw = tw.big_tw3(4 * d);              // row twiddle w_{4M}^{(4 k1 - 1) n2}, M = d
                 G.rtwist = 1;
                 G.row_mod = 4ull * (unsigned long long)d;
-                G.tw1 = tw_table(K >= 2 ? K : 2);
-                G.tw2 = tw_table((size_t)G.N2);
-                G.tw1x2 = tw_table(2 * K);
-                G.tw3 = tw3_table((size_t)G.N1);
-                G.tw3x2 = tw3_table((size_t)2 * G.N1);
-                G.twq = tw3_table((size_t)4 * G.N1);
-                G.twq2 = ((size_t)8 * G.N1 <= ((size_t)3 << kTw3MaxLog)) ? tw3_table((size_t)8 * G.N1) : nullptr;
+                G.tw1 = tw.tw_table(K >= 2 ? K : 2);
+                G.tw2 = tw.tw_table((size_t)G.N2);
+                G.tw1x2 = tw.tw_table(2 * K);
+                G.tw3 = tw.tw3_table((size_t)G.N1);
+                G.tw3x2 = tw.tw3_table((size_t)2 * G.N1);
+                G.twq = tw.tw3_table((size_t)4 * G.N1);
+                G.twq2 = ((size_t)8 * G.N1 <= ((size_t)3 << kTw3MaxLog)) ? tw.tw3_table((size_t)8 * G.N1) : nullptr;
                 G.y_unscaled = w.y_from_bridge ? 1 : 0;
                 const bool next_split = (n / 2 / batch > 1) && K <= (size_t)kR3BridgeMaxK;
                 ok = run_split_level(w, G, dispatch_r3col_fwd<BE>, dispatch_r3bridge<BE>, dispatch_r3col_inv<BE>,
                                      next_split);
             } else if (M <= (size_t)kRealFusedMaxM) {
-                L.tw = tw_table(M);
-                L.twx = tw_table(4 * M);
+                L.tw = tw.tw_table(M);
+                L.twx = tw.tw_table(4 * M);
                 ok = dispatch_rpair(be, L, (int)M);
             } else {
                 BigLevel G;
@@ -804,13 +614,13 @@ public:
                 G.N2 = row_len_gen(M);
                 G.N1 = (int)(M / (size_t)G.N2);
                 if (4 * (size_t)G.N1 > (size_t)kMaxTwTable) return NFT_EC_NOT_YET_IMPLEMENTED;
-                G.btw = big_tw(4 * M);   // row twiddle w_{4M}^{(4 k1 - 1) n2}
+                G.btw = tw.big_tw(4 * M);   // row twiddle w_{4M}^{(4 k1 - 1) n2}
                 G.rtwist = 1;
-                G.tw1 = tw_table((size_t)G.N1);
-                G.tw2 = tw_table((size_t)G.N2);
-                G.tw1x2 = tw_table((size_t)2 * G.N1);
-                G.twq = tw_table((size_t)4 * G.N1);
-                G.twq2 = (8 * (size_t)G.N1 <= (size_t)kMaxTwTable) ? tw_table((size_t)8 * G.N1) : nullptr;
+                G.tw1 = tw.tw_table((size_t)G.N1);
+                G.tw2 = tw.tw_table((size_t)G.N2);
+                G.tw1x2 = tw.tw_table((size_t)2 * G.N1);
+                G.twq = tw.tw_table((size_t)4 * G.N1);
+                G.twq2 = (8 * (size_t)G.N1 <= (size_t)kMaxTwTable) ? tw.tw_table((size_t)8 * G.N1) : nullptr;
                 G.y_unscaled = w.y_from_bridge ? 1 : 0;
                 const bool next_split = (n / 2 / batch > 1) && G.N1 <= kRBridgeMaxN1
                                         && row_len_gen(2 * M) == G.N2;
@@ -840,7 +650,7 @@ public:
         while (n / batch > 1) {
             TreeLevel L = tree_level(w, n, d, ne, dbg_flags);
             const size_t N = nft_product_len(d);
-            L.tw = (N <= (size_t)kMaxTwTable) ? tw_table(N) : nullptr;
+            L.tw = (N <= (size_t)kMaxTwTable) ? tw.tw_table(N) : nullptr;
             bool ok;
             // consecutive fused levels of the symmetric form in one launch: as many as fit (<= 3)
             int stages = 1;
@@ -852,7 +662,7 @@ public:
                 leaf_pending = false;
             }
             if (stages > 1) {
-                for (int s = 0; s < stages; s++) L.twm[s] = tw_table(N << s);
+                for (int s = 0; s < stages; s++) L.twm[s] = tw.tw_table(N << s);
                 if (leaf_pending) {
                     LeafMultiParams Q;
                     Q.lp = leaf_lp;
@@ -881,11 +691,11 @@ public:
                 G.y_split = w.y_from_bridge ? 1 : 0;   // every bridge doubles: Y holds the odd rows only
                 G.N2 = (ne == 4) ? row_len_gen(N) : kRowTree;
                 G.N1 = (int)(N / (size_t)G.N2);
-                G.btw = big_tw(N);
-                G.tw1 = (G.N1 >= 2) ? tw_table((size_t)G.N1) : nullptr;
-                G.tw2 = tw_table((size_t)G.N2);
-                G.tw1x2 = tw_table((size_t)2 * G.N1);
-                G.btw2 = big_tw(2 * N);
+                G.btw = tw.big_tw(N);
+                G.tw1 = (G.N1 >= 2) ? tw.tw_table((size_t)G.N1) : nullptr;
+                G.tw2 = tw.tw_table((size_t)G.N2);
+                G.tw1x2 = tw.tw_table((size_t)2 * G.N1);
+                G.btw2 = tw.big_tw(2 * N);
                 G.y_unscaled = w.y_from_bridge ? 1 : 0;
                 // first split level of the symmetric form: a length-4 column transform of two non-zero rows is done
                 // by the row kernel on the fly (saves the column launch and its 32 + 64 MB)
@@ -990,16 +800,6 @@ public:
         int normalization_flag;
     };
 
-    void fill_chirp_geometry(ChirpParams &C, size_t L)
-    {
-        C.N2 = kRowChirp;
-        C.N1 = (int)(L / kRowChirp);
-        C.btw = big_tw(L);
-        C.tw1 = tw_table((size_t)C.N1);
-        C.tw2 = tw_table(kRowChirp);
-        C.jobs_per_group = 2;
-    }
-
     int run_contspec(void *d_contspec, const Contspec &cs) { return run_contspec_impl(d_contspec, cs, nullptr, 0); }
 
     // nsev_compute_contspec (src/fnft_nsev.c:744-891) on a transfer matrix the CALLER supplies: d_tm holds, per
@@ -1046,7 +846,7 @@ public:
         C.logW[0] = lV.real(); C.logW[1] = lV.imag();
         C.M = (long long)M;
         C.Ybuf = chY; C.Vbuf = chV; C.Hbuf = nullptr;
-        fill_chirp_geometry(C, Lc);
+        fill_chirp_geometry(tw, C, Lc);
         C.contspec = (cplx *)d_contspec;
         C.W = from_tm ? wuser : wexp[cur];
         C.status = status;
@@ -1092,7 +892,7 @@ public:
         C.logW[0] = lV.real(); C.logW[1] = lV.imag();
         C.M = (long long)M;
         C.Ybuf = chY; C.Vbuf = chV;
-        fill_chirp_geometry(C, Lc);
+        fill_chirp_geometry(tw, C, Lc);
         C.contspec = (cplx *)d_contspec;
         C.W = wexp[cur];
         C.status = status;
@@ -1145,53 +945,38 @@ public:
         const bool hit = vs_valid && std::memcmp(key, vs_key, sizeof(key)) == 0;
         C.VS = chVS;
         C.v_mode = hit ? 2 : 1;
-        const int rc = run_chirp(C);
+        const int rc = run_chirp(be, C);
         if (rc == NFT_SUCCESS) { std::memcpy(vs_key, key, sizeof(key)); vs_valid = true; }
         return rc;
     }
 
-    int run_chirp(const ChirpParams &C)
+    // stand-alone chirp z-transform of one host polynomial (fnft__poly_chirpz.c:33-105): no plan, tables and workspace
+    // from a temporary arena.  d_out != NULL: the M values stay on the device (d_out), `result` is not touched
+    static int chirpz_host(BE &be, size_t deg, const std::complex<double> *p, std::complex<double> A,
+                           std::complex<double> Wc, size_t Mo, std::complex<double> *result, cplx *d_out = nullptr)
     {
-        if (!dispatch_chirp_col_fwd(be, C)) return NFT_EC_NOT_YET_IMPLEMENTED;
-        const int njobs = C.batch * C.npoly;
-        be.template run<KChirpRows>(C.N1, (njobs + C.jobs_per_group - 1) / C.jobs_per_group, C);
-        if (!dispatch_chirp_col_inv(be, C)) return NFT_EC_NOT_YET_IMPLEMENTED;
-        return NFT_SUCCESS;
-    }
-
-    // stand-alone chirp z-transform of one host polynomial (fnft__poly_chirpz.c:33-105)
-    // d_out != NULL: the M values stay on the device (d_out), `result` is not touched
-    static int chirpz_host(BE &be, size_t deg, const std::complex<double> *p,
-                           std::complex<double> A, std::complex<double> Wc, size_t Mo,
-                           std::complex<double> *result, cplx *d_out = nullptr)
-    {
-        NftPlan pl(be);
         DevArena<BE> tmp(be);
-        size_t L = nft_nextpow2(deg + 1 + Mo - 1);
-        if (L < 2 * (size_t)kRowChirp) L = 2 * (size_t)kRowChirp;
+        NftTwiddles<BE> tabs;
+        const size_t L = nft_chirp_len(deg + 1 + Mo - 1);
         if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
         cplx *dp = nullptr, *dY = nullptr, *dV = nullptr, *dH = nullptr;
         int *dstatus = nullptr;
-        const bool ok = pl.init_twiddles_only() && tmp.get(dp, deg + 1) && tmp.get(dY, L) && tmp.get(dV, L)
-                        && tmp.get(dH, Mo) && tmp.get(dstatus, 4);
+        const bool ok = tabs.init(tmp) && tmp.get(dp, deg + 1) && tmp.get(dY, L) && tmp.get(dV, L) && tmp.get(dH, Mo)
+                        && tmp.get(dstatus, 4);
         if (!ok) return NFT_EC_NOMEM;
         be.h2d(dp, p, (deg + 1) * sizeof(cplx));
         be.memset0(dstatus, 4 * sizeof(int));
         const std::complex<double> lA = nft_clog(A), lW = nft_clog(Wc);
         ChirpParams C;
         std::memset(&C, 0, sizeof(C));
-        C.poly = dp;
-        C.deg = (long long)deg;
-        C.batch = 1;
-        C.npoly = 1;
+        C.poly = dp; C.deg = (long long)deg; C.M = (long long)Mo;
+        C.batch = 1; C.npoly = 1;
         C.logA[0] = lA.real(); C.logA[1] = lA.imag();
         C.logW[0] = lW.real(); C.logW[1] = lW.imag();
-        C.M = (long long)Mo;
         C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = d_out ? d_out : dH;
-        pl.fill_chirp_geometry(C, L);
-        C.status = dstatus;
-        C.cstype = -1;
-        int rc = pl.run_chirp(C);
+        fill_chirp_geometry(tabs, C, L);
+        C.status = dstatus; C.cstype = -1;
+        int rc = run_chirp(be, C);
         if (rc == NFT_SUCCESS) {
             if (!d_out) be.d2h(result, dH, Mo * sizeof(cplx));
             rc = be.sync();
@@ -1199,57 +984,25 @@ public:
         return rc;
     }
 
-    // stand-alone band-limited shift of one host signal by delta (fnft__misc.c:326-407): DFT of any length
-    // (chirp kernels in DFT mode), phase ramp exp(2 pi i delta f), inverse DFT, 1/D
+    // stand-alone band-limited shift of one host signal by delta (fnft__misc.c:326-407), 1/D included: a batch-1
+    // resampler over a temporary arena
     static int resample_host(BE &be, size_t Dn, double eps_t, const std::complex<double> *q, double delta,
                              std::complex<double> *q_new, int *warn_not_bandlimited = nullptr)
     {
-        NftPlan pl(be);
         DevArena<BE> tmp(be);
-        size_t L = nft_nextpow2(2 * Dn - 1);
-        if (L < 2 * (size_t)kRowChirp) L = 2 * (size_t)kRowChirp;
-        if (L > kMaxSplitChirp) return NFT_EC_NOT_YET_IMPLEMENTED;
-        cplx *dq = nullptr, *dX = nullptr, *dX12 = nullptr, *dQ12 = nullptr, *dY = nullptr, *dV = nullptr;
-        int *dstatus = nullptr;
-        const bool ok = pl.init_twiddles_only() && tmp.get(dq, Dn) && tmp.get(dX, Dn) && tmp.get(dX12, 2 * Dn)
-                        && tmp.get(dQ12, 2 * Dn) && tmp.get(dY, 2 * L) && tmp.get(dV, L) && tmp.get(dstatus, 4);
-        if (!ok) return NFT_EC_NOMEM;
+        NftTwiddles<BE> tabs;
+        NftResampler<BE> one(be, tabs);
+        cplx *dq = nullptr;
+        int rc = one.init(tmp, Dn, 1);
+        if (rc == NFT_SUCCESS && !(tabs.init(tmp) && tmp.get(dq, Dn))) rc = NFT_EC_NOMEM;
+        if (rc != NFT_SUCCESS) return rc;
         be.h2d(dq, q, Dn * sizeof(cplx));
-        be.memset0(dstatus, 4 * sizeof(int));
-        ChirpParams C;
-        std::memset(&C, 0, sizeof(C));
-        C.poly = dq;
-        C.deg = (long long)Dn - 1;
-        C.batch = 1;
-        C.npoly = 1;
-        C.M = (long long)Dn;
-        C.Ybuf = dY; C.Vbuf = dV; C.Hbuf = dX;
-        pl.fill_chirp_geometry(C, L);
-        C.status = dstatus;
-        C.cstype = -1;
-        C.dft_len = (long long)Dn;
-        C.dft_sign = -1;
-        int rc = pl.run_chirp(C);                               // X = DFT(q), :366-370
-        if (rc == NFT_SUCCESS) {
-            ResampleParams R;
-            std::memset(&R, 0, sizeof(R));
-            R.X = dX; R.X12 = dX12; R.Q12 = dQ12; R.qpre = nullptr;
-            R.Din = (long long)Dn; R.Dsub = (long long)Dn; R.nskip = 1;
-            R.batch = 1;
-            R.delta_over_span = delta / ((double)Dn * eps_t);    // freq[i]*delta, :383-393
-            R.status = dstatus;
-            be.template run<KBandCheck>(1, 1, R);                // :371-381
-            be.template run<KResamplePhase>((int)((Dn + 255) / 256), 1, R);
-            C.poly = dX12;
-            C.npoly = 2;
-            C.Hbuf = dQ12;
-            C.dft_sign = +1;
-            rc = pl.run_chirp(C);                               // inverse DFTs of the -delta and +delta copies
-        }
+        ResampleParams R;
+        rc = one.run(dq, delta / ((double)Dn * eps_t), one.ft.status, 0, true, R);   // freq[i]*delta, :383-393
         if (rc == NFT_SUCCESS) {
             int hst[4] = {0, 0, 0, 0};
-            be.d2h(hst, dstatus, sizeof(hst));
-            be.d2h(q_new, dQ12 + Dn, Dn * sizeof(cplx));        // the +delta copy
+            be.d2h(hst, one.ft.status, sizeof(hst));
+            be.d2h(q_new, one.Q12 + Dn, Dn * sizeof(cplx));      // the +delta copy
             rc = be.sync();
             if (warn_not_bandlimited) *warn_not_bandlimited = (hst[0] & 4) ? 1 : 0;
             const double inv = 1.0 / (double)Dn;                // :395-399

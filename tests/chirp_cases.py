@@ -1,6 +1,6 @@
 """Case table of the chirp z-transform path tests (tests/test_chirp_schedule.py, tests/test_gpu_chirp_paths.py).
 
-The chirp transform of length L = 4096 N1 runs three launches (NftPlan::run_chirp): KChirpColFwd<N1, DFT>, KChirpRows,
+The chirp transform of length L = 4096 N1 runs three launches (run_chirp, nft_chirp.h): KChirpColFwd<N1, DFT>, KChirpRows,
 KChirpColInv<N1, DFT, KDV>.  Each case names its entry point, sizes and mode, and the column length N1 it must reach;
 the kernels it must launch follow from those (names as the emulator's schedule and the plans' launch timers print them,
 spaces removed).  Entries:

@@ -32,8 +32,9 @@ struct CountingBackend : EmuBackend {
     }
 };
 
-// init() of one plan; *class_bytes: the plan's own count while it is alive
-static int init_one(CountingBackend &be, int kind, const long long *a, size_t *class_bytes)
+// init() of one plan or part; *class_bytes: its own count while it is alive (a part: the count of the arena it was given);
+// *inner_bytes: kind 6 only, the count of the plan without the tables it borrows
+static int init_one(CountingBackend &be, int kind, const long long *a, size_t *class_bytes, size_t *inner_bytes)
 {
     typedef CountingBackend BE;
     switch (kind) {
@@ -68,6 +69,34 @@ static int init_one(CountingBackend &be, int kind, const long long *a, size_t *c
         *class_bytes = inv.workspace_bytes();
         return rc;
     }
+    case 4: {   // NftResampler alone: a = {Din, batch}
+        DevArena<BE> mem(be);
+        NftTwiddles<BE> tw;
+        NftResampler<BE> rs(be, tw);
+        const int rc = tw.init(mem) ? rs.init(mem, (size_t)a[0], (size_t)a[1]) : NFT_EC_NOMEM;
+        *class_bytes = mem.bytes;
+        return rc;
+    }
+    case 5: {   // NftAnyDft alone: a = {nmax, jobs}
+        DevArena<BE> mem(be);
+        NftTwiddles<BE> tw;
+        NftAnyDft<BE> ft(be, tw);
+        const int rc = tw.init(mem) ? ft.init(mem, (size_t)a[0], (size_t)a[1]) : NFT_EC_NOMEM;
+        *class_bytes = mem.bytes;
+        return rc;
+    }
+    case 6: {   // NftPlan on borrowed tables: a as for kind 0
+        DevArena<BE> mem(be);
+        NftTwiddles<BE> tw;
+        if (!tw.init(mem, a[7] != 0)) return NFT_EC_NOMEM;
+        NftPlan<BE> pl(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], (int)a[3], (int)a[4], &tw);
+        pl.set_front((size_t)a[5], 1, (int)a[6]);
+        pl.kdv = a[7] != 0;
+        const int rc = pl.init();
+        *inner_bytes = pl.mem.bytes;
+        *class_bytes = mem.bytes + pl.mem.bytes;
+        return rc;
+    }
     default: return -1;
     }
 }
@@ -75,22 +104,65 @@ static int init_one(CountingBackend &be, int kind, const long long *a, size_t *c
 extern "C" {
 
 // out = {requests made, blocks live after the plan is gone, bytes requested and served, the plan's own byte count,
-// bad frees}; returns init()'s code
+// bad frees, kind 6: the plan's count without the borrowed tables}; returns init()'s code
 int emu_alloc_balance(int kind, const long long *a, long fail_at, unsigned long long *out)
 {
     CountingBackend be;
     be.fail_at = fail_at;
     std::vector<std::string> names;
     emu_schedule = &names;
-    size_t class_bytes = 0;
-    const int rc = init_one(be, kind, a, &class_bytes);
+    size_t class_bytes = 0, inner_bytes = 0;
+    const int rc = init_one(be, kind, a, &class_bytes, &inner_bytes);
     emu_schedule = nullptr;
     out[0] = (unsigned long long)be.nalloc;
     out[1] = be.live.size();
     out[2] = be.requested;
     out[3] = class_bytes;
     out[4] = (unsigned long long)be.bad_free;
+    out[5] = inner_bytes;
     for (void *p : be.live) std::free(p);
+    return rc;
+}
+
+// Schedule of one run() of a batched plan class without executing it (schedule-only mode, as emu_tree_schedule of
+// emu_main.cpp): kind and a as in init_one (kinds 1 .. 3); the names of every kernel that init() and run() launch,
+// '\n'-separated, into out[cap].  Nothing executes, so one dummy address stands for every device array of the caller.
+// Returns the plan's rc, or -1 if out is too small.
+int emu_plan_schedule(int kind, const long long *a, char *out, size_t cap)
+{
+    EmuBackend be;
+    std::vector<std::string> names;
+    emu_schedule = &names;
+    cplx *dummy = (cplx *)be.alloc(16);
+    const double T[2] = {-1.0, 1.0}, XI[2] = {-0.5, 0.7};
+    int rc = NFT_EC_INVALID_ARGUMENT;
+    if (kind == 1) {
+        NftSlowOpts o;
+        o.nse_disc = (int)a[3]; o.cstype = (int)a[4]; o.richardson = (int)a[5];
+        NftSlowPlan<EmuBackend> sp(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], o);
+        rc = sp.init();
+        if (rc == NFT_SUCCESS) rc = sp.run(dummy, T, dummy, XI, +1);
+    } else if (kind == 2) {
+        NftDsOpts o;
+        o.bsfilt = 2; o.bsloc = 1; o.niter = 10; o.Dsub = 0; o.dstype = 2; o.nse_disc = (int)a[3]; o.richardson = 0;
+        NftDiscSpecBatch<EmuBackend> ds(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], o);
+        rc = ds.init();
+        if (rc == NFT_SUCCESS) rc = ds.run(dummy, T, dummy, dummy, dummy, (unsigned long long *)dummy);
+    } else if (kind == 3) {
+        NftInverseBatch<EmuBackend> inv(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], (int)a[3], (size_t)a[4], (int)a[5],
+                                        (size_t)a[6], (int)a[7], (int)a[8]);
+        rc = inv.init();
+        const double eps_t = (T[1] - T[0]) / (double)(a[0] - 1);
+        if (rc == NFT_SUCCESS)
+            rc = a[6] ? inv.run_discrete(dummy, XI, dummy, dummy, dummy, T, eps_t, +1, 0.0)
+                      : inv.run(dummy, XI, dummy, eps_t, +1, 0.0);
+    }
+    be.free(dummy);
+    emu_schedule = nullptr;
+    std::string s;
+    for (const auto &n : names) s += n + "\n";
+    if (s.size() + 1 > cap) return -1;
+    std::memcpy(out, s.c_str(), s.size() + 1);
     return rc;
 }
 

@@ -2,9 +2,14 @@
 (tests/emu/emu_alloc_balance.cpp), for the smallest shapes that reach every allocation branch of the init() functions:
 a successful init() followed by the end of the plan's scope leaves no block behind, and the plan's byte count is what the
 back end saw requested; an init() that finds no memory at its n-th request, for every n, returns an error and leaves no
-block behind either, and no block is ever handed back twice.  No kernel executes.  No GPU needed."""
+block behind either, and no block is ever handed back twice.  The parts a plan is made of (twiddle tables, any-length
+DFT, resampler: fnft_amd/csrc/nft_twiddles.h, nft_chirp.h) stand alone under the same assertions, and a tree plan on
+borrowed tables requests what the owning plan requests minus the tables.
+The same library records the launches of one run() of the batched plan classes (emu_plan_schedule): which kernels the
+parts contribute to them.  No kernel executes.  No GPU needed."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -17,7 +22,7 @@ EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libfnft_emu_alloc_balance.so")
 CSRC = os.path.join(ROOT, "fnft_amd", "csrc")
 
-PLAN, SLOW, DISCSPEC, INVERSE = 0, 1, 2, 3
+PLAN, SLOW, DISCSPEC, INVERSE, RESAMPLER, ANYDFT, PLAN_BORROWED = 0, 1, 2, 3, 4, 5, 6
 D = capi.NSE_DISC
 CASES = {
     # NftPlan: D of the tree, M, batch, akns discretization, its degree, input samples, upsampling, kdv
@@ -32,7 +37,18 @@ CASES = {
     # NftInverseBatch: D, M, batch, cstype, oversampling, modal, K, discrete mode, residues
     "inverse-b-of-xi-K2": (INVERSE, [512, 512, 2, 1, 8, 1, 2, 1, 1]),          # 512 > leaf: work arrays and sub-plans
     "inverse-M0-K2": (INVERSE, [512, 0, 2, 0, 8, 1, 2, 0, 0]),
+    # NftResampler alone (with the tables it borrows in the same arena): input samples, batch
+    "resampler-D64-batch2": (RESAMPLER, [64, 2]),
+    # NftAnyDft alone: largest length, transforms at a time (37: the shortest chirp, 4099: a prime above 4096)
+    "anydft-37": (ANYDFT, [37, 2]),
+    "anydft-4099": (ANYDFT, [4099, 2]),
 }
+# NftPlan on tables it borrows: the arguments of the owning case
+BORROWED = {"plan-borrowed-" + k[5:]: (PLAN_BORROWED, v[1]) for k, v in CASES.items() if v[0] == PLAN}
+CASES.update(BORROWED)
+# bytes of one set of twiddle tables without the lengths 3*2^b, with them (nft_twiddles.h)
+TABLES = 16 * (2 * 16384 + 2 ** 12 + 2 ** 13)
+TABLES3 = TABLES + 16 * (3 * 2 ** 13 + 2 ** 12)
 
 
 @pytest.fixture(scope="module")
@@ -44,12 +60,13 @@ def emu():
                                "-o", EMU_LIB, os.path.join(EMU_DIR, "emu_alloc_balance.cpp")])
     L = C.CDLL(EMU_LIB)
     L.emu_alloc_balance.argtypes = [C.c_int, C.c_void_p, C.c_long, C.c_void_p]
+    L.emu_plan_schedule.argtypes = [C.c_int, C.c_void_p, C.c_char_p, C.c_size_t]
     return L
 
 
 def run(emu, kind, args, fail_at):
     a = np.array(args, np.int64)
-    out = np.zeros(5, np.uint64)
+    out = np.zeros(6, np.uint64)
     rc = emu.emu_alloc_balance(kind, a.ctypes.data_as(C.c_void_p), fail_at, out.ctypes.data_as(C.c_void_p))
     return (rc,) + tuple(int(x) for x in out)
 
@@ -57,12 +74,93 @@ def run(emu, kind, args, fail_at):
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_arena_balances(emu, case):
     kind, args = CASES[case]
-    rc, nalloc, live, requested, class_bytes, bad = run(emu, kind, args, -1)
+    rc, nalloc, live, requested, class_bytes, bad, _ = run(emu, kind, args, -1)
     print(case, "requests", nalloc, "bytes", requested)
     assert rc == 0
     assert nalloc > 0 and live == 0 and bad == 0
     assert class_bytes == requested
     for n in range(nalloc):
-        rc, _, live, _, _, bad = run(emu, kind, args, n)
+        rc, _, live, _, _, bad, _ = run(emu, kind, args, n)
         assert rc != 0, (case, n)
         assert live == 0 and bad == 0, (case, n, live, bad)
+
+
+@pytest.mark.parametrize("case", sorted(BORROWED))
+def test_borrowed_tables(emu, case):
+    """The plan on borrowed tables requests exactly the owning plan's bytes minus the tables."""
+    own = run(emu, PLAN, BORROWED[case][1], -1)
+    rc, _, _, requested, _, _, plan_bytes = run(emu, *BORROWED[case], -1)
+    tables = TABLES3 if BORROWED[case][1][7] else TABLES
+    print(case, "owning plan", own[3], "borrowing plan", plan_bytes, "tables", tables)
+    assert rc == 0 and own[0] == 0
+    assert requested == own[3]                  # tables in the owner's arena + the plan = the owning plan
+    assert plan_bytes == own[3] - tables
+
+
+# ---- launches of one run() of the batched plan classes -----------------------------------------------------------------
+def schedule(emu, kind, args):
+    a = np.array(args, np.int64)
+    buf = C.create_string_buffer(1 << 18)
+    rc = emu.emu_plan_schedule(kind, a.ctypes.data_as(C.c_void_p), buf, len(buf))
+    assert rc == 0, (kind, args, rc)
+    return [n.replace(" ", "") for n in buf.value.decode().split("\n") if n]
+
+
+def chirp_kinds(names):
+    """(kernel, column length, DFT mode) of every chirp column kernel; KChirpRows as it is."""
+    out = []
+    for n in names:
+        m = re.match(r"^(KChirpColFwd|KChirpColInv)<(\d+),(true|false)", n)
+        if m:
+            out.append((m.group(1), int(m.group(2)), m.group(3) == "true"))
+        elif n == "KChirpRows":
+            out.append((n, 0, True))
+    return out
+
+
+DFT_TRIPLE = ["KChirpColFwd", "KChirpRows", "KChirpColInv"]
+
+
+def test_discspec_front_is_the_resampler_alone(emu):
+    """NftDiscSpecBatch, 4SPLIT4B: the front end is the resampler and the combination, and no level 0 of a tree."""
+    names = schedule(emu, DISCSPEC, CASES["discspec-4SPLIT4B"][1])
+    front = names[:names.index("KDsBox")]
+    assert [k for k, _, dft in chirp_kinds(front)] == DFT_TRIPLE * 2 and all(d for _, _, d in chirp_kinds(front))
+    rest = [n for n in front if not n.startswith("KChirp")]
+    assert rest == ["KBandCheck", "KResamplePhase", "KResampleCombine"], front
+    assert front.index("KBandCheck") == 3 and front[-1] == "KResampleCombine"
+    assert not [n for n in names if n.startswith(("KCoeffs", "KLeaf"))], names
+
+
+def test_slow_second_pass_reuses_the_spectrum(emu):
+    """NftSlowPlan, CF4_2 with Richardson: the first pass transforms the signal and checks its band, the second (every
+    other sample, fwd = false) starts at the phase ramps."""
+    names = schedule(emu, SLOW, CASES["slow-CF4_2-front-richardson"][1])
+    cut = [i for i, n in enumerate(names) if n == "KSlowPrep"]
+    assert len(cut) == 2
+    first, second = names[:cut[0]], names[cut[0] + 1:cut[1]]
+    second = second[next(i for i, n in enumerate(second) if n.startswith(("KChirp", "KResample", "KBandCheck"))):]
+    assert [k for k, _, _ in chirp_kinds(first)] == DFT_TRIPLE * 2
+    assert [n for n in first if not n.startswith("KChirp")] == ["KBandCheck", "KResamplePhase"]
+    assert [k for k, _, _ in chirp_kinds(second)] == DFT_TRIPLE
+    assert [n for n in second if not n.startswith("KChirp")] == ["KResamplePhase"] and second[0] == "KResamplePhase"
+
+
+def test_inverse_dfts_run_at_their_own_length(emu):
+    """NftInverseBatch, b(xi), D = M = 512, oversampling 8: the M-point DFT and the four of the spectral factorization
+    (next_fast_size(513 * 8) = 4104 points) each run at the column length NftAnyDft::len(n) / kRowChirp of their own length, not at
+    the workspace's."""
+    names = schedule(emu, INVERSE, [512, 512, 2, 1, 8, 1, 0, 0, 0])
+    row = 4096                                                    # kRowChirp (tests/chirp_cases.py: ROW)
+
+    def n1(n):
+        L = 1
+        while L < 2 * n - 1:
+            L *= 2
+        return max(L, 2 * row) // row
+    ck = chirp_kinds(names)
+    assert [k for k, _, _ in ck] == DFT_TRIPLE * 5 and all(d for _, _, d in ck)
+    want = [n1(512)] + [n1(4104)] * 4
+    assert [c for k, c, _ in ck if k == "KChirpColFwd"] == want
+    assert [c for k, c, _ in ck if k == "KChirpColInv"] == want
+    assert n1(512) != n1(4104)
