@@ -152,6 +152,22 @@ def test_every_slot_equals_the_drop_in(capi, torch, cstype, method, disc, kappa,
         assert rc == next((int(s) for s in st if s != 0), 0)
 
 
+@pytest.mark.parametrize("D", (8192, 16384))
+@pytest.mark.parametrize("disc, kappa", (("2SPLIT2_MODAL", 1), ("2SPLIT2A", -1)))
+def test_every_slot_equals_the_drop_in_where_step_4_is_a_plan(capi, torch, disc, kappa, D):
+    """The sizes above reach every one-launch product of the layer peeling but no product of the inverses (step 4)
+    through a plan: D = 8192 is the first with one (degree 2048), D = 16384 the first at degree 4096 -- here with the
+    batch strides of T, Ti and the product's output (tests/peel_cases.py, PATHS)."""
+    opts = {"discretization": disc, "contspec_type": "B_OF_XI", "contspec_inversion_method": "DEFAULT"}
+    XI, rows = spectra(capi, D, D, disc, kappa, "B_OF_XI")
+    rc, q, st, wn = run_batch(capi, torch, D, D, opts, rows, XI, T_STD, kappa)
+    for b, cs in enumerate(rows):
+        r0, q0 = drop_in(capi, D, cs, XI, D, T_STD, kappa, opts)
+        assert st[b] == r0 == 0, (b, st[b], r0)      # every slot is compared
+        assert_slot_equal(q[b], q0)
+    assert rc == 0
+
+
 # ---- 2. independence of the slots -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("cstype", ("REFLECTION_COEFFICIENT", "B_OF_XI"))
 def test_slots_are_independent(capi, torch, cstype):
