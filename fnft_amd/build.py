@@ -2,9 +2,9 @@
 
 Usage: python -m fnft_amd.build [--force] [-j N]
 The library is the product; it has no CPU fallback.  hipcc cross-compiles without a GPU.
-The HIP side is several translation units (csrc/hip_backend.hip + the 24 units csrc/hip_kernels_*.hip, which
-instantiate the 261 kernels listed in csrc/nft_kernel_list.h -- 258 in the 23 units of FA_ALL_UNITS, 3 in the unit of
-FA_EXT_UNITS; see csrc/hip_be.h) compiled in parallel; only units whose object is older than the sources are rebuilt.
+The HIP side is several translation units (csrc/hip_backend.hip + the 25 units csrc/hip_kernels_*.hip, which
+instantiate the 263 kernels listed in csrc/nft_kernel_list.h -- 258 in the 23 units of FA_ALL_UNITS, 3 in the unit of
+FA_EXT_UNITS, 2 in the unit of FA_EXT2_UNITS; see csrc/hip_be.h) compiled in parallel; only units whose object is older than the sources are rebuilt.
 """
 import glob
 import os

@@ -114,6 +114,7 @@ EXPORTED = [
     "fnft_amd_discspec_plan_set_launch_timing", "fnft_amd_discspec_plan_launch_count", "fnft_amd_discspec_plan_launch_ms",
     "fnft_amd_slow_plan_create", "fnft_amd_slow_plan_destroy", "fnft_amd_slow_plan_workspace_bytes",
     "fnft_amd_nsev_slow_device", "fnft_amd_slow_plan_finish", "fnft_amd_slow_plan_chunks",
+    "fnft_amd_plan_set_richardson", "fnft_amd_discspec_plan_set_richardson",
 ]
 
 _lib = None
@@ -306,6 +307,10 @@ def load(path=None):
     L.fnft_amd_nsev_slow_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
     L.fnft_amd_slow_plan_finish.restype = i32
     L.fnft_amd_slow_plan_finish.argtypes = [vp, vp, vp, vp]
+    L.fnft_amd_plan_set_richardson.restype = i32
+    L.fnft_amd_plan_set_richardson.argtypes = [vp, C.c_int]
+    L.fnft_amd_discspec_plan_set_richardson.restype = i32
+    L.fnft_amd_discspec_plan_set_richardson.argtypes = [vp, C.c_int]
     if path is None:
         _lib = L
     return L
@@ -815,6 +820,10 @@ class Plan(_TreePlan):
     def workspace_bytes(self):
         return int(self.L.fnft_amd_plan_workspace_bytes(self.h))
 
+    def set_richardson(self, on=True):
+        """fnft_amd_plan_set_richardson: Richardson extrapolation for the contspec_device calls that follow; the code."""
+        return int(self.L.fnft_amd_plan_set_richardson(self.h, 1 if on else 0))
+
     def cs_len(self, contspec_type):
         c = CSTYPE[contspec_type] if isinstance(contspec_type, str) else int(contspec_type)
         return self.M * CS_FACTOR[c]
@@ -954,6 +963,11 @@ class DiscSpecPlan(_BatchPlan):
 
     def workspace_bytes(self):
         return int(self.L.fnft_amd_discspec_plan_workspace_bytes(self.h))
+
+    def set_richardson(self, on=True):
+        """fnft_amd_discspec_plan_set_richardson: Richardson extrapolation for the run_device calls that follow; the
+        code."""
+        return int(self.L.fnft_amd_discspec_plan_set_richardson(self.h, 1 if on else 0))
 
     def nc_len(self):
         """complex128 values per signal of the norming-constant / residue output (2K for BOTH)."""

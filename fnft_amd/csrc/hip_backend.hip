@@ -169,6 +169,9 @@ struct fnft_amd_discspec_plan : PlanHandle<NftDiscSpecBatch<HipBackend>> {
     // fnft_amd_discspec_search_plan_create: the guess-free plan in place of `core` (it owns its own NftDiscSpecBatch)
     std::unique_ptr<NftDiscSpecSearch<HipBackend>> search;
     std::vector<int> wn;                          // its warning bits, read by finish
+    // fnft_amd_discspec_plan_set_richardson: the stage that follows the fine pass of either core (nft_ds_richardson.h)
+    std::unique_ptr<NftDsRichardson<HipBackend>> rich;
+    bool rich_on = false;
 };
 struct fnft_amd_slow_plan : PlanHandle<NftSlowPlan<HipBackend>> {
     std::vector<int> wn;
@@ -363,7 +366,27 @@ FNFT_INT fnft_amd_plan_create_sub(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT
 
 void fnft_amd_plan_destroy(fnft_amd_plan_t *plan) { batch_destroy(plan); }
 
-FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->core->mem.bytes : 0; }
+FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->core->workspace_bytes() : 0; }
+
+// Richardson extrapolation for the calls that follow (NftPlan::enable_richardson / run_richardson).  The first enabling
+// call waits for the plan's last stream and allocates the coarse pass's workspace; disabling keeps it.
+FNFT_INT fnft_amd_plan_set_richardson(fnft_amd_plan_t *plan, int enabled)
+{
+    if (!plan || plan->kdv_disc >= 0 || plan->core->M == 0 || plan->core->Din < 3) return FNFT_EC_INVALID_ARGUMENT;
+    if (plan->core->nskip > 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
+    PlanCall call(plan->mtx, plan->device);
+    if (!call.ok) return FNFT_EC_OTHER;
+    Plan &pl = *plan->core;
+    if (!enabled || pl.rich_child) {
+        pl.rich_on = enabled != 0;
+        return FNFT_SUCCESS;
+    }
+    if (plan->be.sync() != NFT_SUCCESS) return FNFT_EC_OTHER;   // what the last call enqueued: the child's uploads follow it
+    const int rc = pl.enable_richardson();
+    (void)plan->be.sync();
+    if (rc != NFT_SUCCESS) return rc;
+    return plan->be.failed ? FNFT_EC_NOMEM : FNFT_SUCCESS;
+}
 
 int fnft_amd_plan_device(const fnft_amd_plan_t *plan) { return plan ? plan->device : -1; }
 
@@ -505,6 +528,7 @@ FNFT_INT fnft_amd_nsev_contspec_device(fnft_amd_plan_t *plan, const void *d_q, v
         cs.cstype = cst;
         cs.normalization_flag = normalization_flag;
         rc = pl.run_contspec(d_contspec, cs);
+        if (rc == NFT_SUCCESS && pl.rich_on) rc = pl.run_richardson(d_q, T, kappa, d_contspec, cs);
     }
     plan->be.mark(2);
     if (plan->be.failed) return FNFT_EC_OTHER;
@@ -1177,11 +1201,13 @@ FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UIN
 
 void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
 {
-    if (!plan || !plan->search) return batch_destroy(plan);
-    {   // batch_destroy for the guess-free core: on the plan's device, after everything it enqueued
+    if (!plan) return;
+    {   // batch_destroy with the plan's other owners: on the plan's device, after everything it enqueued
         DeviceGuard dg(plan->device);
         plan_quiesce(plan->last_stream);
+        plan->rich.reset();
         plan->search.reset();
+        plan->core.reset();
         plan->be.destroy_events();
     }
     delete plan;
@@ -1190,7 +1216,36 @@ void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
 FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan)
 {
     if (!plan) return 0;
-    return plan->search ? plan->search->workspace_bytes() : plan->core->workspace_bytes();
+    return (plan->search ? plan->search->workspace_bytes() : plan->core->workspace_bytes())
+           + (plan->rich ? plan->rich->workspace_bytes() : 0);
+}
+
+// Richardson extrapolation for the calls that follow, on a plan of either creator.  The first enabling call waits for
+// the plan's last stream and allocates the coarse pass's workspace; disabling keeps it.
+FNFT_INT fnft_amd_discspec_plan_set_richardson(fnft_amd_discspec_plan_t *plan, int enabled)
+{
+    SEAM_CHECK(!plan, plan);
+    const size_t D = plan->search ? plan->search->D : plan->core->D;
+    SEAM_CHECK(D < 3, D);
+    PlanCall call(plan->mtx, plan->device);
+    if (!call.ok) return FNFT_EC_OTHER;
+    if (!enabled || plan->rich) {
+        plan->rich_on = enabled != 0;
+        return FNFT_SUCCESS;
+    }
+    if (plan->be.sync() != NFT_SUCCESS) return FNFT_EC_OTHER;   // what the last call enqueued
+    // the coarse pass is a Newton pass with the caller's niter, whatever found the fine bound states
+    const size_t K = plan->search ? plan->search->K : plan->core->K;
+    const size_t batch = plan->search ? plan->search->batch : plan->core->batch;
+    const NftDsOpts &o = plan->search ? plan->search->o : plan->core->o;
+    std::unique_ptr<NftDsRichardson<HipBackend>> r(new (std::nothrow) NftDsRichardson<HipBackend>(plan->be, D, K, batch, o));
+    if (!r) return FNFT_EC_NOMEM;
+    const int rc = r->init();
+    (void)plan->be.sync();
+    if (rc != NFT_SUCCESS || plan->be.failed) return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;   // r hands its blocks back
+    plan->rich = std::move(r);
+    plan->rich_on = true;
+    return FNFT_SUCCESS;
 }
 
 FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
@@ -1207,8 +1262,12 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
     PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
     if (!call.ok) return FNFT_EC_OTHER;
     plan->last_K = (const unsigned long long *)d_K_out;
-    const int rc = plan->core->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
-                                   (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
+    const int rc = plan->rich_on
+                       ? plan->rich->run_after(*plan->core, (const cplx *)d_q, T, (const cplx *)d_guesses,
+                                               (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
+                                               (unsigned long long *)d_K_out)
+                       : plan->core->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
+                                         (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
     return batch_run_result(plan->be, rc, __func__, __LINE__);
 }
 
@@ -1313,8 +1372,18 @@ FNFT_INT fnft_amd_nsev_discspec_search_device(fnft_amd_discspec_plan_t *plan, co
     PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
     if (!call.ok) return FNFT_EC_OTHER;
     plan->last_K = (const unsigned long long *)d_K_out;
-    const int rc = plan->search->run((const cplx *)d_q, T, (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
-                                     (unsigned long long *)d_K_out);
+    int rc;
+    if (plan->rich_on) {
+        NftDsRichardson<HipBackend> &r = *plan->rich;
+        rc = plan->search->run((const cplx *)d_q, T, (cplx *)d_bound_states, r.fine_nc((cplx *)d_normconsts_or_residues),
+                               (unsigned long long *)d_K_out, r.fine_dstype());
+        if (rc == NFT_SUCCESS)
+            rc = r.run((const cplx *)d_q, T, (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
+                       (unsigned long long *)d_K_out, plan->search->refine->status);
+    } else {
+        rc = plan->search->run((const cplx *)d_q, T, (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
+                               (unsigned long long *)d_K_out);
+    }
     return batch_run_result(plan->be, rc, __func__, __LINE__);
 }
 

@@ -1,6 +1,6 @@
 // hip_be.h -- HIP back end of NftPlan (device memory, copies, kernel launches, event timers) and the
-// kernel entry template.  The library is built from 24 kernel translation units so that the 261 kernel
-// instantiations (FA_ALL_UNITS: 258 in 23 units, FA_EXT_UNITS: 3 in one) compile in parallel: HipBackend::run<K> is only DECLARED for the host logic
+// kernel entry template.  The library is built from 25 kernel translation units so that the 263 kernel
+// instantiations (FA_ALL_UNITS: 258 in 23 units, FA_EXT_UNITS: 3 in one, FA_EXT2_UNITS: 2 in one) compile in parallel: HipBackend::run<K> is only DECLARED for the host logic
 // (hip_backend.hip); each hip_kernels_<name>.hip defines FA_HIP_RUN_IMPL, sees the definition, and
 // instantiates run<K> -- and with it kernel_entry<K> -- explicitly for its group of kernels,
 // FA_UNIT_<name>(FA_INST).  nft_kernel_list.h states the groups, from the same size lists the dispatch
@@ -18,6 +18,7 @@
 #include "nft_discspec.h"
 #include "nft_discspec_batch.h"
 #include "nft_discspec_search.h"
+#include "nft_ds_richardson.h"
 #include "nft_nsev_slow.h"
 
 extern thread_local std::string g_last_error;   // defined in hip_backend.hip

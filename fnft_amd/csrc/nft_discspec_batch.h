@@ -5,6 +5,8 @@
 // one workgroup per (signal, eigenvalue) instead of a host loop over chunk kernels (nft_kernels.h: body_ds_*).
 //   box kernel -> Newton kernel (all iterations on chip) -> filter + merge kernel -> norming kernel
 // 4SPLIT4A/B refine on the resampled signal of that scheme's front end (NftResampler::run_4split4, qpre).
+// set_front(Din, nskip): the D samples are every nskip-th of Din input samples (the coarse pass of the Richardson
+// extrapolation, nft_ds_richardson.h) -- gathered (KDsGather) or, for 4SPLIT4A/B, resampled from all Din samples.
 // Back-end independent like NftDiscSpec: hip_backend.hip instantiates it with the HIP back end, tests/emu with the
 // lane emulator.
 #pragma once
@@ -18,10 +20,11 @@ public:
     const NftDsOpts o;
     int ups = 1, deg0 = 0, akns = -1;
     size_t Dq = 0;                    // preprocessed samples per signal
+    size_t Din = 0, nskip = 1;        // set_front: input samples per signal (0: D) and their stride
     int G = 1;                        // samples per lane
     NftTwiddles<BE> tw;
     NftResampler<BE> rs;              // 4SPLIT4A/B: the front end's shifted copies, combined into qpre (batch * Dq)
-    cplx *qpre = nullptr;
+    cplx *qpre = nullptr;             // also the gathered samples of a strided front with upsampling factor 1
     cplx *lam = nullptr;              // batch*K refined eigenvalues
     double *box = nullptr;            // batch*4
     int *status = nullptr;            // batch
@@ -44,18 +47,25 @@ public:
         sphi = ((size_t)G / (size_t)ups + 1) * (size_t)kDsLanes * 2;
     }
 
+    // call before init(): this plan's D = NftPlan::sub_count(Din_, nskip_) samples are every nskip_-th of Din_
+    void set_front(size_t Din_, size_t nskip_) { Din = Din_; nskip = nskip_; }
+
     int init()
     {
         if (akns < 0 || deg0 == 0 || D < 2 || K == 0 || batch == 0) return NFT_EC_INVALID_ARGUMENT;
+        if (Din == 0) { Din = D; nskip = 1; }
+        if (nskip < 1 || D != NftPlan<BE>::sub_count(Din, nskip) || (D - 1) * nskip >= Din) return NFT_EC_INVALID_ARGUMENT;
         if (K > kMaxK || batch > kMaxGroups / K || Dq > (size_t)0x7fffffff * (size_t)kDsLanes)
             return NFT_EC_NOT_YET_IMPLEMENTED;
         if (ups == 2) {
-            if (D <= 2) return NFT_EC_INVALID_ARGUMENT;
+            if (Din <= 2) return NFT_EC_INVALID_ARGUMENT;
             if (nft_tree_too_large(Dq, deg0)) return NFT_EC_NOT_YET_IMPLEMENTED;   // the limit of the scheme's tree plan, kept
-            const int rc = rs.init(mem, D, batch);
+            const int rc = rs.init(mem, Din, batch);
             if (rc != NFT_SUCCESS) return rc;
             // the tables last: their upload waits for the cleared status word
             if (!(mem.get(qpre, batch * Dq) && tw.init(mem))) return NFT_EC_NOMEM;
+        } else if (nskip > 1) {
+            if (!mem.get(qpre, batch * D)) return NFT_EC_NOMEM;
         }
         const size_t per_signal = K * sphi * sizeof(cplx);
         slab = kPhiBytes / per_signal;
@@ -71,23 +81,30 @@ public:
 
     size_t workspace_bytes() const { return mem.bytes; }
 
-    // enqueues everything; waits for nothing.  d_nc may be NULL (no norming constants / residues); d_nguess: live guesses
-    // per signal (the guess-free plan's candidates, nft_discspec_search.h), NULL: K each
+    // enqueues everything; waits for nothing.  d_q, T: the Din input samples per signal and their interval.  d_nc may be
+    // NULL (no norming constants / residues); d_nguess: live guesses per signal (the guess-free plan's candidates,
+    // nft_discspec_search.h; the fine counts of the Richardson stage), NULL: K each; dstype: the output layout of d_nc in
+    // place of the options' (the Richardson stage needs BOTH where the caller asked for residues), -1: the options'
     int run(const cplx *d_q, const double T[2], const cplx *d_guess, cplx *d_bs, cplx *d_nc,
-            unsigned long long *d_K, const unsigned long long *d_nguess = nullptr)
+            unsigned long long *d_K, const unsigned long long *d_nguess = nullptr, int dstype = -1)
     {
-        // grid and step as NftDiscSpec::prepare forms them for the full signal (Dsub = D, nskip = 1)
-        const double eps_in = (T[1] - T[0]) / (double)(D - 1);
-        const double T1 = T[0] + (double)(D - 1) * eps_in;
+        // grid and step as NftDiscSpec::prepare forms them (the full signal: Dsub = D, nskip = 1)
+        const double eps_in = (T[1] - T[0]) / (double)(Din - 1);
+        const double T1 = T[0] + (double)((D - 1) * nskip) * eps_in;
         const double eps_t = (T1 - T[0]) / (double)(D - 1);
         be.memset0(status, batch * sizeof(int));
         if (ups == 2) {
-            const int rc = rs.run_4split4(d_q, 1, D, qpre, rs.ft.status);   // the band check's bit: read by nobody
+            const int rc = rs.run_4split4(d_q, nskip, D, qpre, rs.ft.status);   // the band check's bit: read by nobody
             if (rc != NFT_SUCCESS) return rc;
+        } else if (nskip > 1) {
+            GatherParams Gp;
+            Gp.q = d_q; Gp.out = qpre;
+            Gp.D = (long long)Din; Gp.Dsub = (long long)D; Gp.nskip = (long long)nskip; Gp.batch = (long long)batch;
+            be.template run<KDsGather>((int)((batch * D + 255) / 256), 1, Gp);
         }
         DsBatchParams P;
         std::memset(&P, 0, sizeof(P));
-        P.q = (ups == 2) ? qpre : d_q;
+        P.q = (ups == 2 || nskip > 1) ? qpre : d_q;
         P.D = (long long)Dq;
         P.ups = ups;
         P.G = G;
@@ -103,7 +120,7 @@ public:
         P.re_bound = 0.9 * 3.14159265358979323846 / std::fabs(2.0 / (double)deg0 * eps_t);
         P.bsfilt = o.bsfilt;
         P.niter = (int)std::min<size_t>(o.niter, 0x7fffffff);
-        P.dstype = o.dstype;
+        P.dstype = (dstype >= 0) ? dstype : o.dstype;
         P.modal = (o.nse_disc == 0) ? 1 : 0;
         P.status = status;
         P.bs = d_bs;

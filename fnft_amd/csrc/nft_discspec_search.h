@@ -111,8 +111,9 @@ public:
         return mem.bytes + (tree ? tree->mem.bytes : 0) + (refine ? refine->workspace_bytes() : 0);
     }
 
-    // enqueues everything; waits for nothing.  d_nc may be NULL
-    int run(const cplx *d_q, const double T[2], cplx *d_bs, cplx *d_nc, unsigned long long *d_K)
+    // enqueues everything; waits for nothing.  d_nc may be NULL; dstype: the layout of d_nc in place of the options'
+    // (NftDiscSpecBatch::run), -1: the options'
+    int run(const cplx *d_q, const double T[2], cplx *d_bs, cplx *d_nc, unsigned long long *d_K, int dstype = -1)
     {
         // grid of the subsampled signal, NftDiscSpec::prepare
         const double eps_in = (T[1] - T[0]) / (double)(D - 1);
@@ -159,7 +160,7 @@ public:
         A.den = 2.0 * eps_s / (double)(deg0 * ups);
         roots(tree->tm_out);
         be.template run<KDsCandidates>((int)batch, 1, A);
-        return refine->run(d_q, T, A.cand, d_bs, d_nc, d_K, A.ncand);
+        return refine->run(d_q, T, A.cand, d_bs, d_nc, d_K, A.ncand, dstype);
     }
 
     // all roots of entry 11 of every signal's transfer matrix (tm: batch * 4 * (n + 1) coefficients): start values, the

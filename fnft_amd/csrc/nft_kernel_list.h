@@ -109,12 +109,15 @@
     FA_LIST_CHIRP_N1(FA_K1A, I, KChirpColInv, false, false) FA_LIST_CHIRP_N1(FA_K1A, I, KChirpColInv, true, false) \
     FA_LIST_CHIRP_N1(FA_K1A, I, KChirpColInv, false, true)
 #define FA_UNIT_polyeval(I) FA_LIST_BOOL(FA_K1, I, KPolyEval) I(KPolyJoin)
+#define FA_UNIT_richardson(I) I(KRichCombineCs) I(KRichMatchDs)
 // every unit of the count the tests pin (258 kernels in 23 units), in the order of the file names
 #define FA_ALL_UNITS(I) \
     FA_UNIT_bridge(I) FA_UNIT_chirpa(I) FA_UNIT_chirpb(I) FA_UNIT_col(I) FA_UNIT_discbatch(I) FA_UNIT_discroots(I) \
     FA_UNIT_leafmulti(I) FA_UNIT_mid(I) FA_UNIT_misc(I) FA_UNIT_multi2(I) FA_UNIT_multi3(I) FA_UNIT_pair2(I) \
     FA_UNIT_pair4a(I) FA_UNIT_pair4b(I) FA_UNIT_pair4c(I) FA_UNIT_real3bridge(I) FA_UNIT_real3col(I) \
     FA_UNIT_realbridge(I) FA_UNIT_realcol(I) FA_UNIT_realleaf(I) FA_UNIT_realpair(I) FA_UNIT_realpair4(I) FA_UNIT_slow(I)
-// the units added after that count was pinned.  A unit is in exactly one of the two aggregates; together they are
+// the units added after that count was pinned.  A unit is in exactly one of the three aggregates; together they are
 // every hip_kernels_<name>.hip
 #define FA_EXT_UNITS(I) FA_UNIT_polyeval(I)
+// the units added after the tests pinned FA_EXT_UNITS to the polynomial evaluation
+#define FA_EXT2_UNITS(I) FA_UNIT_richardson(I)

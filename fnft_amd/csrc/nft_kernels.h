@@ -5224,3 +5224,103 @@ FA_DEV void body_polyjoin(const PolyEvalParams &P)
         out[(2 + j) * P.nz + i] = cmake(ldexp(da.x, W), ldexp(da.y, W));
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Richardson extrapolation for the batched fnft_nsev plans (src/fnft_nsev.c:316-441): the result of the full grid and
+// that of a second pass over every nskip-th sample, combined per signal.
+//   body_rich_combine_cs  lane = (signal, grid point): the continuous spectrum, fnft_nsev_host.c (fnft_nsev)
+//   body_rich_match_ds    workgroup = signal: every fine bound state looks for its coarse partner and is extrapolated
+//                         with it, the residue through a' (NftDiscSpec::run)
+// Both restate a host loop of the drop-in operation by operation; nothing in them is contracted to an FMA, so that the
+// mask of the continuous spectrum and the winner of the partner search are the drop-in's.
+// ---------------------------------------------------------------------------------------------
+struct RichCsParams {
+    cplx *c;                  // batch * parts * M, the fine spectrum: extrapolated in place
+    const cplx *cs;           // the coarse spectrum, same layout
+    long long M, batch;
+    int parts;                // 1, 2 or 3 arrays of M values per signal
+    double xi0, dxi, bound;   // grid point i is extrapolated where |xi0 + dxi*i| < bound = 0.9 pi / (2 eps_t_sub)
+    double sn, sd;            // (eps_t_sub / eps_t)^order and sn - 1
+};
+// (sn*f - s)/sd on both components, as the host forms it from a real factor and a real divisor
+FA_DEV cplx rich_step(double sn, double sd, cplx f, cplx s)
+{
+#pragma clang fp contract(off)
+    return cmake((sn * f.x - s.x) / sd, (sn * f.y - s.y) / sd);
+}
+FA_DEV void body_rich_combine_cs(const RichCsParams &P)
+{
+#pragma clang fp contract(off)
+    const long long g = (long long)FA_BID * FA_BDIM + FA_TID;
+    if (g >= P.batch * P.M) return;
+    const long long b = g / P.M, i = g % P.M;
+    const double step = P.dxi * (double)i;   // rounded on its own, then the sum: the host's XI[0] + dxi * i
+    if (!(fabs(P.xi0 + step) < P.bound)) return;
+    for (int j = 0; j < P.parts; j++) {
+        const long long o = (b * P.parts + j) * P.M + i;
+        P.c[o] = rich_step(P.sn, P.sd, P.c[o], P.cs[o]);
+    }
+}
+
+constexpr int kRichTile = 256;   // coarse eigenvalues staged in LDS per round
+struct RichDsParams {
+    cplx *bs;                 // batch * K fine bound states: extrapolated in place
+    const cplx *bs_s;         // batch * K coarse bound states
+    const unsigned long long *K_out, *Ks_out;   // batch: live entries of either
+    const cplx *nc;           // fine norming constants and residues in the BOTH layout (2K per signal); NULL: bound states only
+    const cplx *nc_s;         // coarse, BOTH layout
+    cplx *res;                // residues out: entry i of signal b at b*res_stride + res_off + i (every i < K is written:
+    long long res_stride, res_off;   // the fine residue, NaN tail included, where no partner is found)
+    int K;
+    double thr;               // a partner is closer than this relative distance (eps_t of the fine grid)
+    double sn, sd;
+    int *status;              // batch: the fine pass's words; the coarse pass's bits are OR-ed in
+    const int *status_s;
+};
+FA_DEV void body_rich_match_ds(const RichDsParams &P)
+{
+    FA_LDS_DECL
+    cplx *tile = (cplx *)FA_LDS_PTR;
+    const long long b = FA_BID;
+    const int t = FA_TID, nl = FA_BDIM;
+    const int K = P.K;
+    const int Kf = P.K_out[b] < (unsigned long long)K ? (int)P.K_out[b] : K;
+    const int Ks = P.Ks_out[b] < (unsigned long long)K ? (int)P.Ks_out[b] : K;
+    cplx *bs = P.bs + b * K;
+    const cplx *bs_s = P.bs_s + b * K;
+    // the drop-in runs no coarse pass for a signal without bound states
+    if (t == 0 && Kf > 0 && P.status_s[b] != 0) P.status[b] |= P.status_s[b];
+    const int npass = P.nc ? (K + nl - 1) / nl : (Kf + nl - 1) / nl;   // with residues every slot is written
+    for (int pass = 0; pass < npass; pass++) {
+        const int i = pass * nl + t;
+        const bool live = i < Kf;
+        const cplx bi = live ? bs[i] : cmake(0.0, 0.0);
+        const double abi = hypot(bi.x, bi.y);
+        double thr = P.thr;
+        int loc = -1;
+        for (int j0 = 0; j0 < Ks; j0 += kRichTile) {
+            const int nj = Ks - j0 < kRichTile ? Ks - j0 : kRichTile;
+            FA_SYNC();   // the tile before this one has been read by every lane
+            for (int j = t; j < nj; j += nl) tile[j] = bs_s[j0 + j];
+            FA_SYNC();
+            if (live)
+                for (int j = 0; j < nj; j++) {   // ascending, strictly smaller: the first of equal distances wins
+                    const cplx d = bi - tile[j];
+                    const double e = hypot(d.x, d.y) / abi;
+                    if (e < thr) { thr = e; loc = j0 + j; }
+                }
+        }
+        if (live && loc >= 0) bs[i] = rich_step(P.sn, P.sd, bi, bs_s[loc]);
+        if (P.nc && i < K) {
+            const cplx *nc = P.nc + b * 2 * K;
+            cplx r = nc[K + i];
+            if (live && loc >= 0) {
+                // a' = norming constant / residue on either grid, one step on a', the residue again
+                const cplx *nc_s = P.nc_s + b * 2 * K;
+                const cplx api = c_div_host(nc[i], r), aps = c_div_host(nc_s[loc], nc_s[K + loc]);
+                r = c_div_host(nc[i], rich_step(P.sn, P.sd, api, aps));
+            }
+            P.res[b * P.res_stride + P.res_off + i] = r;
+        }
+    }
+}

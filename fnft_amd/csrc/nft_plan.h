@@ -18,6 +18,7 @@
 #include <complex>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "nft_chirp.h"
@@ -242,6 +243,13 @@ public:
     int tune_stagger = 0;    // row kernel start delay of the second half of a one-round grid (BigLevel::stagger)
     int tune_fuse_root = 1;  // 0: the tree always runs its last inverse column pass itself (A/B runs of ChirpParams::root_fused)
     int dbg_flags = 0;       // timing ablation: only builds with -DFNFT_AMD_ABLATION ever set it (hip_backend.hip)
+    // Richardson extrapolation of the continuous spectrum (enable_richardson, run_richardson): a child plan over every
+    // rich_nskip-th sample on the same back end, fed by KDsGather through rich_q (upsampling factor 1) or with the
+    // caller's samples and the stride (4SPLIT4A/B: the resampler sees all of them); its spectrum goes to rich_cs
+    std::unique_ptr<NftPlan> rich_child;
+    cplx *rich_q = nullptr, *rich_cs = nullptr;
+    size_t rich_Dsub = 0, rich_nskip = 1;
+    bool rich_on = false;
 
     // borrowed: the twiddle tables of the class this plan is a part of (KdV plans: with the lengths 3*2^b); without it the
     // plan allocates its own
@@ -336,7 +344,9 @@ public:
     }
 
     // the workspace back before the plan goes out of scope (the destructor does the same); the plan is not usable after
-    void destroy() { mem.clear(); }
+    void destroy() { rich_child.reset(); mem.clear(); }
+
+    size_t workspace_bytes() const { return mem.bytes + (rich_child ? rich_child->mem.bytes : 0); }
 
     // ---- front end: fnft__nse_discretization_preprocess_signal (:386-656) + level 0 ------------
     // T: interval of the Din input samples.  Tsub: interval of the kept steps (fnft_nsev.c:381-384),
@@ -906,6 +916,75 @@ public:
         return run_chirp_cached(C);
     }
 
+    // ---- Richardson extrapolation of the continuous spectrum (src/fnft_nsev.c:316-406, fnft_nsev_host.c) -----------------
+    // The workspace of the coarse pass, once; the caller has waited for the plan's stream.  The coarse grid is that of
+    // fnft__nse_discretization.c:419-427 for Dsub = D/2.
+    int enable_richardson()
+    {
+        if (rich_child) { rich_on = true; return NFT_SUCCESS; }
+        if (kdv || M == 0 || Din < 3) return NFT_EC_INVALID_ARGUMENT;
+        if (nskip > 1) return NFT_EC_NOT_YET_IMPLEMENTED;
+        size_t Ds = Din / 2;
+        if (Ds < 2) Ds = 2;
+        if (Ds > Din) Ds = Din;
+        rich_nskip = (size_t)std::llround((double)Din / (double)Ds);
+        rich_Dsub = sub_count(Din, rich_nskip);
+        std::unique_ptr<NftPlan> ch(new NftPlan(be, rich_Dsub * (size_t)ups, M, batch, akns_disc, deg0, &tw));
+        if (ups == 2) ch->set_front(Din, rich_nskip, ups);
+        const int rc = ch->init();
+        cplx *q = nullptr, *cs = nullptr;
+        if (rc != NFT_SUCCESS || (ups == 1 && !mem.get(q, batch * rich_Dsub)) || !mem.get(cs, batch * 3 * M)) {
+            (void)be.sync();   // what init enqueued, before the child's blocks go back
+            mem.give_back(q);
+            return rc != NFT_SUCCESS ? rc : NFT_EC_NOMEM;
+        }
+        rich_q = q;
+        rich_cs = cs;
+        rich_child = std::move(ch);
+        rich_on = true;
+        return NFT_SUCCESS;
+    }
+
+    // after run_front / run_tree / run_contspec of the same call (d_q, T: the input samples and their interval; cs: what
+    // run_contspec was given): the coarse pass on the child, then contspec = (sn*contspec - coarse)/sd where
+    // |xi| < 0.9 pi / (2 eps_t_sub), fnft_nsev_host.c (fnft_nsev) in its order
+    int run_richardson(const void *d_q, const double T[2], int kappa, void *d_contspec, const Contspec &cs)
+    {
+        NftPlan &ch = *rich_child;
+        const double eps_t = (T[1] - T[0]) / (double)(Din - 1);
+        const double Tc[2] = {T[0], T[0] + (double)((rich_Dsub - 1) * rich_nskip) * eps_t};
+        const double eps_sub = (Tc[1] - Tc[0]) / (double)(rich_Dsub - 1);
+        double Tsub[2];
+        int rc;
+        if (ups == 1) {
+            GatherParams G;
+            G.q = (const cplx *)d_q; G.out = rich_q;
+            G.D = (long long)Din; G.Dsub = (long long)rich_Dsub; G.nskip = (long long)rich_nskip; G.batch = (long long)batch;
+            be.template run<KDsGather>((int)((batch * rich_Dsub + 255) / 256), 1, G);
+            rc = ch.run_front(rich_q, Tc, kappa, Tsub);
+        } else {
+            rc = ch.run_front(d_q, T, kappa, Tsub);   // resampling of all Din samples, every rich_nskip-th step kept
+        }
+        if (rc == NFT_SUCCESS) rc = ch.run_tree();
+        if (rc != NFT_SUCCESS) return rc;
+        Contspec cc = cs;
+        cc.T[0] = Tsub[0]; cc.T[1] = Tsub[1];
+        rc = ch.run_contspec(rich_cs, cc);
+        if (rc != NFT_SUCCESS) return rc;
+        RichCsParams R;
+        std::memset(&R, 0, sizeof(R));
+        R.c = (cplx *)d_contspec; R.cs = rich_cs;
+        R.M = (long long)M; R.batch = (long long)batch;
+        R.parts = (cs.cstype == 0) ? 1 : (cs.cstype == 1 ? 2 : 3);
+        R.xi0 = cs.XI[0];
+        R.dxi = (cs.XI[1] - cs.XI[0]) / (double)(M - 1);
+        R.bound = 0.9 * std::acos(-1.0) / (2.0 * eps_sub);
+        R.sn = std::pow(eps_sub / eps_t, (double)nft_nse_method_order(cs.nse_disc));
+        R.sd = R.sn - 1.0;
+        be.template run<KRichCombineCs>((int)((batch * M + 255) / 256), 1, R);
+        return NFT_SUCCESS;
+    }
+
     // the root's pending finalize rides on a kernel of the chirp transform (one matrix per signal at the root): on the row
     // kernel, with the root's last inverse column pass on the first column kernel, when that pass is still pending
     // (root_fusable said that this plan's chirp transform can take it; the checks here are about THIS transform); on the
@@ -1015,16 +1094,21 @@ public:
     // device-side status word -> return code (after the stream has been waited for)
     int read_status()
     {
-        int h[4] = {0, 0, 0, 0};
+        int h[4] = {0, 0, 0, 0}, hc[4] = {0, 0, 0, 0};
         be.d2h(h, status, sizeof(h));
+        if (rich_child) be.d2h(hc, rich_child->status, sizeof(hc));
         const int rc = be.sync();
         if (rc != NFT_SUCCESS) return rc;
         // sticky bits of every transform since the last read; cleared here (off the transforms' critical path)
         be.memset0(status, 4 * sizeof(int));
-        last_warn = (h[0] & 4) ? 1 : 0;            // fnft__misc.c:371-381: not an error
+        if (rich_child) be.memset0(rich_child->status, 4 * sizeof(int));
+        last_warn = ((h[0] | hc[0]) & 4) ? 1 : 0;  // fnft__misc.c:371-381: not an error
         if (h[0] & 8) return NFT_EC_INVALID_ARGUMENT;   // real-coefficient path on a potential that is not real
         if (h[0] & 1) return -NFT_EC_OTHER;        // fnft__akns_fscatter.c:122-126 via CHECK_RETCODE
         if (h[0] & 2) return -NFT_EC_DIV_BY_ZERO;  // fnft_nsev.c:850-853 via CHECK_RETCODE
+        // the coarse pass of the Richardson extrapolation: its step-size check and its division, after the fine pass's
+        if (hc[0] & 1) return -NFT_EC_OTHER;
+        if (hc[0] & 2) return -NFT_EC_DIV_BY_ZERO;
         return NFT_SUCCESS;
     }
 };

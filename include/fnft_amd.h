@@ -414,8 +414,21 @@ FNFT_INT fnft_amd_poly_eval_device(FNFT_UINT deg, FNFT_UINT npoly, FNFT_UINT bat
 FNFT_INT fnft_amd_plan_create_sub(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT M, FNFT_UINT batch,
                                   fnft_nse_discretization_t discretization, int device, FNFT_UINT nskip);
 void fnft_amd_plan_destroy(fnft_amd_plan_t *plan);
-/* Bytes of HBM the plan holds. */
+/* Bytes of HBM the plan holds (the workspace of fnft_amd_plan_set_richardson included once it exists). */
 FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan);
+/* Richardson extrapolation (fnft_nsev_opts_t::richardson_extrapolation_flag) for the fnft_amd_nsev_contspec_device
+ * calls that follow: enabled != 0, every call writes, per signal, what fnft_nsev writes to contspec for that signal
+ * alone with the flag set -- a second transform of every other sample on a child plan, combined with the first on the
+ * device where |xi| < 0.9 pi / (2 eps_t_sub) (src/fnft_nsev.c:316-406).  enabled == 0 restores the plain results bit for
+ * bit.  fnft_amd_nsev_contspec_from_tm_device, fnft_amd_nsev_eval_device and fnft_amd_plan_get_transfer_matrix* are not
+ * affected: the plan's last tree run stays the fine one.  fnft_amd_plan_finish returns the fine pass's status if that
+ * is non-zero, else the coarse pass's (its step-size check under 2SPLIT2_MODAL, its division).
+ * The first enabling call waits for the plan's last stream and allocates the coarse pass's workspace; a transform call
+ * still allocates nothing and never waits.  Disabling keeps the workspace, fnft_amd_plan_destroy gives it back.
+ * FNFT_EC_INVALID_ARGUMENT: plan == NULL (before any HIP call), a KdV plan, a plan with M == 0, D < 3 (the stride would
+ * round to 1); FNFT_EC_NOT_YET_IMPLEMENTED: a plan of fnft_amd_plan_create_sub with nskip > 1; FNFT_EC_NOMEM,
+ * FNFT_EC_OTHER as elsewhere. */
+FNFT_INT fnft_amd_plan_set_richardson(fnft_amd_plan_t *plan, int enabled);
 /* Warnings of the last finished call (after fnft_amd_plan_finish): bit 0 = the band-limited resampler of the
  * 4SPLIT4A/B front end found the signal's spectrum not decayed (the reference's "Signal does not appear to be
  * bandlimited" warning, src/private/fnft__misc.c:371-381; the drop-in fnft_nsev prints it through the printf hook). */
@@ -559,8 +572,9 @@ FNFT_INT fnft_amd_nsev_inverse_discrete_device(fnft_amd_inverse_plan_t *plan, co
  * Create-time codes, before any HIP call: FNFT_EC_INVALID_ARGUMENT for plan == NULL, D < 2, K == 0, batch == 0, an
  * unknown discretization, bound_state_localization, bound_state_filtering or discspec_type;
  * FNFT_EC_NOT_YET_IMPLEMENTED for the slow discretizations (BO, CF*, ES4, TES4), a localization other than NEWTON,
- * richardson_extrapolation_flag != 0, and K > 65535 or batch*K > 2^31 - 1 (one workgroup per (signal, eigenvalue) on
- * one grid axis; one lane merges a signal's K values).  Every workspace is allocated at create; a call allocates
+ * richardson_extrapolation_flag != 0 (create keeps refusing the flag in opts: Richardson extrapolation is switched on
+ * for a created plan by fnft_amd_discspec_plan_set_richardson), and K > 65535 or batch*K > 2^31 - 1 (one workgroup per
+ * (signal, eigenvalue) on one grid axis; one lane merges a signal's K values).  Every workspace is allocated at create; a call allocates
  * nothing, never waits for the device and copies nothing to the host.  One workgroup refines one (signal, eigenvalue)
  * pair through all its iterations on chip; signals of up to 2048 preprocessed samples are staged in LDS. */
 typedef struct fnft_amd_discspec_plan fnft_amd_discspec_plan_t;
@@ -568,8 +582,19 @@ FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UIN
                                        fnft_nsev_opts_t const *opts, int device);
 /* Waits for the plan's last stream, then gives its workspace back.  NULL is ignored. */
 void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan);
-/* Bytes of HBM the plan holds. */
+/* Bytes of HBM the plan holds (the workspace of fnft_amd_discspec_plan_set_richardson included once it exists). */
 FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan);
+/* Richardson extrapolation for the fnft_amd_nsev_discspec_device / fnft_amd_nsev_discspec_search_device calls that follow
+ * (plans of either creator): enabled != 0, every call writes, per signal, what fnft_nsev returns in bound_states and
+ * normconsts_or_residues with richardson_extrapolation_flag set (src/fnft_nsev.c:340-364, :406-441) -- a coarse Newton
+ * pass over every other sample started from the fine bound states, then every fine bound state and its nearest coarse
+ * one (closer than eps_t, relative) combined, residues through a' = norming constant / residue; norming constants are
+ * not extrapolated, counts and NaN tails stay.  The coarse pass's status bits are OR-ed into the signal's word.
+ * enabled == 0 restores the plain results bit for bit.
+ * The first enabling call waits for the plan's last stream and allocates the coarse pass's workspace; a transform call
+ * still allocates nothing, never waits and copies nothing to the host.  Disabling keeps the workspace.
+ * FNFT_EC_INVALID_ARGUMENT: plan == NULL (before any HIP call), D < 3; FNFT_EC_NOMEM, FNFT_EC_OTHER as elsewhere. */
+FNFT_INT fnft_amd_discspec_plan_set_richardson(fnft_amd_discspec_plan_t *plan, int enabled);
 /* d_q: batch*D complex128 (device; signal b at +b*D) and d_guesses: batch*K complex128, both NOT modified.
  * d_bound_states: batch*K complex128 out: the first K_out[b] entries of signal b are its bound states in the order
  * fnft_nsev returns them, the rest NaN + NaN i.  d_normconsts_or_residues: NULL (that stage is skipped), or batch*K
@@ -606,7 +631,8 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
  * Create-time codes, before any HIP call: FNFT_EC_INVALID_ARGUMENT for plan == NULL, D < 2, K == 0, batch == 0, an
  * unknown discretization, localization, filtering or discspec_type, and the localization NEWTON (that is
  * fnft_amd_discspec_plan_create); FNFT_EC_NOT_YET_IMPLEMENTED for the slow discretizations,
- * richardson_extrapolation_flag != 0, K > 65535 or batch*K > 2^31 - 1, and more than 16384 roots per signal (the
+ * richardson_extrapolation_flag != 0 (see fnft_amd_discspec_plan_set_richardson), K > 65535 or batch*K > 2^31 - 1, and
+ * more than 16384 roots per signal (the
  * degree of the transfer matrix: Dsub * upsampling factor * degree per sample under SUBSAMPLE_AND_REFINE, with D in
  * place of Dsub under FAST_EIGENVALUE; the drop-in remains the path above it).  Every workspace is allocated at
  * create; a call allocates nothing, never waits for the device and copies nothing to the host. */
