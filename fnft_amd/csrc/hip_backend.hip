@@ -142,7 +142,7 @@ struct DeviceGuard {
 
 // ---- the parts of the plans' entry points that do not depend on the plan -----------------------------------------------
 // One handle for the tree plan and the three batched plans: the back end, the plan core (NftPlan, NftInverseBatch,
-// NftDiscSpecBatch, NftSlowPlan), the device it lives on, the stream of its last call (destroy waits for it), the status
+// NftDiscSpecPlan, NftSlowPlan), the device it lives on, the stream of its last call (destroy waits for it), the status
 // words finish reads back, and the lock that makes calls on one plan take turns.  The public opaque types add their few
 // own fields.
 template <class CoreT> struct PlanHandle {
@@ -163,15 +163,10 @@ struct fnft_amd_inverse_plan : PlanHandle<NftInverseBatch<HipBackend>> {
     int cstype = 0;
     size_t K = 0;                 // fnft_amd_inverse_plan_create_discrete: bound states per signal (>= 1)
 };
-struct fnft_amd_discspec_plan : PlanHandle<NftDiscSpecBatch<HipBackend>> {
+struct fnft_amd_discspec_plan : PlanHandle<NftDiscSpecPlan<HipBackend>> {
     const unsigned long long *last_K = nullptr;   // d_K_out of the last call
     std::vector<unsigned long long> kout;
-    // fnft_amd_discspec_search_plan_create: the guess-free plan in place of `core` (it owns its own NftDiscSpecBatch)
-    std::unique_ptr<NftDiscSpecSearch<HipBackend>> search;
-    std::vector<int> wn;                          // its warning bits, read by finish
-    // fnft_amd_discspec_plan_set_richardson: the stage that follows the fine pass of either core (nft_ds_richardson.h)
-    std::unique_ptr<NftDsRichardson<HipBackend>> rich;
-    bool rich_on = false;
+    std::vector<int> wn;                          // a guess-free plan's warning bits, read by finish
 };
 struct fnft_amd_slow_plan : PlanHandle<NftSlowPlan<HipBackend>> {
     std::vector<int> wn;
@@ -240,6 +235,24 @@ struct PlanCall {
         }
     }
 };
+
+// Richardson extrapolation for the calls that follow, after the entry's own argument checks.  The first enabling call
+// waits for the plan's last stream and allocates the coarse pass (the core's enable_richardson); disabling keeps it.
+template <class H> static FNFT_INT plan_set_richardson(H *plan, int enabled)
+{
+    PlanCall call(plan->mtx, plan->device);
+    if (!call.ok) return FNFT_EC_OTHER;
+    typename H::Core &pl = *plan->core;
+    if (!enabled || pl.rich_ready()) {
+        pl.rich_on = enabled != 0;
+        return FNFT_SUCCESS;
+    }
+    if (plan->be.sync() != NFT_SUCCESS) return FNFT_EC_OTHER;   // what the last call enqueued: the coarse pass's uploads follow
+    const int rc = pl.enable_richardson();
+    (void)plan->be.sync();
+    if (rc != NFT_SUCCESS) return rc;
+    return plan->be.failed ? FNFT_EC_NOMEM : FNFT_SUCCESS;
+}
 
 // finish: wait for the stream and read the status words (read: the core's own call, which fills plan->st), then every
 // signal's word through the plan's mapping to_status(b, word) -- which also stores the plan's second per-signal output
@@ -352,7 +365,7 @@ FNFT_INT fnft_amd_plan_create_sub(fnft_amd_plan_t **plan, FNFT_UINT D, FNFT_UINT
     const int ups = nft_nse_upsampling((int)discretization);
     if (ups == 1 && nskip != 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
     if (ups == 2 && D <= 2) return FNFT_EC_INVALID_ARGUMENT;   // fnft__misc.c:331-332
-    const size_t Dtree = (ups == 1) ? (size_t)D : 2 * Plan::sub_count((size_t)D, (size_t)nskip);
+    const size_t Dtree = (ups == 1) ? (size_t)D : 2 * nft_sub_count((size_t)D, (size_t)nskip);
     auto h = batch_new<fnft_amd_plan>(Dtree, (size_t)M, (size_t)batch, akns, nft_akns_degree(akns));
     if (h) {
         h->nse_disc = (int)discretization;
@@ -368,24 +381,12 @@ void fnft_amd_plan_destroy(fnft_amd_plan_t *plan) { batch_destroy(plan); }
 
 FNFT_UINT fnft_amd_plan_workspace_bytes(const fnft_amd_plan_t *plan) { return plan ? plan->core->workspace_bytes() : 0; }
 
-// Richardson extrapolation for the calls that follow (NftPlan::enable_richardson / run_richardson).  The first enabling
-// call waits for the plan's last stream and allocates the coarse pass's workspace; disabling keeps it.
+// NftPlan::enable_richardson / run_richardson
 FNFT_INT fnft_amd_plan_set_richardson(fnft_amd_plan_t *plan, int enabled)
 {
     if (!plan || plan->kdv_disc >= 0 || plan->core->M == 0 || plan->core->Din < 3) return FNFT_EC_INVALID_ARGUMENT;
     if (plan->core->nskip > 1) return FNFT_EC_NOT_YET_IMPLEMENTED;
-    PlanCall call(plan->mtx, plan->device);
-    if (!call.ok) return FNFT_EC_OTHER;
-    Plan &pl = *plan->core;
-    if (!enabled || pl.rich_child) {
-        pl.rich_on = enabled != 0;
-        return FNFT_SUCCESS;
-    }
-    if (plan->be.sync() != NFT_SUCCESS) return FNFT_EC_OTHER;   // what the last call enqueued: the child's uploads follow it
-    const int rc = pl.enable_richardson();
-    (void)plan->be.sync();
-    if (rc != NFT_SUCCESS) return rc;
-    return plan->be.failed ? FNFT_EC_NOMEM : FNFT_SUCCESS;
+    return plan_set_richardson(plan, enabled);
 }
 
 int fnft_amd_plan_device(const fnft_amd_plan_t *plan) { return plan ? plan->device : -1; }
@@ -1163,7 +1164,24 @@ FNFT_INT fnft_amd_inverse_plan_finish(fnft_amd_inverse_plan_t *plan, void *strea
 
 // ---- batched, device-resident discrete spectrum of fnft_nsev (NEWTON) ----------------------------------------------
 // Size and option checks follow fnft_nsev (fnft_nsev_host.c) in its order, with its codes and message texts, and run
-// before any HIP call.
+// before any HIP call.  Both create entries make the same handle (core: NftDiscSpecPlan, nft_discspec_plan.h); each
+// keeps its own list of checks, and they share the list's end -- the message of its refusal, or NULL:
+static const char *discspec_create_refused(const fnft_nsev_opts_t &o, FNFT_UINT K, FNFT_UINT batch)
+{
+    if (o.richardson_extrapolation_flag != 0)   // fnft_amd_discspec_plan_set_richardson switches it on
+        return "Not yet implemented (batched discrete spectrum: Richardson extrapolation).";
+    if (K > NftDiscSpecBatch<HipBackend>::kMaxK || batch > NftDiscSpecBatch<HipBackend>::kMaxGroups / K)
+        return "Not yet implemented (batched discrete spectrum: K > 65535 or batch*K > 2^31 - 1).";
+    return nullptr;
+}
+static NftDsOpts discspec_opts(const fnft_nsev_opts_t &o)
+{
+    NftDsOpts d;
+    d.bsfilt = (int)o.bound_state_filtering; d.bsloc = (int)o.bound_state_localization; d.niter = o.niter;
+    d.Dsub = o.Dsub; d.dstype = (int)o.discspec_type; d.nse_disc = (int)o.discretization; d.richardson = 0;
+    return d;
+}
+
 FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UINT D, FNFT_UINT K, FNFT_UINT batch,
                                        fnft_nsev_opts_t const *opts, int device)
 {
@@ -1187,65 +1205,39 @@ FNFT_INT fnft_amd_discspec_plan_create(fnft_amd_discspec_plan_t **plan, FNFT_UIN
     if (loc != (int)fnft_nsev_bsloc_NEWTON)
         return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
                                "Not yet implemented (batched discrete spectrum: FAST_EIGENVALUE and SUBSAMPLE_AND_REFINE).");
-    if (o.richardson_extrapolation_flag != 0)
-        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
-                               "Not yet implemented (batched discrete spectrum: Richardson extrapolation).");
-    if (K > NftDiscSpecBatch<HipBackend>::kMaxK || batch > NftDiscSpecBatch<HipBackend>::kMaxGroups / K)
-        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
-                               "Not yet implemented (batched discrete spectrum: K > 65535 or batch*K > 2^31 - 1).");
-    NftDsOpts d;
-    d.bsfilt = (int)o.bound_state_filtering; d.bsloc = 1; d.niter = o.niter; d.Dsub = 0;
-    d.dstype = (int)o.discspec_type; d.nse_disc = disc; d.richardson = 0;
+    if (const char *msg = discspec_create_refused(o, K, batch))
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__, msg);
+    NftDsOpts d = discspec_opts(o);   // bsloc 1: a guess plan
+    d.Dsub = 0;
     return batch_init(plan, batch_new<fnft_amd_discspec_plan>((size_t)D, (size_t)K, (size_t)batch, d), device);
 }
 
-void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan)
-{
-    if (!plan) return;
-    {   // batch_destroy with the plan's other owners: on the plan's device, after everything it enqueued
-        DeviceGuard dg(plan->device);
-        plan_quiesce(plan->last_stream);
-        plan->rich.reset();
-        plan->search.reset();
-        plan->core.reset();
-        plan->be.destroy_events();
-    }
-    delete plan;
-}
+void fnft_amd_discspec_plan_destroy(fnft_amd_discspec_plan_t *plan) { batch_destroy(plan); }
 
 FNFT_UINT fnft_amd_discspec_plan_workspace_bytes(const fnft_amd_discspec_plan_t *plan)
 {
-    if (!plan) return 0;
-    return (plan->search ? plan->search->workspace_bytes() : plan->core->workspace_bytes())
-           + (plan->rich ? plan->rich->workspace_bytes() : 0);
+    return plan ? plan->core->workspace_bytes() : 0;
 }
 
-// Richardson extrapolation for the calls that follow, on a plan of either creator.  The first enabling call waits for
-// the plan's last stream and allocates the coarse pass's workspace; disabling keeps it.
+// on a plan of either creator (NftDiscSpecPlan::enable_richardson)
 FNFT_INT fnft_amd_discspec_plan_set_richardson(fnft_amd_discspec_plan_t *plan, int enabled)
 {
     SEAM_CHECK(!plan, plan);
-    const size_t D = plan->search ? plan->search->D : plan->core->D;
-    SEAM_CHECK(D < 3, D);
-    PlanCall call(plan->mtx, plan->device);
+    SEAM_CHECK(plan->core->D < 3, D);
+    return plan_set_richardson(plan, enabled);
+}
+
+// one call of either kind of plan; d_guesses NULL: a guess-free plan
+static FNFT_INT discspec_run(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T, const void *d_guesses,
+                             void *d_bound_states, void *d_normconsts_or_residues, void *d_K_out, void *stream,
+                             const char *func, int line)
+{
+    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
     if (!call.ok) return FNFT_EC_OTHER;
-    if (!enabled || plan->rich) {
-        plan->rich_on = enabled != 0;
-        return FNFT_SUCCESS;
-    }
-    if (plan->be.sync() != NFT_SUCCESS) return FNFT_EC_OTHER;   // what the last call enqueued
-    // the coarse pass is a Newton pass with the caller's niter, whatever found the fine bound states
-    const size_t K = plan->search ? plan->search->K : plan->core->K;
-    const size_t batch = plan->search ? plan->search->batch : plan->core->batch;
-    const NftDsOpts &o = plan->search ? plan->search->o : plan->core->o;
-    std::unique_ptr<NftDsRichardson<HipBackend>> r(new (std::nothrow) NftDsRichardson<HipBackend>(plan->be, D, K, batch, o));
-    if (!r) return FNFT_EC_NOMEM;
-    const int rc = r->init();
-    (void)plan->be.sync();
-    if (rc != NFT_SUCCESS || plan->be.failed) return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;   // r hands its blocks back
-    plan->rich = std::move(r);
-    plan->rich_on = true;
-    return FNFT_SUCCESS;
+    plan->last_K = (const unsigned long long *)d_K_out;
+    const int rc = plan->core->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
+                                   (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
+    return batch_run_result(plan->be, rc, func, line);
 }
 
 FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
@@ -1258,17 +1250,9 @@ FNFT_INT fnft_amd_nsev_discspec_device(fnft_amd_discspec_plan_t *plan, const voi
     SEAM_CHECK(!d_guesses, guesses);
     SEAM_CHECK(!d_bound_states, bound_states);
     SEAM_CHECK(!d_K_out, K_out);
-    if (plan->search) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));   // a guess-free plan
-    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
-    if (!call.ok) return FNFT_EC_OTHER;
-    plan->last_K = (const unsigned long long *)d_K_out;
-    const int rc = plan->rich_on
-                       ? plan->rich->run_after(*plan->core, (const cplx *)d_q, T, (const cplx *)d_guesses,
-                                               (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
-                                               (unsigned long long *)d_K_out)
-                       : plan->core->run((const cplx *)d_q, T, (const cplx *)d_guesses, (cplx *)d_bound_states,
-                                         (cplx *)d_normconsts_or_residues, (unsigned long long *)d_K_out);
-    return batch_run_result(plan->be, rc, __func__, __LINE__);
+    if (plan->core->guess_free()) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));
+    return discspec_run(plan, d_q, T, d_guesses, d_bound_states, d_normconsts_or_residues, d_K_out, stream, __func__,
+                        __LINE__);
 }
 
 FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *stream, FNFT_INT *status,
@@ -1277,10 +1261,7 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
     SEAM_CHECK(!plan, plan);
     return batch_finish(
         plan, stream, status,
-        [&] {
-            if (plan->search) return plan->search->read(plan->st, plan->kout, plan->wn, plan->last_K);
-            return plan->core->read(plan->st, plan->kout, plan->last_K);
-        },
+        [&] { return plan->core->read(plan->st, plan->kout, plan->wn, plan->last_K); },
         [&](size_t b, int h) -> FNFT_INT {
             if (K_out) K_out[b] = (FNFT_UINT)plan->kout[b];
             if (h & 8) return -FNFT_EC_OTHER;   // guess-free plans: the root finder did not converge (poly_roots_fasteigen)
@@ -1295,19 +1276,11 @@ FNFT_INT fnft_amd_discspec_plan_finish(fnft_amd_discspec_plan_t *plan, void *str
 }
 
 // ---- the same without guesses: FAST_EIGENVALUE and SUBSAMPLE_AND_REFINE (nft_discspec_search.h) --------------------
-static NftDsOpts search_opts(const fnft_nsev_opts_t &o)
-{
-    NftDsOpts d;
-    d.bsfilt = (int)o.bound_state_filtering; d.bsloc = (int)o.bound_state_localization; d.niter = o.niter;
-    d.Dsub = o.Dsub; d.dstype = (int)o.discspec_type; d.nse_disc = (int)o.discretization; d.richardson = 0;
-    return d;
-}
-
 FNFT_UINT fnft_amd_discspec_search_plan_roots(FNFT_UINT D, fnft_nsev_opts_t const *opts, FNFT_UINT *Dsub)
 {
     const fnft_nsev_opts_t o = opts ? *opts : fnft_nsev_default_opts();
     size_t ds = 0, nskip = 1, roots = 0;
-    NftDiscSpecSearch<HipBackend>::sizes((size_t)D, search_opts(o), &ds, &nskip, &roots);
+    NftDiscSpecSearch<HipBackend>::sizes((size_t)D, discspec_opts(o), &ds, &nskip, &roots);
     if (Dsub) *Dsub = (FNFT_UINT)ds;
     return (FNFT_UINT)roots;
 }
@@ -1331,32 +1304,15 @@ FNFT_INT fnft_amd_discspec_search_plan_create(fnft_amd_discspec_plan_t **plan, F
     if (slow)
         return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
                                "Not yet implemented (discretization). GPU path covers the fast (polynomial) discretizations.");
-    if (o.richardson_extrapolation_flag != 0)
-        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
-                               "Not yet implemented (batched discrete spectrum: Richardson extrapolation).");
-    if (K > NftDiscSpecBatch<HipBackend>::kMaxK || batch > NftDiscSpecBatch<HipBackend>::kMaxGroups / K)
-        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
-                               "Not yet implemented (batched discrete spectrum: K > 65535 or batch*K > 2^31 - 1).");
-    const NftDsOpts d = search_opts(o);
+    if (const char *msg = discspec_create_refused(o, K, batch))
+        return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__, msg);
+    const NftDsOpts d = discspec_opts(o);
     size_t ds = 0, nskip = 1, roots = 0;
     NftDiscSpecSearch<HipBackend>::sizes((size_t)D, d, &ds, &nskip, &roots);
     if (roots > NftDiscSpecSearch<HipBackend>::kMaxRoots)
         return fnft_amd__raise(FNFT_EC_NOT_YET_IMPLEMENTED, __func__, __LINE__,
                                "Not yet implemented (batched discrete spectrum: more than 16384 roots per signal).");
-    std::unique_ptr<fnft_amd_discspec_plan> h(new (std::nothrow) fnft_amd_discspec_plan());
-    if (h) h->search.reset(new (std::nothrow) NftDiscSpecSearch<HipBackend>(h->be, (size_t)D, (size_t)K, (size_t)batch, d));
-    if (!h || !h->search) return FNFT_EC_NOMEM;
-    DeviceGuard dg(device);
-    if (!dg.ok) return FNFT_EC_OTHER;
-    h->device = device;
-    const int rc = h->search->init();
-    if (rc != NFT_SUCCESS || h->be.failed) {
-        (void)h->be.sync();
-        h.reset();                // on the plan's device
-        return rc != NFT_SUCCESS ? rc : FNFT_EC_NOMEM;
-    }
-    *plan = h.release();
-    return FNFT_SUCCESS;
+    return batch_init(plan, batch_new<fnft_amd_discspec_plan>((size_t)D, (size_t)K, (size_t)batch, d), device);
 }
 
 FNFT_INT fnft_amd_nsev_discspec_search_device(fnft_amd_discspec_plan_t *plan, const void *d_q, const FNFT_REAL *T,
@@ -1368,23 +1324,9 @@ FNFT_INT fnft_amd_nsev_discspec_search_device(fnft_amd_discspec_plan_t *plan, co
     SEAM_CHECK(T == NULL || T[0] >= T[1], T);
     SEAM_CHECK(!d_bound_states, bound_states);
     SEAM_CHECK(!d_K_out, K_out);
-    if (!plan->search) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));   // a guess plan
-    PlanCall call(plan->mtx, plan->device, plan->be, &plan->last_stream, stream);
-    if (!call.ok) return FNFT_EC_OTHER;
-    plan->last_K = (const unsigned long long *)d_K_out;
-    int rc;
-    if (plan->rich_on) {
-        NftDsRichardson<HipBackend> &r = *plan->rich;
-        rc = plan->search->run((const cplx *)d_q, T, (cplx *)d_bound_states, r.fine_nc((cplx *)d_normconsts_or_residues),
-                               (unsigned long long *)d_K_out, r.fine_dstype());
-        if (rc == NFT_SUCCESS)
-            rc = r.run((const cplx *)d_q, T, (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
-                       (unsigned long long *)d_K_out, plan->search->refine->status);
-    } else {
-        rc = plan->search->run((const cplx *)d_q, T, (cplx *)d_bound_states, (cplx *)d_normconsts_or_residues,
-                               (unsigned long long *)d_K_out);
-    }
-    return batch_run_result(plan->be, rc, __func__, __LINE__);
+    if (!plan->core->guess_free()) return inv_subroutine(__func__, __LINE__, seam_invalid(__func__, __LINE__, "plan"));
+    return discspec_run(plan, d_q, T, nullptr, d_bound_states, d_normconsts_or_residues, d_K_out, stream, __func__,
+                        __LINE__);
 }
 
 // per-launch timers of the plan's calls, as fnft_amd_plan_set_launch_timing and its two readers
@@ -1414,8 +1356,7 @@ FNFT_INT fnft_amd_discspec_plan_warnings(const fnft_amd_discspec_plan_t *plan, i
 {
     SEAM_CHECK(!plan, plan);
     SEAM_CHECK(!warnings, warnings);
-    const size_t nb = plan->search ? plan->search->batch : plan->core->batch;
-    for (size_t b = 0; b < nb; b++) warnings[b] = (b < plan->wn.size()) ? plan->wn[b] : 0;
+    for (size_t b = 0; b < plan->core->batch; b++) warnings[b] = (b < plan->wn.size()) ? plan->wn[b] : 0;
     return FNFT_SUCCESS;
 }
 

@@ -16,9 +16,7 @@
 
 #include "nft_api.h"
 #include "nft_discspec.h"
-#include "nft_discspec_batch.h"
-#include "nft_discspec_search.h"
-#include "nft_ds_richardson.h"
+#include "nft_discspec_plan.h"
 #include "nft_nsev_slow.h"
 
 extern thread_local std::string g_last_error;   // defined in hip_backend.hip

@@ -128,17 +128,12 @@ public:
         if (akns < 0) return NFT_EC_INVALID_ARGUMENT;
         P.ups = nft_nse_upsampling(nse_disc);
         P.deg0 = nft_akns_degree(akns);
-        size_t Dsub = Dsub_wish;
-        if (Dsub < 2) Dsub = 2;
-        if (Dsub > D) Dsub = D;
-        const size_t nskip = (size_t)std::llround((double)D / (double)Dsub);
-        Dsub = (size_t)std::llround((double)D / (double)nskip);
-        const double eps_in = (T[1] - T[0]) / (double)(D - 1);
+        const NftSubGrid g = nft_sub_grid(D, Dsub_wish);
+        const size_t Dsub = g.Dsub, nskip = g.nskip;
         P.Dsub = Dsub;
         P.Deff = Dsub * (size_t)P.ups;
         P.T[0] = T[0];
-        P.T[1] = T[0] + (double)((Dsub - 1) * nskip) * eps_in;
-        P.eps_t = (P.T[1] - P.T[0]) / (double)(Dsub - 1);
+        nft_sub_interval(T, D, Dsub, nskip, &P.T[1], &P.eps_t);
         std::vector<cd> hq;
         const cd *src = q;
         size_t Din = D;

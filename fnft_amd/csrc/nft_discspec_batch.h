@@ -6,7 +6,7 @@
 //   box kernel -> Newton kernel (all iterations on chip) -> filter + merge kernel -> norming kernel
 // 4SPLIT4A/B refine on the resampled signal of that scheme's front end (NftResampler::run_4split4, qpre).
 // set_front(Din, nskip): the D samples are every nskip-th of Din input samples (the coarse pass of the Richardson
-// extrapolation, nft_ds_richardson.h) -- gathered (KDsGather) or, for 4SPLIT4A/B, resampled from all Din samples.
+// extrapolation, nft_discspec_plan.h) -- gathered (KDsGather) or, for 4SPLIT4A/B, resampled from all Din samples.
 // Back-end independent like NftDiscSpec: hip_backend.hip instantiates it with the HIP back end, tests/emu with the
 // lane emulator.
 #pragma once
@@ -47,14 +47,14 @@ public:
         sphi = ((size_t)G / (size_t)ups + 1) * (size_t)kDsLanes * 2;
     }
 
-    // call before init(): this plan's D = NftPlan::sub_count(Din_, nskip_) samples are every nskip_-th of Din_
+    // call before init(): this plan's D = nft_sub_count(Din_, nskip_) samples are every nskip_-th of Din_
     void set_front(size_t Din_, size_t nskip_) { Din = Din_; nskip = nskip_; }
 
     int init()
     {
         if (akns < 0 || deg0 == 0 || D < 2 || K == 0 || batch == 0) return NFT_EC_INVALID_ARGUMENT;
         if (Din == 0) { Din = D; nskip = 1; }
-        if (nskip < 1 || D != NftPlan<BE>::sub_count(Din, nskip) || (D - 1) * nskip >= Din) return NFT_EC_INVALID_ARGUMENT;
+        if (nskip < 1 || D != nft_sub_count(Din, nskip) || (D - 1) * nskip >= Din) return NFT_EC_INVALID_ARGUMENT;
         if (K > kMaxK || batch > kMaxGroups / K || Dq > (size_t)0x7fffffff * (size_t)kDsLanes)
             return NFT_EC_NOT_YET_IMPLEMENTED;
         if (ups == 2) {
@@ -88,10 +88,9 @@ public:
     int run(const cplx *d_q, const double T[2], const cplx *d_guess, cplx *d_bs, cplx *d_nc,
             unsigned long long *d_K, const unsigned long long *d_nguess = nullptr, int dstype = -1)
     {
-        // grid and step as NftDiscSpec::prepare forms them (the full signal: Dsub = D, nskip = 1)
-        const double eps_in = (T[1] - T[0]) / (double)(Din - 1);
-        const double T1 = T[0] + (double)((D - 1) * nskip) * eps_in;
-        const double eps_t = (T1 - T[0]) / (double)(D - 1);
+        // grid and step as NftDiscSpec::prepare forms them (without set_front the full signal: Dsub = D, nskip = 1)
+        double T1, eps_t;
+        nft_sub_interval(T, Din, D, nskip, &T1, &eps_t);
         be.memset0(status, batch * sizeof(int));
         if (ups == 2) {
             const int rc = rs.run_4split4(d_q, nskip, D, qpre, rs.ft.status);   // the band check's bit: read by nobody

@@ -40,10 +40,8 @@ public:
         if (o.bsloc == 2) {
             Dsub = o.Dsub;
             if (Dsub == 0) Dsub = (size_t)std::sqrt((double)D * std::log2((double)D) * std::log2((double)D));
-            if (Dsub < 2) Dsub = 2;
-            if (Dsub > D) Dsub = D;
-            nskip = (size_t)std::llround((double)D / (double)Dsub);
-            Dsub = (size_t)std::llround((double)D / (double)nskip);
+            const NftSubGrid g = nft_sub_grid(D, Dsub);
+            Dsub = g.Dsub; nskip = g.nskip;
         }
         *Dsub_out = Dsub;
         *nskip_out = nskip;
@@ -116,9 +114,8 @@ public:
     int run(const cplx *d_q, const double T[2], cplx *d_bs, cplx *d_nc, unsigned long long *d_K, int dstype = -1)
     {
         // grid of the subsampled signal, NftDiscSpec::prepare
-        const double eps_in = (T[1] - T[0]) / (double)(D - 1);
-        const double Ts1 = T[0] + (double)((Dsub - 1) * nskip) * eps_in;
-        const double eps_s = (Ts1 - T[0]) / (double)(Dsub - 1);
+        double Ts1, eps_s;
+        nft_sub_interval(T, D, Dsub, nskip, &Ts1, &eps_s);
         be.memset0(sstatus, batch * sizeof(int));
         be.memset0(warn, batch * sizeof(int));
         const cplx *qs = d_q;     // preprocessed samples of the signal the roots belong to

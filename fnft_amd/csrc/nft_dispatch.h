@@ -93,7 +93,7 @@ constexpr int kPolyEvalTile = 512;
 template <bool DERIV> FA_FUNCTOR(KPolyEval, PolyEvalParams, 256, 2 * kPolyEvalTile * sizeof(cplx),
                                 (body_polyeval<kPolyEvalTile, DERIV>));
 FA_FUNCTOR(KPolyJoin, PolyEvalParams, 256, 0, body_polyjoin);
-// Richardson extrapolation of the batched plans (NftPlan::run_richardson, nft_ds_richardson.h)
+// Richardson extrapolation of the batched plans (NftPlan::run_richardson, nft_discspec_plan.h)
 FA_FUNCTOR(KRichCombineCs, RichCsParams, 256, 0, body_rich_combine_cs);
 FA_FUNCTOR(KRichMatchDs, RichDsParams, 256, kRichTile * sizeof(cplx), body_rich_match_ds);
 template <int DEG> struct LeafCfg {

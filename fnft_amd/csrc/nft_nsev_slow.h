@@ -149,12 +149,9 @@ public:
         ntile = (M + kSlowLanes - 1) / kSlowLanes;
         nchunk = nft_slow_chunks(D, M, batch, &L);
         gsize = nft_slow_group(nchunk);
-        if (o.richardson) {   // subsampling rule of fnft__nse_discretization.c:423-430 for Dsub = CEIL(D/2), fnft_nsev.c:376
-            size_t Ds = D / 2;
-            if (Ds < 2) Ds = 2;
-            if (Ds > D) Ds = D;
-            nskip2 = (size_t)std::llround((double)D / (double)Ds);
-            D2 = (size_t)std::llround((double)D / (double)nskip2);
+        if (o.richardson) {   // nft_sub_grid for Dsub = D/2, fnft_nsev.c:376
+            const NftSubGrid g = nft_sub_grid(D, D / 2);
+            nskip2 = g.nskip; D2 = g.Dsub;
             nchunk2 = (D2 + L - 1) / L;
         }
     }
@@ -262,10 +259,10 @@ public:
         if (rc != NFT_SUCCESS) return rc;
         phase_factors(T, eps_t, P.pf);
         if (o.richardson) {
-            const double Tsub[2] = {T[0], T[0] + (double)((D2 - 1) * nskip2) * eps_t};
+            double Tsub[2] = {T[0], 0.0}, eps_sub;
+            nft_sub_interval(T, D, D2, nskip2, &Tsub[1], &eps_sub);
             rc = pass(P, d_q, D2, nskip2, Tsub, eps_t, false, rec2, cm2, nchunk2, cmr2);
             if (rc != NFT_SUCCESS) return rc;
-            const double eps_sub = (Tsub[1] - Tsub[0]) / (double)(D2 - 1);
             phase_factors(Tsub, eps_sub, P.pf2);
             P.cm2 = cmr2 ? cmr2 : cm2;
             P.nchunk2 = (int)(cmr2 ? groups(nchunk2) : nchunk2);

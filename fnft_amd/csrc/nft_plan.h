@@ -23,6 +23,7 @@
 
 #include "nft_chirp.h"
 #include "nft_schemes.h"
+#include "nft_sub_grid.h"
 
 // fnft__akns_discretization.c:29-67 restricted to what the coefficient kernel implements
 inline int nft_akns_degree(int akns_disc)
@@ -244,11 +245,11 @@ public:
     int tune_fuse_root = 1;  // 0: the tree always runs its last inverse column pass itself (A/B runs of ChirpParams::root_fused)
     int dbg_flags = 0;       // timing ablation: only builds with -DFNFT_AMD_ABLATION ever set it (hip_backend.hip)
     // Richardson extrapolation of the continuous spectrum (enable_richardson, run_richardson): a child plan over every
-    // rich_nskip-th sample on the same back end, fed by KDsGather through rich_q (upsampling factor 1) or with the
+    // rich_g.nskip-th sample on the same back end, fed by KDsGather through rich_q (upsampling factor 1) or with the
     // caller's samples and the stride (4SPLIT4A/B: the resampler sees all of them); its spectrum goes to rich_cs
     std::unique_ptr<NftPlan> rich_child;
     cplx *rich_q = nullptr, *rich_cs = nullptr;
-    size_t rich_Dsub = 0, rich_nskip = 1;
+    NftSubGrid rich_g{0, 1};
     bool rich_on = false;
 
     // borrowed: the twiddle tables of the class this plan is a part of (KdV plans: with the lengths 3*2^b); without it the
@@ -262,9 +263,8 @@ public:
         plane = n0 * (size_t)deg0;
     }
 
-    // fnft__nse_discretization.c:419-427: samples kept when every nskip-th of Din is used
-    static size_t sub_count(size_t Din_, size_t nskip_) { return (size_t)std::llround((double)Din_ / (double)nskip_); }
-    // call before init(): this plan was constructed with D = ups_ * sub_count(Din_, nskip_)
+    static size_t sub_count(size_t Din_, size_t nskip_) { return nft_sub_count(Din_, nskip_); }   // its name on the tree plan
+    // call before init(): this plan was constructed with D = ups_ * nft_sub_count(Din_, nskip_)
     void set_front(size_t Din_, size_t nskip_, int ups_) { Din = Din_; nskip = nskip_; ups = ups_; }
     // largest pair product done by one workgroup.  General (4-entry) form: 2048 -- a 4096-point pair needs 8 + 4
     // transforms of 16 points per lane in one workgroup (616 B of scratch per lane, 75 us for ONE pair); as a split
@@ -276,7 +276,7 @@ public:
         if (D < 1 || batch < 1 || deg0 < 1) return NFT_EC_INVALID_ARGUMENT;
         if (Din == 0) Din = D;
         if (ups == 1 && (nskip != 1 || Din != D)) return NFT_EC_NOT_YET_IMPLEMENTED;
-        if (ups == 2 && (Din <= 2 || D != 2 * sub_count(Din, nskip))) return NFT_EC_INVALID_ARGUMENT;
+        if (ups == 2 && (Din <= 2 || D != 2 * nft_sub_count(Din, nskip))) return NFT_EC_INVALID_ARGUMENT;
         // largest product transform of the tree and chirp length must be within the split limits
         if (nft_tree_too_large(D, deg0)) return NFT_EC_NOT_YET_IMPLEMENTED;
         bool ok = true;
@@ -360,9 +360,9 @@ public:
             return run_coeffs(d_q, kdv ? rneg : nullptr, eps_in, kappa);
         }
         const size_t Dsub = D / 2;
+        double eps_t;
         Tsub[0] = T[0];
-        Tsub[1] = T[0] + (double)((Dsub - 1) * nskip) * eps_in;
-        const double eps_t = (Tsub[1] - Tsub[0]) / (double)(Dsub - 1);
+        nft_sub_interval(T, Din, Dsub, nskip, &Tsub[1], &eps_t);
         const int rc = rs.run_4split4(d_q, nskip, Dsub, qpre, status);
         if (rc != NFT_SUCCESS) return rc;
         return run_coeffs(qpre, nullptr, eps_t, kappa, false);
@@ -918,22 +918,19 @@ public:
 
     // ---- Richardson extrapolation of the continuous spectrum (src/fnft_nsev.c:316-406, fnft_nsev_host.c) -----------------
     // The workspace of the coarse pass, once; the caller has waited for the plan's stream.  The coarse grid is that of
-    // fnft__nse_discretization.c:419-427 for Dsub = D/2.
+    // nft_sub_grid for Dsub = D/2.
+    bool rich_ready() const { return (bool)rich_child; }
     int enable_richardson()
     {
         if (rich_child) { rich_on = true; return NFT_SUCCESS; }
         if (kdv || M == 0 || Din < 3) return NFT_EC_INVALID_ARGUMENT;
         if (nskip > 1) return NFT_EC_NOT_YET_IMPLEMENTED;
-        size_t Ds = Din / 2;
-        if (Ds < 2) Ds = 2;
-        if (Ds > Din) Ds = Din;
-        rich_nskip = (size_t)std::llround((double)Din / (double)Ds);
-        rich_Dsub = sub_count(Din, rich_nskip);
-        std::unique_ptr<NftPlan> ch(new NftPlan(be, rich_Dsub * (size_t)ups, M, batch, akns_disc, deg0, &tw));
-        if (ups == 2) ch->set_front(Din, rich_nskip, ups);
+        rich_g = nft_sub_grid(Din, Din / 2);
+        std::unique_ptr<NftPlan> ch(new NftPlan(be, rich_g.Dsub * (size_t)ups, M, batch, akns_disc, deg0, &tw));
+        if (ups == 2) ch->set_front(Din, rich_g.nskip, ups);
         const int rc = ch->init();
         cplx *q = nullptr, *cs = nullptr;
-        if (rc != NFT_SUCCESS || (ups == 1 && !mem.get(q, batch * rich_Dsub)) || !mem.get(cs, batch * 3 * M)) {
+        if (rc != NFT_SUCCESS || (ups == 1 && !mem.get(q, batch * rich_g.Dsub)) || !mem.get(cs, batch * 3 * M)) {
             (void)be.sync();   // what init enqueued, before the child's blocks go back
             mem.give_back(q);
             return rc != NFT_SUCCESS ? rc : NFT_EC_NOMEM;
@@ -952,18 +949,18 @@ public:
     {
         NftPlan &ch = *rich_child;
         const double eps_t = (T[1] - T[0]) / (double)(Din - 1);
-        const double Tc[2] = {T[0], T[0] + (double)((rich_Dsub - 1) * rich_nskip) * eps_t};
-        const double eps_sub = (Tc[1] - Tc[0]) / (double)(rich_Dsub - 1);
+        double Tc[2] = {T[0], 0.0}, eps_sub;
+        nft_sub_interval(T, Din, rich_g.Dsub, rich_g.nskip, &Tc[1], &eps_sub);
         double Tsub[2];
         int rc;
         if (ups == 1) {
             GatherParams G;
             G.q = (const cplx *)d_q; G.out = rich_q;
-            G.D = (long long)Din; G.Dsub = (long long)rich_Dsub; G.nskip = (long long)rich_nskip; G.batch = (long long)batch;
-            be.template run<KDsGather>((int)((batch * rich_Dsub + 255) / 256), 1, G);
+            G.D = (long long)Din; G.Dsub = (long long)rich_g.Dsub; G.nskip = (long long)rich_g.nskip; G.batch = (long long)batch;
+            be.template run<KDsGather>((int)((batch * rich_g.Dsub + 255) / 256), 1, G);
             rc = ch.run_front(rich_q, Tc, kappa, Tsub);
         } else {
-            rc = ch.run_front(d_q, T, kappa, Tsub);   // resampling of all Din samples, every rich_nskip-th step kept
+            rc = ch.run_front(d_q, T, kappa, Tsub);   // resampling of all Din samples, every rich_g.nskip-th step kept
         }
         if (rc == NFT_SUCCESS) rc = ch.run_tree();
         if (rc != NFT_SUCCESS) return rc;

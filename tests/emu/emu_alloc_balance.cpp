@@ -8,7 +8,7 @@
 
 thread_local fa_emu_ctx *fa_emu = nullptr;
 
-#include "../../fnft_amd/csrc/nft_discspec_batch.h"
+#include "../../fnft_amd/csrc/nft_discspec_plan.h"
 #include "../../fnft_amd/csrc/nft_nsev_inverse.h"
 #include "../../fnft_amd/csrc/nft_nsev_slow.h"
 
@@ -32,8 +32,17 @@ struct CountingBackend : EmuBackend {
     }
 };
 
+// the options of kind 7 (those of kind 2 with a[4] as the localization): FULL, niter 10, the default Dsub, BOTH
+static NftDsOpts ds_plan_opts(const long long *a)
+{
+    NftDsOpts o;
+    o.bsfilt = 2; o.bsloc = (int)a[4]; o.niter = 10; o.Dsub = 0; o.dstype = 2; o.nse_disc = (int)a[3]; o.richardson = 0;
+    return o;
+}
+
 // init() of one plan or part; *class_bytes: its own count while it is alive (a part: the count of the arena it was given);
-// *inner_bytes: kind 6 only, the count of the plan without the tables it borrows
+// *inner_bytes: kind 6, the count of the plan without the tables it borrows; kind 7, what a failing enable_richardson()
+// left wrong (0: nothing)
 static int init_one(CountingBackend &be, int kind, const long long *a, size_t *class_bytes, size_t *inner_bytes)
 {
     typedef CountingBackend BE;
@@ -97,6 +106,23 @@ static int init_one(CountingBackend &be, int kind, const long long *a, size_t *c
         *class_bytes = mem.bytes + pl.mem.bytes;
         return rc;
     }
+    case 7: {   // NftDiscSpecPlan: a = {D, K, batch, nse_disc, bsloc, Richardson}
+        NftDiscSpecPlan<BE> pl(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], ds_plan_opts(a));
+        int rc = pl.init();
+        if (rc == NFT_SUCCESS && a[5]) {
+            const size_t before = be.live.size();
+            rc = pl.enable_richardson();
+            if (rc != NFT_SUCCESS) {   // blocks it left behind while the plan lives; 2^20: the plan no longer runs as it did
+                cplx *dummy = (cplx *)pl.fine_status();   // schedule-only: no kernel reads the caller's arrays
+                const double T[2] = {-1.0, 1.0};
+                const bool runs = !pl.rich_on && !pl.rich_ready()
+                                  && pl.run(dummy, T, dummy, dummy, dummy, (unsigned long long *)dummy) == NFT_SUCCESS;
+                *inner_bytes = (be.live.size() - before) + (runs ? 0 : (size_t)1 << 20);
+            }
+        }
+        *class_bytes = pl.workspace_bytes();
+        return rc;
+    }
     default: return -1;
     }
 }
@@ -104,7 +130,8 @@ static int init_one(CountingBackend &be, int kind, const long long *a, size_t *c
 extern "C" {
 
 // out = {requests made, blocks live after the plan is gone, bytes requested and served, the plan's own byte count,
-// bad frees, kind 6: the plan's count without the borrowed tables}; returns init()'s code
+// bad frees, kind 6: the plan's count without the borrowed tables, kind 7: what a failing enable_richardson() left wrong};
+// returns init()'s code (kind 7 with Richardson: enable_richardson()'s after a successful init())
 int emu_alloc_balance(int kind, const long long *a, long fail_at, unsigned long long *out)
 {
     CountingBackend be;
@@ -125,7 +152,7 @@ int emu_alloc_balance(int kind, const long long *a, long fail_at, unsigned long 
 }
 
 // Schedule of one run() of a batched plan class without executing it (schedule-only mode, as emu_tree_schedule of
-// emu_main.cpp): kind and a as in init_one (kinds 1 .. 3); the names of every kernel that init() and run() launch,
+// emu_main.cpp): kind and a as in init_one (kinds 1 .. 3 and 7); the names of every kernel that init() and run() launch,
 // '\n'-separated, into out[cap].  Nothing executes, so one dummy address stands for every device array of the caller.
 // Returns the plan's rc, or -1 if out is too small.
 int emu_plan_schedule(int kind, const long long *a, char *out, size_t cap)
@@ -148,6 +175,12 @@ int emu_plan_schedule(int kind, const long long *a, char *out, size_t cap)
         NftDiscSpecBatch<EmuBackend> ds(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], o);
         rc = ds.init();
         if (rc == NFT_SUCCESS) rc = ds.run(dummy, T, dummy, dummy, dummy, (unsigned long long *)dummy);
+    } else if (kind == 7) {
+        NftDiscSpecPlan<EmuBackend> pl(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], ds_plan_opts(a));
+        rc = pl.init();
+        if (rc == NFT_SUCCESS && a[5]) rc = pl.enable_richardson();
+        if (rc == NFT_SUCCESS)
+            rc = pl.run(dummy, T, pl.guess_free() ? nullptr : dummy, dummy, dummy, (unsigned long long *)dummy);
     } else if (kind == 3) {
         NftInverseBatch<EmuBackend> inv(be, (size_t)a[0], (size_t)a[1], (size_t)a[2], (int)a[3], (size_t)a[4], (int)a[5],
                                         (size_t)a[6], (int)a[7], (int)a[8]);

@@ -66,3 +66,10 @@ struct EmuBackend {
             }
     }
 };
+
+// the same with one segment per sweep of the guess-free discrete spectrum (kTargetWorkgroups decides the segments of a
+// plan): every emulated workgroup is 256 host threads, and the fixed schedule launches all of them whether or not a
+// signal has converged
+struct EmuBackendOneSegment : EmuBackend {
+    static constexpr size_t kTargetWorkgroups = 1;
+};

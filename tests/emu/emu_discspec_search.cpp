@@ -7,12 +7,6 @@ thread_local fa_emu_ctx *fa_emu = nullptr;
 
 #include "../../fnft_amd/csrc/nft_discspec_search.h"
 
-// the emulator's back end with one segment per sweep (kTargetWorkgroups decides the segments of a plan): every emulated
-// workgroup is 256 host threads, and the fixed schedule launches all of them whether or not a signal has converged
-struct EmuBackendOneSegment : EmuBackend {
-    static constexpr size_t kTargetWorkgroups = 1;
-};
-
 template <class BE>
 static int run_search(size_t D, size_t K, size_t batch, const NftDsOpts &o, const cplx *q, const double *T, cplx *bound_states,
                       cplx *normconsts, unsigned long long *K_out, int *status, int *warn, size_t *sizes)

@@ -215,7 +215,7 @@ int emu_tree_schedule(int entry, size_t D, int disc, size_t batch, int real, cha
     if (entry == 1) {
         akns = nft_nse_to_akns(disc);
         ups = nft_nse_upsampling(disc);
-        Dtree = (ups == 1) ? D : 2 * NftPlan<EmuBackend>::sub_count(D, 1);
+        Dtree = (ups == 1) ? D : 2 * nft_sub_count(D, 1);
     } else if (entry == 2) {
         akns = disc;
     } else if (entry == 3) {
@@ -287,7 +287,7 @@ int emu_chirp_schedule(int entry, size_t n, size_t M, int disc, size_t batch, in
         const int akns = nft_nse_to_akns(disc);
         const int ups = nft_nse_upsampling(disc);
         if (akns >= 0) {
-            const size_t Dtree = (ups == 1) ? n : 2 * P::sub_count(n, 1);
+            const size_t Dtree = (ups == 1) ? n : 2 * nft_sub_count(n, 1);
             P pl(be, Dtree, M, batch, akns, nft_akns_degree(akns));
             pl.set_front(n, 1, ups);
             rc = pl.init();

@@ -1,11 +1,11 @@
 // emu_richardson.cpp -- builds tests/emu/libfnft_emu_richardson.so: Richardson extrapolation of the batched nsev plans
-// (NftPlan::enable_richardson / run_richardson, nft_ds_richardson.h, KRichCombineCs, KRichMatchDs) in the CPU lane
+// (NftPlan::enable_richardson / run_richardson, nft_discspec_plan.h, KRichCombineCs, KRichMatchDs) in the CPU lane
 // emulator (TEST INFRASTRUCTURE ONLY; see emu_backend.h).
 #include "emu_backend.h"
 
 thread_local fa_emu_ctx *fa_emu = nullptr;
 
-#include "../../fnft_amd/csrc/nft_ds_richardson.h"
+#include "../../fnft_amd/csrc/nft_discspec_plan.h"
 
 extern "C" {
 
@@ -38,27 +38,26 @@ int emu_rich_contspec(size_t D, size_t M, size_t batch, int disc, int kappa, int
     return pl.read_status();
 }
 
-// The guess plan (NftDiscSpecBatch) with fnft_amd_discspec_plan_set_richardson(plan, richardson) before the call; every
-// array in host memory, status: the device status words
-int emu_rich_discspec(size_t D, size_t K, size_t batch, int nse_disc, size_t niter, int bsfilt, int dstype, int richardson,
-                      const cplx *q, const double *T, const cplx *guesses, cplx *bound_states, cplx *normconsts,
-                      unsigned long long *K_out, int *status)
+// The discrete-spectrum plan (NftDiscSpecPlan) as fnft_amd_nsev_discspec_device / fnft_amd_nsev_discspec_search_device
+// drive it, with fnft_amd_discspec_plan_set_richardson(plan, richardson) before the call.  bsloc 1: a guess plan; 0, 2:
+// a guess-free plan (guesses NULL, Dsub as in the options; one segment per sweep).  Every array in host memory, status:
+// the device status words
+int emu_rich_discspec(size_t D, size_t K, size_t batch, int nse_disc, int bsloc, size_t niter, size_t Dsub, int bsfilt,
+                      int dstype, int richardson, const cplx *q, const double *T, const cplx *guesses, cplx *bound_states,
+                      cplx *normconsts, unsigned long long *K_out, int *status)
 {
-    EmuBackend be;
+    EmuBackendOneSegment be;
     NftDsOpts o;
-    o.bsfilt = bsfilt; o.bsloc = 1; o.niter = niter; o.Dsub = 0; o.dstype = dstype; o.nse_disc = nse_disc;
+    o.bsfilt = bsfilt; o.bsloc = bsloc; o.niter = niter; o.Dsub = Dsub; o.dstype = dstype; o.nse_disc = nse_disc;
     o.richardson = 0;
-    NftDiscSpecBatch<EmuBackend> ds(be, D, K, batch, o);
-    NftDsRichardson<EmuBackend> rich(be, D, K, batch, o);
+    NftDiscSpecPlan<EmuBackendOneSegment> ds(be, D, K, batch, o);
     int rc = ds.init();
-    if (rc == NFT_SUCCESS && richardson) rc = rich.init();
-    if (rc != NFT_SUCCESS) return rc;
-    rc = richardson ? rich.run_after(ds, q, T, guesses, bound_states, normconsts, K_out)
-                    : ds.run(q, T, guesses, bound_states, normconsts, K_out);
+    if (rc == NFT_SUCCESS && richardson) rc = ds.enable_richardson();
+    if (rc == NFT_SUCCESS) rc = ds.run(q, T, guesses, bound_states, normconsts, K_out);
     if (rc == NFT_SUCCESS) {
-        std::vector<int> st;
+        std::vector<int> st, wn;
         std::vector<unsigned long long> ko;
-        rc = ds.read(st, ko, K_out);
+        rc = ds.read(st, ko, wn, K_out);
         for (size_t b = 0; b < batch; b++) status[b] = st[b];
     }
     return rc;

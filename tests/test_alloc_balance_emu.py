@@ -5,8 +5,11 @@ back end saw requested; an init() that finds no memory at its n-th request, for 
 block behind either, and no block is ever handed back twice.  The parts a plan is made of (twiddle tables, any-length
 DFT, resampler: fnft_amd/csrc/nft_twiddles.h, nft_chirp.h) stand alone under the same assertions, and a tree plan on
 borrowed tables requests what the owning plan requests minus the tables.
+The discrete-spectrum plan (nft_discspec_plan.h) stands under them with its Richardson stage enabled, as a guess plan
+and as a guess-free one: enable_richardson() failing at any request leaves no block behind and the plan as it was.
 The same library records the launches of one run() of the batched plan classes (emu_plan_schedule): which kernels the
-parts contribute to them.  No kernel executes.  No GPU needed."""
+parts contribute to them, and that a call with the stage is the plain call followed by the coarse pass and one match
+kernel.  No kernel executes.  No GPU needed."""
 import ctypes as C
 import os
 import re
@@ -22,7 +25,7 @@ EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libfnft_emu_alloc_balance.so")
 CSRC = os.path.join(ROOT, "fnft_amd", "csrc")
 
-PLAN, SLOW, DISCSPEC, INVERSE, RESAMPLER, ANYDFT, PLAN_BORROWED = 0, 1, 2, 3, 4, 5, 6
+PLAN, SLOW, DISCSPEC, INVERSE, RESAMPLER, ANYDFT, PLAN_BORROWED, DISCSPEC_PLAN = 0, 1, 2, 3, 4, 5, 6, 7
 D = capi.NSE_DISC
 CASES = {
     # NftPlan: D of the tree, M, batch, akns discretization, its degree, input samples, upsampling, kdv
@@ -34,6 +37,9 @@ CASES = {
     "slow-BO-reduce": (SLOW, [4096, 16, 1, D["BO"], 2, 0]),                    # >= 64 chunks: the reduce stage's buffers
     # NftDiscSpecBatch: D, K, batch, discretization
     "discspec-4SPLIT4B": (DISCSPEC, [64, 3, 2, D["4SPLIT4B"]]),
+    # NftDiscSpecPlan: D, K, batch, discretization, localization (1: guess plan, 2: guess-free), Richardson stage enabled
+    "discspec-plan-4SPLIT4B-guess-richardson": (DISCSPEC_PLAN, [64, 3, 2, D["4SPLIT4B"], 1, 1]),
+    "discspec-plan-2SPLIT2A-search-richardson": (DISCSPEC_PLAN, [64, 3, 2, D["2SPLIT2A"], 2, 1]),
     # NftInverseBatch: D, M, batch, cstype, oversampling, modal, K, discrete mode, residues
     "inverse-b-of-xi-K2": (INVERSE, [512, 512, 2, 1, 8, 1, 2, 1, 1]),          # 512 > leaf: work arrays and sub-plans
     "inverse-M0-K2": (INVERSE, [512, 0, 2, 0, 8, 1, 2, 0, 0]),
@@ -80,9 +86,25 @@ def test_arena_balances(emu, case):
     assert nalloc > 0 and live == 0 and bad == 0
     assert class_bytes == requested
     for n in range(nalloc):
-        rc, _, live, _, _, bad, _ = run(emu, kind, args, n)
+        rc, _, live, _, _, bad, extra = run(emu, kind, args, n)
         assert rc != 0, (case, n)
         assert live == 0 and bad == 0, (case, n, live, bad)
+        if kind == DISCSPEC_PLAN:      # a failing enable_richardson(): no block behind while the plan lives, and it still runs
+            assert extra == 0, (case, n, extra)
+
+
+@pytest.mark.parametrize("case", sorted(k for k, v in CASES.items() if v[0] == DISCSPEC_PLAN))
+def test_enable_richardson_fails_at_every_request(emu, case):
+    """The requests of enable_richardson() alone (those after init()'s): each in turn finds no memory."""
+    kind, args = CASES[case]
+    plain = run(emu, kind, args[:5] + [0], -1)
+    full = run(emu, kind, args, -1)
+    assert plain[0] == 0 and full[0] == 0 and full[1] > plain[1] and full[3] > plain[3]
+    for n in range(plain[1], full[1]):
+        rc, _, live, requested, class_bytes, bad, extra = run(emu, kind, args, n)
+        assert rc != 0 and live == 0 and bad == 0 and extra == 0, (case, n, rc, live, bad, extra)
+        assert class_bytes == plain[4] == plain[3]     # the plan's count is that of the plan without the stage
+        assert requested >= plain[3]                   # init() was served in full
 
 
 @pytest.mark.parametrize("case", sorted(BORROWED))
@@ -164,3 +186,37 @@ def test_inverse_dfts_run_at_their_own_length(emu):
     assert [c for k, c, _ in ck if k == "KChirpColFwd"] == want
     assert [c for k, c, _ in ck if k == "KChirpColInv"] == want
     assert n1(512) != n1(4104)
+
+
+# ---- the discrete-spectrum plan: one statement of "fine pass, then stage" ------------------------------------------------
+DS_PLAN = [64, 3, 2]                                               # D, K, batch
+COARSE_TAIL = ["KDsBox", "KDsNewton", "KDsFilter", "KDsNorm", "KRichMatchDs"]
+
+
+def base(names):
+    """kernel names without their template arguments"""
+    return [n.split("<")[0] for n in names]
+
+
+@pytest.mark.parametrize("disc,bsloc,front", [("4SPLIT4B", 1, "resampler"), ("2SPLIT2A", 2, "gather")])
+def test_discspec_plan_schedules(emu, disc, bsloc, front):
+    """NftDiscSpecPlan, guess plan and guess-free plan: with the stage, a call is the plain call followed by the coarse
+    front (KDsGather, or the resampler's launches), the coarse pass's box, Newton, filter and norming kernels and one
+    KRichMatchDs, last.  The guess plan's plain call is NftDiscSpecBatch's."""
+    plain = schedule(emu, DISCSPEC_PLAN, DS_PLAN + [D[disc], bsloc, 0])
+    rich = schedule(emu, DISCSPEC_PLAN, DS_PLAN + [D[disc], bsloc, 1])
+    if bsloc == 1:
+        assert plain == schedule(emu, DISCSPEC, DS_PLAN + [D[disc]])
+    else:
+        assert "KDsCandidates" in plain and "KAberthBStart" in plain
+    assert rich[:len(plain)] == plain and "KRichMatchDs" not in plain
+    tail = rich[len(plain):]
+    cut = tail.index("KDsBox")
+    coarse_front, coarse = tail[:cut], tail[cut:]
+    if front == "gather":
+        assert coarse_front == ["KDsGather"]
+    else:       # the resampler over all D samples: forward DFT, band check, phase ramps, inverse DFTs, combination
+        assert [k for k, _, _ in chirp_kinds(coarse_front)] == DFT_TRIPLE * 2
+        assert [n for n in coarse_front if not n.startswith("KChirp")] == ["KBandCheck", "KResamplePhase", "KResampleCombine"]
+    assert base(coarse) == COARSE_TAIL, coarse
+    assert rich.count("KRichMatchDs") == 1 and rich[-1] == "KRichMatchDs"

@@ -1,6 +1,7 @@
 """Richardson extrapolation of the batched nsev plans in the CPU lane emulator, executing: the tree plan with
-NftPlan::enable_richardson (child plan, KDsGather or the resampler's stride, KRichCombineCs), the guess plan with the
-stage of nft_ds_richardson.h (coarse NftDiscSpecBatch, KRichMatchDs), and KRichMatchDs alone on synthetic arrays.
+NftPlan::enable_richardson (child plan, KDsGather or the resampler's stride, KRichCombineCs), the discrete-spectrum plan
+of nft_discspec_plan.h with its stage (guess plan and guess-free plan; coarse NftDiscSpecBatch, KRichMatchDs), and
+KRichMatchDs alone on synthetic arrays.
 Against the oracle's restatement of fnft_nsev with richardson_extrapolation_flag = 1, signal by signal.  No GPU needed."""
 import ctypes as C
 import os
@@ -36,14 +37,15 @@ def emu():
     deps = [os.path.join(EMU_DIR, f) for f in ("emu_richardson.cpp", "emu_backend.h")]
     deps += [os.path.join(CSRC, f) for f in ("dev_compat.h", "fft_dev.h", "nft_kernels.h", "nft_real.h", "nft_dispatch.h",
                                              "nft_kernel_list.h", "nft_plan.h", "nft_chirp.h", "nft_twiddles.h",
-                                             "nft_arena.h", "nft_schemes.h", "nft_discspec.h", "nft_discspec_batch.h",
-                                             "nft_ds_richardson.h")]
+                                             "nft_arena.h", "nft_schemes.h", "nft_sub_grid.h", "nft_discspec.h",
+                                             "nft_discspec_batch.h", "nft_discspec_search.h", "nft_discspec_plan.h")]
     if not os.path.exists(EMU_LIB) or max(map(os.path.getmtime, deps)) > os.path.getmtime(EMU_LIB):
         subprocess.check_call(["g++", "-std=c++20", "-O2", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas",
                                "-o", EMU_LIB, os.path.join(EMU_DIR, "emu_richardson.cpp")])
     L = C.CDLL(EMU_LIB)
     L.emu_rich_contspec.argtypes = [sz, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.emu_rich_discspec.argtypes = [sz, sz, sz, C.c_int, sz, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.emu_rich_discspec.argtypes = [sz, sz, sz, C.c_int, C.c_int, sz, sz, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
+                                    vp]
     L.emu_rich_match.argtypes = [sz, sz, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.emu_rich_kernel_list.argtypes = [C.c_int, C.c_char_p, sz]
     return L
@@ -82,18 +84,22 @@ def test_contspec_vs_oracle_and_mask(emu, oracle, disc, D, lo, hi, cname, oname,
 
 
 # ---- discrete spectrum --------------------------------------------------------------------------------------------
-def run_discspec(emu, disc, q, g, richardson, niter=10, bsfilt=2, dstype=2, want_nc=True):
+BSLOC = {"FAST_EIGENVALUE": 0, "NEWTON": 1, "SUBSAMPLE_AND_REFINE": 2}
+
+
+def run_discspec(emu, disc, q, g, richardson, niter=10, bsfilt=2, dstype=2, want_nc=True, bsloc="NEWTON", Dsub=0, K=None):
+    """g: the guesses of a guess plan; None: a guess-free plan with room for K bound states per signal."""
     B, D = q.shape
-    K = g.shape[1]
+    K = g.shape[1] if g is not None else K
     bs = np.zeros((B, K), np.complex128)
     nc = np.zeros((B, 2 * K if dstype == 2 else K), np.complex128) if want_nc else None
     ko = np.zeros(B, np.uint64)
     st = np.zeros(B, np.int32)
-    q0, g0 = q.copy(), g.copy()
-    rc = emu.emu_rich_discspec(D, K, B, NSE_DISC[disc], niter, bsfilt, dstype, int(richardson), _P(q), _P(np.array(DC.T)),
-                               _P(g), _P(bs), _P(nc), _P(ko), _P(st))
+    q0, g0 = q.copy(), None if g is None else g.copy()
+    rc = emu.emu_rich_discspec(D, K, B, NSE_DISC[disc], BSLOC[bsloc], niter, Dsub, bsfilt, dstype, int(richardson), _P(q),
+                               _P(np.array(DC.T)), _P(g), _P(bs), _P(nc), _P(ko), _P(st))
     assert rc == 0, rc
-    assert np.array_equal(q, q0) and np.array_equal(g, g0)
+    assert np.array_equal(q, q0) and (g is None or np.array_equal(g, g0))
     return bs, nc, ko.astype(int), st
 
 
@@ -139,6 +145,41 @@ def test_discspec_output_layouts(emu):
         assert np.array_equal(bs, bs2, equal_nan=True) and np.array_equal(ko, ko2)
     assert np.array_equal(nc1, nc2[:, K:], equal_nan=True)
     assert np.array_equal(nc0, nc2[:, :K], equal_nan=True)
+
+
+SEARCH_CASES = [("2SPLIT4B", 256), ("4SPLIT4B", 128)]     # the coarse pass gathers; the coarse pass resamples
+
+
+@pytest.mark.parametrize("disc,D", SEARCH_CASES)
+def test_search_plan_vs_oracle(emu, oracle, disc, D):
+    """The guess-free plan (SUBSAMPLE_AND_REFINE, FULL, niter = 10, BOTH) with the stage: the one statement of "fine
+    pass, then stage" that the library runs, against the oracle's fnft_nsev with the flag, as sets per signal.
+    Measured (2SPLIT4B / 4SPLIT4B): bound states within 6.7e-16 / 1.7e-15, norming constants 1.2e-15 / 1.7e-15, residues
+    1.3e-14 / 8.6e-15, counts [2, 2, 3] -- what the shim's two former statements gave when transcribed over the emulator."""
+    K, pairs = 4, DC.PAIRS[1:4]
+    q = np.stack([DC.signal(D, A, c) for A, c in pairs])
+    kw = dict(bsloc="SUBSAMPLE_AND_REFINE", K=K)
+    bs, nc, ko, st = run_discspec(emu, disc, q, None, True, **kw)
+    bs0, nc0, ko0, st0 = run_discspec(emu, disc, q, None, False, **kw)
+    assert not st.any() and not st0.any()
+    assert np.array_equal(ko, ko0)
+    for b in range(len(pairs)):
+        rc, bs_o, nc_o, res_o = oracle.fnft_nsev_ds(q[b], DC.T, disc, bsloc="SUBSAMPLE_AND_REFINE", bsfilt="FULL", niter=10,
+                                                    richardson=True)
+        assert rc == 0
+        k = bs_o.size
+        assert ko[b] == k, (b, ko[b], bs[b], bs_o)
+        order = [int(np.abs(bs[b, :k] - x).argmin()) for x in bs_o]      # nearest pairs, one to one
+        assert sorted(order) == list(range(k))
+        e_bs = np.abs(bs[b, order] - bs_o).max()
+        e_nc = (np.abs(nc[b, :K][order] - nc_o) / np.abs(nc_o)).max()
+        e_res = (np.abs(nc[b, K:][order] - res_o) / np.abs(res_o)).max()
+        print(disc, D, "signal", b, "K_out", k, "|bs - oracle| %.2e  nc rel %.2e  res rel %.2e" % (e_bs, e_nc, e_res))
+        assert e_bs < ORACLE_BS_ABS
+        assert e_nc < ORACLE_NC_REL and e_res < ORACLE_NC_REL
+        # norming constants are not extrapolated; every bound state and residue is
+        assert np.array_equal(nc[b, :k], nc0[b, :k])
+        assert (bs[b, :k] != bs0[b, :k]).all() and (nc[b, K:K + k] != nc0[b, K:K + k]).all()
 
 
 # ---- the match kernel alone ---------------------------------------------------------------------------------------
